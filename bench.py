@@ -20,6 +20,14 @@ roofline = algorithmic bytes per launch (2048 B in + 1 B symbol + 4K B
 magnitudes per window) / mean batch duration from HIP events
 recorded on the launch stream, vs the 8 TB/s HBM peak. traffic = HBM bytes per
 launch from the committed rocprofv3 PMC summary (profiles/), or null.
+
+A plain run (`--gpus N --steps K --warmup W`) does what that figure needs and
+no more: set up, warm up, time the K steps, write the outputs if
+--dump-outputs DIR is given (the last timed step's symbols and magnitudes as
+DIR/<name>.npy, float32, at most 64 MB), print the line. Everything below
+(cpu_baseline, parity_all, parity_sample, rescue, sustained and the extra
+entries) is measured only with --full.
+
 cpu_baseline = the oracle's C restatement (OpenMP over the host cores this
 process may use) on a bounded sample of the same windows (rank 0, N = 1 only),
 median of >= 5 timed repetitions; its output doubles as a parity check of the
@@ -28,7 +36,7 @@ histogram SURVEY §7 asks for, at sigma 400 and at the sigma 2000 stress level).
 rescue = the same step with the decision rescue switched off
 (FSKD_NO_RESCUE=1), i.e. the rescue's cost.
 
-Extra entries of the default run:
+Extra entries of a --full run:
   * N = 1: configs[2] (8-FSK) "fsk8"; configs[3] (sliding FFT, hop 256)
     "fft_hop256" with an oracle parity sample of 16384 consecutive windows, and
     with the full 513-bin spectrum stored, "fft_hop256_spectrum"; configs[4]
@@ -42,7 +50,7 @@ Extra entries of the default run:
 
 Defaults: 200 timed steps after 20 warmup steps (the warmup is at least 64
 launches, MIN_WARMUP), so each config keeps the GPU busy for 0.1-0.5 s
-rather than a few ms. "sustained" (N = 1 headline, --sustain 6): the same
+rather than a few ms. "sustained" (N = 1 headline, --full --sustain 6): the same
 step back to back for ~6 s, the steady rate over seconds, during which an
 outside utilisation sampler sees the GPU busy.
 """
@@ -416,14 +424,56 @@ def c_group_bucket(A, D, torch, dist, cfg, n_streams, rank, world, group, dev, w
         cg.close()
 
 
+DUMP_CAP_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together stay below this
+DUMP_SEED = 0x0D0FF5
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: write each (name, array) as out_dir/<name>.npy in
+    float32 (float64 arrays stay float64). `array` is a numpy array or a
+    device tensor, its first axis the windows. If all of them together would
+    exceed `cap` bytes, every array keeps the same fraction of its rows: a
+    fixed sample (sorted, drawn without replacement from a generator seeded
+    with DUMP_SEED and the row count), so two builds dump the same rows.
+    Returns {name: rows written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [(name, a) for name, a in arrays if a is not None]
+
+    def nbytes_as_written(a):
+        per = 8 if str(a.dtype).endswith("float64") else 4
+        n = 1
+        for s in a.shape:
+            n *= int(s)
+        return n * per
+
+    data = sum(nbytes_as_written(a) for _, a in arrays)
+    head = 128 * len(arrays)   # the .npy headers
+    frac = 1.0 if data + head <= cap else max(0.0, (cap - head) / float(data))
+    written = {}
+    for name, a in arrays:
+        rows = int(a.shape[0])
+        if frac < 1.0:
+            keep = max(1, int(rows * frac * 0.999))
+            idx = np.sort(np.random.default_rng([DUMP_SEED, rows]).choice(rows, keep, replace=False))
+            a = a[idx] if isinstance(a, np.ndarray) else a[torch_like(a, idx)]
+        if not isinstance(a, np.ndarray):
+            a = a.cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = int(a.shape[0])
+    return written
+
+
 def run_config(A, D, torch, dist, args, config, rank, world, local, use_dist, steps, warmup,
                plan="survey", method_name="auto", hop_fft=256, no_mags=False, spectrum=False,
                rescue_ab=False, parity_windows=0, n_streams_total=1024, sustain_s=0.0,
-               parity_every=0, group=None, fft_plan="fsk2"):
+               parity_every=0, group=None, fft_plan="fsk2", dump_dir=None):
     """Allocate, synthesise, warm up and time one workload; returns a dict.
     fft_plan: configs[3]'s tone plan (fsk2, or fsk8: the plan-independent
     work, every post-pass block of the FFT's tones-only kernel that a
-    full 8-tone plan touches)."""
+    full 8-tone plan touches). dump_dir: rank 0 writes the
+    last timed step's outputs there (dump_outputs) before anything else
+    touches the output buffers."""
     freqs = A.FSK8_FREQS if (config == "fsk8" or (config == "fft" and fft_plan == "fsk8")) else A.FSK2_FREQS
     if config == "fsk8" and plan == "odd":
         freqs = tuple(46.875 * (32 + 9 * i) for i in range(8))
@@ -799,6 +849,14 @@ def run_config(A, D, torch, dist, args, config, rank, world, local, use_dist, st
     else:
         step_w = n // hop
         sym_err = int((d_sym[::step_w][:W] != d_true).sum().item())
+    dumped = None
+    if dump_dir and rank == 0:
+        # what a caller of the timed path holds after its last step: the
+        # symbols, the tone powers and (configs[3] --spectrum) the spectrum
+        dumped = dump_outputs(dump_dir, [("symbols", d_sym),
+                                         ("magnitudes", d_magR[-n_eval:] if (bucket and ring is not None
+                                                                             and d_magR is not None) else d_mag),
+                                         ("spectrum", d_spec)])
     framed = None
     if dev_framing and bucket:
         # the last bucket's frames of every rank, every step: each must decode
@@ -887,7 +945,7 @@ def run_config(A, D, torch, dist, args, config, rank, world, local, use_dist, st
             "timed": "the whole batch: detector launch(es) + the rescue launch (HIP events)",
         },
         "d_pcm": d_pcm, "d_sym": d_sym, "d_mag": d_mag, "d_true": d_true, "cfg": cfg,
-        "spectrum": d_spec is not None,
+        "spectrum": d_spec is not None, "dumped": dumped,
     }
     if dev_framing and bucket is not None and bucket.get("det_graph_ms"):
         # configs[4] on the step's own timing basis: the
@@ -1605,7 +1663,24 @@ def main():
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="nccl (= RCCL over xGMI) on the real node; gloo only to rehearse the "
                          "multi-rank path with several ranks sharing one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the CPU "
+                         "baseline and its parity samples, parity of every timed window, the rescue "
+                         "A/B, the sustained rate and the extra entries (other configs, host_e2e, "
+                         "error_model, rescue_worst, quiet_cost, streams; at N > 1 configs[4]). "
+                         "Without it the run sets up, warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (rank 0: symbols, "
+                         "magnitudes, and the spectrum with --spectrum) as DIR/<name>.npy in float32, at "
+                         "most 64 MB in all (a fixed seeded sample of the rows beyond that)")
     args = ap.parse_args()
+    if not args.full:
+        if args.extras_only:
+            ap.error("--extras-only picks among the entries of --full: add --full")
+        # the headline figure alone: no CPU baseline or parity pass, no rescue
+        # A/B, no sustained run, no extra entries
+        args.no_cpu_baseline = args.no_extras = args.no_rescue_ab = True
+        args.sustain = 0.0
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -1642,7 +1717,7 @@ def main():
                    rescue_ab=plain and args.config in ("fsk2", "fsk8", "fft") and not args.no_rescue_ab,
                    sustain_s=args.sustain if plain and args.config == "fsk2" and not args.no_extras else 0.0,
                    parity_every=1
-                   if plain and not args.no_cpu_baseline else 0)
+                   if plain and not args.no_cpu_baseline else 0, dump_dir=args.dump_outputs)
 
     extras = {}
     guard = None
@@ -1891,6 +1966,9 @@ def headline_line(args, r, world, extras) -> dict:
         out["parity_all"] = r["parity_all"]
     if r["framed"]:
         out["framing"] = r["framed"]
+    if r.get("dumped"):
+        out["dump_outputs"] = {"dir": args.dump_outputs, "rows": r["dumped"],
+                               "what": "the last timed step's outputs (rank 0), <name>.npy"}
     out.update(extras)
     return out
 

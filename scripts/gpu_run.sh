@@ -5,11 +5,11 @@
 #   tests            pytest -m gpu (whole suite)
 #   tests:<expr>     pytest -m gpu -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
+#   bench            the whole line: bench.py --gpus 1 --steps 20 --warmup 5 --full
 #   benchq[:<args>]  headline only (no CPU baseline / extras / rescue A/B), extra bench args
-#   benchcfg:<args>  bench.py --no-cpu-baseline <args> (e.g. "--config fsk8")
-#   ab:<N>:<envA>:<envB>:<args>  N interleaved rounds of bench.py <args> with env A, env B
-#   kt               rocprofv3 --kernel-trace --stats of the driver's command
+#   benchcfg:<args>  bench.py --full --no-cpu-baseline <args> (e.g. "--config fsk8")
+#   ab:<N>:<envA>:<envB>:<args>  N interleaved rounds of bench.py --full <args> with env A, env B
+#   kt               rocprofv3 --kernel-trace --stats of the bench step's command
 #   pmc              HBM PMC passes (FETCH_SIZE, WRITE_SIZE separately): fsk2, fsk8, fft, fft+spectrum
 #   sq[:<args>]      one SQ pass (issue counts) of the tones-only FFT kernel
 #   sqw[:<ENV=V|-> <args>]  one SQ pass of its wait states (SQ_WAIT_ANY / _INST_ANY / _INST_LDS)
@@ -42,19 +42,19 @@ for st in "$@"; do
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$log" 2>&1 || exit $? ;;
     bench)
-      timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$log" 2>&1 || exit $? ;;
+      timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$log" 2>&1 || exit $? ;;
     benchq)
       timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-rescue-ab --no-extras --sustain 0 --steps 100 --warmup 10 $arg > "$log" 2>&1 || exit $? ;;
     benchcfg)
-      timeout -k 10 400 python3 bench.py --no-cpu-baseline $arg > "$log" 2>&1 || exit $? ;;
+      timeout -k 10 400 python3 bench.py --full --no-cpu-baseline $arg > "$log" 2>&1 || exit $? ;;
     ab)
       IFS=: read -r n ea eb rest <<< "$arg"
       for r in $(seq 1 "$n"); do
-        env $ea timeout -k 10 200 python3 bench.py --no-cpu-baseline $rest > "$O/$(printf %02d $i)_ab_A_$r.log" 2>&1 || exit $?
-        env $eb timeout -k 10 200 python3 bench.py --no-cpu-baseline $rest > "$O/$(printf %02d $i)_ab_B_$r.log" 2>&1 || exit $?
+        env $ea timeout -k 10 200 python3 bench.py --full --no-cpu-baseline $rest > "$O/$(printf %02d $i)_ab_A_$r.log" 2>&1 || exit $?
+        env $eb timeout -k 10 200 python3 bench.py --full --no-cpu-baseline $rest > "$O/$(printf %02d $i)_ab_B_$r.log" 2>&1 || exit $?
       done ;;
     kt)
-      (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o run -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --sustain 0) > "$log" 2>&1 || exit $? ;;
+      (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o run -- python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --sustain 0) > "$log" 2>&1 || exit $? ;;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
         for cfg in fsk2 fsk8; do

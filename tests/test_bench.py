@@ -54,8 +54,51 @@ def test_bench_help_lists_the_contract_flags():
                        capture_output=True, timeout=120, cwd=ROOT)
     out = r.stdout.decode()
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--dist-backend", "--no-extras"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--dist-backend", "--no-extras",
+                 "--full", "--dump-outputs"):
         assert flag in out
+
+
+def test_extras_only_needs_full():
+    """--extras-only picks among the entries of --full: alone it is an error,
+    said before any GPU call."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--extras-only", "fsk8"],
+                       capture_output=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and b"--full" in r.stderr
+
+
+def test_dump_outputs_writes_float32_and_samples_past_the_cap(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every array as <name>.npy in
+    float32 with the values unchanged; past the byte cap each array keeps the
+    same seeded, sorted sample of its rows, identical from call to call, and
+    the files together stay below the cap."""
+    import torch
+    rng = np.random.default_rng(5)
+    sym = rng.integers(0, 2, 1000).astype(np.uint8)
+    mag = rng.random((1000, 2)).astype(np.float32)
+    rows = bench.dump_outputs(str(tmp_path / "a"), [("symbols", torch.from_numpy(sym)),
+                                                    ("magnitudes", torch.from_numpy(mag)),
+                                                    ("spectrum", None)])
+    assert rows == {"symbols": 1000, "magnitudes": 1000}
+    assert sorted(os.listdir(tmp_path / "a")) == ["magnitudes.npy", "symbols.npy"]
+    s = np.load(tmp_path / "a" / "symbols.npy")
+    m = np.load(tmp_path / "a" / "magnitudes.npy")
+    assert s.dtype == np.float32 and m.dtype == np.float32
+    assert np.array_equal(s, sym.astype(np.float32)) and np.array_equal(m, mag)
+    cap = 6000
+    for d in ("b", "c"):
+        rows = bench.dump_outputs(str(tmp_path / d), [("symbols", torch.from_numpy(sym)),
+                                                      ("magnitudes", mag)], cap=cap)
+    assert rows["symbols"] == rows["magnitudes"] < 1000
+    total = sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c"))
+    assert cap // 2 < total <= cap
+    s_b, s_c = np.load(tmp_path / "b" / "symbols.npy"), np.load(tmp_path / "c" / "symbols.npy")
+    m_c = np.load(tmp_path / "c" / "magnitudes.npy")
+    assert np.array_equal(s_b, s_c)
+    # the rows kept are rows of the input, in order, the same for both arrays
+    idx = np.sort(np.random.default_rng([bench.DUMP_SEED, 1000]).choice(1000, rows["symbols"],
+                                                                       replace=False))
+    assert np.array_equal(s_c, sym[idx].astype(np.float32)) and np.array_equal(m_c, mag[idx])
 
 
 def test_decision_checker_requires_the_oracle_symbol_everywhere():

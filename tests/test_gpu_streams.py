@@ -33,7 +33,7 @@ def test_config5_streams_rccl_gather_world1():
     env.pop("MASTER_PORT", None)
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--config", "streams",
                         "--force-dist", "--dist-backend", "nccl", "--steps", "20", "--warmup", "5",
-                        "--cpu-seconds", "2"],
+                        "--full", "--cpu-seconds", "2"],
                        capture_output=True, timeout=400, cwd=ROOT, env=env)
     out = r.stdout.decode()
     assert r.returncode == 0, (out[-2000:], r.stderr.decode()[-4000:])
@@ -130,7 +130,7 @@ def test_config5_capture_failure_mid_capture_world1():
 def test_config5_rank_shard_world1():
     """One rank's shard of the 8-GPU configs[4] run (128 of the 1024 streams)
     through the same graph step at world size 1: the streams_shard entry and
-    projected_scaling_8 of the default bench line."""
+    projected_scaling_8 of the --full bench line."""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
@@ -205,7 +205,7 @@ def test_streams_two_ranks_on_one_gpu():
 
 
 def test_self_launch_two_ranks_prints_n_gpus_2():
-    """A plain `bench.py --gpus 2` (no torch.distributed.run around it) starts
+    """`bench.py --gpus 2 --full` (no torch.distributed.run around it) starts
     the two ranks itself; here they share the one GPU over
     gloo. Rank 0's line reports n_gpus 2, and the configs[4] entry (strong
     scaling over the two ranks) carries scaling_vs_n1 against the same 1024
@@ -218,7 +218,7 @@ def test_self_launch_two_ranks_prints_n_gpus_2():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
                         "--dist-backend", "gloo", "--windows", "65536", "--steps", "3",
-                        "--warmup", "1"], capture_output=True, timeout=600, cwd=ROOT, env=env)
+                        "--warmup", "1", "--full"], capture_output=True, timeout=600, cwd=ROOT, env=env)
     out = r.stdout.decode()
     assert r.returncode == 0, (out[-2000:], r.stderr.decode()[-4000:])
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
@@ -256,7 +256,7 @@ def test_self_launch_graph_failure_times_eager_bucket():
     env["BENCH_TEST_GRAPH_FAIL"] = "1"
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
                         "--dist-backend", "gloo", "--windows", "65536", "--steps", "3",
-                        "--warmup", "1", "--ring-gib", "2"], capture_output=True, timeout=600,
+                        "--warmup", "1", "--ring-gib", "2", "--full"], capture_output=True, timeout=600,
                        cwd=ROOT, env=env)
     out = r.stdout.decode()
     assert r.returncode == 0, (out[-2000:], r.stderr.decode()[-4000:])
@@ -286,7 +286,7 @@ def test_self_launch_watchdog_keeps_the_headline():
     env["BENCH_TEST_HANG_EXTRA"] = "1"
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2",
                         "--dist-backend", "gloo", "--windows", "65536", "--steps", "3",
-                        "--warmup", "1", "--extras-timeout", "5"],
+                        "--warmup", "1", "--extras-timeout", "5", "--full"],
                        capture_output=True, timeout=600, cwd=ROOT, env=env)
     out = r.stdout.decode()
     assert r.returncode != 0, (out[-2000:], r.stderr.decode()[-4000:])
