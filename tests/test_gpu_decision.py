@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from decision import check_decisions
+from guards import near_tie_windows
 
 pytestmark = pytest.mark.gpu
 
@@ -34,40 +35,6 @@ def torch():
     if not t.cuda.is_available():
         pytest.skip("no GPU visible")
     return t
-
-
-def near_tie_windows(freqs, W, seed, n=1024, amp=9000.0):
-    """W windows, each two random tones a, b of the plan with random phases;
-    b's amplitude is solved (bisection, double precision, before rounding to
-    int16) so that the two tones' DFT powers at their own frequencies are in
-    ratio P_b / P_a = 1 + eps exactly — including the leakage between them,
-    which matters for off-bin plans."""
-    rng = np.random.default_rng(seed)
-    K = len(freqs)
-    t = np.arange(n)
-    eps_set = np.array([0.0, 1e-7, 3e-7, 1e-6, 2e-6, 5e-6, 1e-5, 1e-4])
-    ab = np.array([rng.choice(K, 2, replace=False) for _ in range(W)])
-    eps = eps_set[np.arange(W) % eps_set.size]
-    ph = rng.uniform(0, 2 * np.pi, (W, 2))
-    w = 2 * np.pi * np.asarray(freqs, np.float64)[ab] / 48000.0          # (W, 2)
-    tones = np.cos(w[:, :, None] * t + ph[:, :, None])                  # (W, 2, n)
-    E = np.exp(-1j * w[:, :, None] * t)                                  # (W, 2, n)
-    c = np.einsum("wjn,wkn->wjk", tones, E)   # c[w, j, k]: tone j's DFT at tone k's frequency
-
-    def ratio(a2):
-        Xa = amp * c[:, 0, 0] + a2 * c[:, 1, 0]
-        Xb = amp * c[:, 0, 1] + a2 * c[:, 1, 1]
-        return np.abs(Xb) ** 2 / np.abs(Xa) ** 2
-
-    lo, hi = np.full(W, 0.5 * amp), np.full(W, 2.0 * amp)
-    for _ in range(60):
-        mid = 0.5 * (lo + hi)
-        up = ratio(mid) < 1.0 + eps
-        lo, hi = np.where(up, mid, lo), np.where(up, hi, mid)
-    a2 = 0.5 * (lo + hi)
-    v = amp * tones[:, 0] + a2[:, None] * tones[:, 1]
-    x = np.clip(np.round(v), -32768, 32767).astype(np.int16)
-    return x, ab
 
 
 @pytest.mark.parametrize("plan,method", [
