@@ -135,6 +135,31 @@ class DemodPlanInfo(ctypes.Structure):
 
 ENERGY_RAW, ENERGY_FOLDED, ENERGY_PARSEVAL = 0, 1, 2
 
+DEMOD_MAX_PHASES = 64
+DEMOD_MAX_SYNC = 64
+ACQUIRE_TILE = 1024   # DEMOD_ACQUIRE_TILE: windows per workgroup tile of the acquisition scan
+
+
+class DemodAcquireResult(ctypes.Structure):
+    """demod_acquire_result_t (include/demod.h): phase metric, phase, sync word
+    position and the symbol-rate stream's extent."""
+    _fields_ = [
+        ("metric", ctypes.c_double * DEMOD_MAX_PHASES),
+        ("phases", ctypes.c_uint32), ("phase", ctypes.c_uint32),
+        ("per_phase", ctypes.c_uint64),
+        ("sync_window", ctypes.c_int64),
+        ("sync_errors", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("first_window", ctypes.c_uint64), ("n_out", ctypes.c_uint64),
+        ("n_written", ctypes.c_uint64),
+    ]
+
+
+def acquire_result_dict(r: "DemodAcquireResult") -> dict:
+    """The fields of a DemodAcquireResult; `metric` as float64 [phases]."""
+    out = {f: int(getattr(r, f)) for f, _ in DemodAcquireResult._fields_ if f != "metric"}
+    out["metric"] = np.array(r.metric[:r.phases], np.float64)
+    return out
+
 
 class DemodError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
@@ -191,6 +216,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "demod_batch": (ctypes.c_int, [_P, _P, _SZ, _P, _P]),
         "demod_batch_async": (ctypes.c_int, [_P, _P, _SZ, _P, _P, _P]),
         "demod_batch_spectrum_async": (ctypes.c_int, [_P, _P, _SZ, _P, _P, _P, _P]),
+        "demod_acquire_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg)]),
+        "demod_acquire_async": (ctypes.c_int, [_P, _P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _P, _SZ,
+                                               _P, _P, _P]),
+        "demod_acquire": (ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _P, _SZ,
+                                         ctypes.POINTER(DemodAcquireResult)]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -330,6 +360,20 @@ def plan_info(cfg: DemodCfg) -> dict:
     out["rot"] = rot
     out["rot64"] = rot64
     return out
+
+
+def acquire_workspace_size(cfg: DemodCfg) -> int:
+    """demod_acquire_workspace_size: bytes of d_work an acquisition of cfg needs
+    (no GPU). Raises DemodError(DEMOD_BAD_ARG) where the configuration has no
+    acquisition (n % hop != 0, more than DEMOD_MAX_PHASES phases)."""
+    size = int(load_library().demod_acquire_workspace_size(ctypes.byref(cfg)))
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_acquire_workspace_size")
+    return size
+
+
+def _sync_bytes(sync) -> np.ndarray:
+    return np.zeros(0, np.uint8) if sync is None else np.ascontiguousarray(sync, dtype=np.uint8).reshape(-1)
 
 
 def _ptr(a) -> int:
@@ -522,6 +566,70 @@ class Demodulator:
         if rc < 0:
             raise DemodError(rc, "demod_batch_spectrum_async")
         return rc
+
+    def acquire(self, pcm, n_windows: Optional[int] = None, sync=None, max_errors: int = 0,
+                cap: Optional[int] = None):
+        """demod_acquire: the detector over the sliding windows of pcm (a host
+        int16 array or a device tensor), then symbol timing and the sync word.
+        Returns (symbols after the word at the symbol rate, result dict)."""
+        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
+        if host:
+            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+            size = flat.size
+        else:
+            size = int(pcm.numel())
+        if n_windows is None:
+            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
+        n_windows = int(n_windows)
+        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
+        if host:
+            if need > size:
+                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
+            buf = flat
+            if flat.ctypes.data % 16:
+                buf = np.empty(flat.size + 8, dtype=np.int16)
+                off = (-buf.ctypes.data % 16) // 2
+                buf = buf[off:off + flat.size]
+                buf[:] = flat
+        else:
+            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
+            buf = pcm
+        sync = _sync_bytes(sync)
+        if cap is None:
+            cap = n_windows // max(self.n // self.hop, 1) + 1
+        out = np.empty(max(int(cap), 1), dtype=np.uint8)
+        res = DemodAcquireResult()
+        rc = self._lib.demod_acquire(self._h, _ptr(buf), n_windows, _ptr(sync) if sync.size else None,
+                                     sync.size, int(max_errors), _ptr(out), int(cap),
+                                     ctypes.byref(res))
+        if rc < 0:
+            raise DemodError(rc, "demod_acquire")
+        return out[:rc], acquire_result_dict(res)
+
+    def acquire_async(self, d_sym, d_mag, n_windows: int, sync, max_errors: int, d_out, d_result,
+                      d_work, stream: int = 0) -> None:
+        """demod_acquire_async on a batch's device outputs: d_out (uint8, its
+        numel is cap; None: no output stream), d_result (uint8,
+        sizeof(DemodAcquireResult) bytes) and d_work (uint8,
+        acquire_workspace_size bytes) are device tensors, checked like the
+        batch calls' (dtype, contiguity, device, size)."""
+        n_windows = int(n_windows)
+        if n_windows < 0:
+            raise DemodError(DEMOD_BAD_ARG, "n_windows < 0")
+        dev = int(self.cfg.device)
+        _check_dev(d_sym, "d_sym", "uint8", max(n_windows, 1), dev)
+        _check_dev(d_mag, "d_mag", "float32", max(n_windows, 1) * self.k, dev)
+        _check_dev(d_out, "d_out", "uint8", 0, dev, nullable=True)
+        _check_dev(d_result, "d_result", "uint8", ctypes.sizeof(DemodAcquireResult), dev)
+        _check_dev(d_work, "d_work", "uint8", acquire_workspace_size(self.cfg), dev)
+        sync = _sync_bytes(sync)
+        cap = 0 if d_out is None else int(d_out.numel())
+        rc = self._lib.demod_acquire_async(self._h, _ptr(d_sym), _ptr(d_mag), n_windows,
+                                           _ptr(sync) if sync.size else None, sync.size,
+                                           int(max_errors), _ptr(d_out) if cap else None, cap,
+                                           _ptr(d_result), _ptr(d_work), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_acquire_async")
 
 
 class Streams:

@@ -72,6 +72,11 @@ struct demod {
     uint8_t *d_sym = nullptr;
     float *d_mag = nullptr;
     size_t d_out_cap = 0;       // windows
+    // demod_acquire: workspace, result and symbol-rate output (first use)
+    void *d_acq_work = nullptr;
+    demod_acquire_result_t *d_acq_res = nullptr;
+    uint8_t *d_acq_out = nullptr;
+    size_t d_acq_out_cap = 0;   // bytes
     int16_t *h_in = nullptr;            // pinned staging for small host calls
     size_t h_in_cap = 0;                // samples
     uint8_t *h_sym = nullptr;           // pinned
@@ -292,6 +297,9 @@ static void free_state(demod_t *st)
     if (st->d_in) (void)hipFree(st->d_in);
     if (st->d_sym) (void)hipFree(st->d_sym);
     if (st->d_mag) (void)hipFree(st->d_mag);
+    if (st->d_acq_work) (void)hipFree(st->d_acq_work);
+    if (st->d_acq_res) (void)hipFree(st->d_acq_res);
+    if (st->d_acq_out) (void)hipFree(st->d_acq_out);
     if (st->h_in) (void)hipHostFree(st->h_in);
     if (st->h_sym) (void)hipHostFree(st->h_sym);
     if (st->h_mag) (void)hipHostFree(st->h_mag);
@@ -817,6 +825,110 @@ int demod_batch_spectrum_async(demod_t *st, const int16_t *d_pcm, size_t n_windo
     DeviceGuard guard(st->device);
     HIP_TRY(guard.err);
     return enqueue_fft(st, d_pcm, n_windows, d_symbols, d_mags, d_spectrum, (hipStream_t)stream);
+}
+
+// ---- acquisition (acquire.hip) -------------------------------------------
+
+// R = n / hop when it divides and is at most DEMOD_MAX_PHASES, else 0 (n and
+// hop are powers of two for every valid configuration, so R is one)
+static uint32_t acquire_phases(const demod_cfg_t &c)
+{
+    if (c.hop == 0 || c.n % c.hop != 0) return 0;
+    const uint32_t r = c.n / c.hop;
+    return (r >= 1 && r <= DEMOD_MAX_PHASES && (r & (r - 1)) == 0) ? r : 0;
+}
+
+size_t demod_acquire_workspace_size(const demod_cfg_t *cfg)
+{
+    if (validate(cfg) != DEMOD_OK) return 0;
+    // [kAcqMaxBlocks][R] doubles, then as many 64-bit first-match words
+    return (size_t)2 * kAcqMaxBlocks * acquire_phases(*cfg) * sizeof(double);
+}
+
+// The handle's R when the shape and the sync word are acceptable, else 0.
+static uint32_t acquire_check(const demod_t *st, size_t n_windows, const uint8_t *sync,
+                              size_t sync_len, uint32_t max_errors)
+{
+    if (!st) return 0;
+    const uint32_t R = acquire_phases(st->cfg);
+    if (R == 0 || n_windows < R || n_windows > 0x7FFFFFFF) return 0;
+    if (sync_len > DEMOD_MAX_SYNC || (sync_len && (!sync || max_errors >= sync_len))) return 0;
+    for (size_t i = 0; i < sync_len; ++i)
+        if (sync[i] >= st->cfg.k) return 0;
+    return R;
+}
+
+int demod_acquire_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                        size_t n_windows, const uint8_t *sync, size_t sync_len,
+                        uint32_t max_errors, uint8_t *d_out, size_t cap,
+                        demod_acquire_result_t *d_result, void *d_work, void *stream)
+{
+    if (!d_symbols || !d_mags || !d_result || !d_work) return DEMOD_BAD_ARG;
+    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
+    if (R == 0) return DEMOD_BAD_ARG;
+    if ((cap && !d_out) || ((uintptr_t)d_result & 7) != 0 || ((uintptr_t)d_work & 7) != 0)
+        return DEMOD_BAD_ARG;
+    AcquireParams p;
+    std::memset(&p, 0, sizeof(p));
+    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
+    p.sym = d_symbols;
+    p.mag = d_mags;
+    p.n_windows = (long long)n_windows;
+    p.per_phase = (long long)(n_windows / R);
+    p.phases = (int)R;
+    p.k = (int)st->cfg.k;
+    p.sync_len = (int)sync_len;
+    p.max_errors = max_errors;
+    p.cap = cap;
+    p.out = d_out;
+    p.res = d_result;
+    p.part = static_cast<double *>(d_work);
+    p.first = reinterpret_cast<unsigned long long *>(p.part + (size_t)kAcqMaxBlocks * R);
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_acquire(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+int demod_acquire(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                  size_t sync_len, uint32_t max_errors, uint8_t *out, size_t cap,
+                  demod_acquire_result_t *result)
+{
+    if (!pcm || !result || (cap && !out) || ((uintptr_t)pcm & 15) != 0) return DEMOD_BAD_ARG;
+    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
+    if (R == 0) return DEMOD_BAD_ARG;   // before the detector runs
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
+    const bool din = is_device_ptr(pcm);
+    int rc;
+    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
+    if (!st->d_acq_work) {
+        HIP_TRY(hipMalloc(&st->d_acq_work, demod_acquire_workspace_size(&st->cfg)));
+        HIP_TRY(hipMalloc(&st->d_acq_res, sizeof(demod_acquire_result_t)));
+    }
+    const size_t dcap = std::min(cap, n_windows / R + 1);  // n_out <= ceil(W / R)
+    if (dcap > st->d_acq_out_cap) {
+        if (st->d_acq_out) (void)hipFree(st->d_acq_out);
+        st->d_acq_out = nullptr;
+        st->d_acq_out_cap = 0;
+        HIP_TRY(hipMalloc(&st->d_acq_out, dcap + dcap / 4 + 16));
+        st->d_acq_out_cap = dcap + dcap / 4 + 16;
+    }
+    if (!din)
+        HIP_TRY(hipMemcpyAsync(st->d_in, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
+                               st->stream));
+    rc = enqueue_batch(st, din ? pcm : st->d_in, n_windows, st->d_sym, st->d_mag, st->stream);
+    if (rc < 0) return rc;
+    rc = demod_acquire_async(st, st->d_sym, st->d_mag, n_windows, sync, sync_len, max_errors,
+                             dcap ? st->d_acq_out : nullptr, dcap, st->d_acq_res, st->d_acq_work,
+                             st->stream);
+    if (rc < 0) return rc;
+    HIP_TRY(hipMemcpyAsync(result, st->d_acq_res, sizeof(*result), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    if (result->n_written)
+        HIP_TRY(hipMemcpy(out, st->d_acq_out, result->n_written, hipMemcpyDeviceToHost));
+    return (int)result->n_written;
 }
 
 // The mono samples of n_frames frames (cfg.channels interleaved): the

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct demod_acquire_result;  // include/demod.h
+
 namespace fskd {
 
 constexpr int kSeg = 64;              // samples per lane segment
@@ -609,5 +611,28 @@ long long frame_streams_size(long long n, int bits, long long max_payload, unsig
                              unsigned *full, int *frames);
 hipError_t launch_frame_streams(const uint8_t *d_sym, long long n_streams, long long n, int bits,
                                 long long max_payload, uint8_t *d_out, hipStream_t s);
+
+// acquire.hip: symbol timing and sync word over a batch's outputs
+constexpr int kAcqTile = 1024;       // windows per workgroup tile (DEMOD_ACQUIRE_TILE)
+constexpr int kAcqMaxBlocks = 1024;  // the scan's grid: min(tiles, this)
+struct AcquireParams {
+    const uint8_t *sym;      // [n_windows]
+    const float *mag;        // [n_windows][k]
+    long long n_windows;
+    long long per_phase;     // J = n_windows / phases
+    int phases;              // R = n / hop, a power of two <= 64
+    int k;
+    int sync_len;
+    unsigned max_errors;
+    unsigned long long cap;
+    uint8_t *out;            // [cap] or nullptr (cap == 0)
+    ::demod_acquire_result *res;
+    double *part;            // d_work: [grid][phases] per-block phase sums
+    unsigned long long *first;  // d_work: [grid][phases] (w << 8 | errors), ~0: no match
+    int grid;                // set by launch_acquire
+    uint8_t sync[64];
+};
+int acquire_grid(long long n_windows);
+hipError_t launch_acquire(AcquireParams p, hipStream_t s);
 
 }  // namespace fskd

@@ -322,6 +322,87 @@ int demod_batch_spectrum_async(demod_t *st, const int16_t *d_pcm, size_t n_windo
                                uint8_t *d_symbols, float *d_mags, float *d_spectrum,
                                void *stream);
 
+/* ---- acquisition: symbol timing and sync word --------- */
+/*
+ * The detectors decide windows; with overlapping windows (hop < n) a batch
+ * looks at the stream at every phase. Acquisition turns a batch's outputs,
+ * sym[W] (uint8) and P[W][K] (fp32), window w at sample w hop, into the phase
+ * on which symbols start, the window at which a frame starts, and the
+ * symbol-rate stream after it. R = n / hop must divide exactly, 1 <= R <=
+ * DEMOD_MAX_PHASES (n and hop are powers of two, so R is); W >= R;
+ * J = floor(W / R).
+ *
+ *   phase metric  M[r] = sum_{j < J} (double) P[jR + r][sym[jR + r]], r < R:
+ *                 the decided tone's power, summed in double. A symbol byte
+ *                 >= K contributes nothing and its row of P is not read. The
+ *                 tail windows w >= J R are left out, so every phase sums the
+ *                 same count.
+ *   phase         argmax_r M[r], ties to the lowest r.
+ *   sync word     sync_len symbols (0 <= sync_len <= DEMOD_MAX_SYNC, each
+ *                 < K; a HOST pointer, copied into the launch arguments, so a
+ *                 captured graph bakes it in). For a start window w with
+ *                 w + (sync_len - 1) R < W, errors(w) = #{i : sym[w + iR] !=
+ *                 sync[i]} (a byte >= K mismatches). sync_window is the
+ *                 lowest w = phase (mod R) with errors(w) <= max_errors, -1 if
+ *                 there is none; sync_errors = errors(sync_window) (0 if
+ *                 none). max_errors < sync_len is required.
+ *   output        first_window = sync_window + sync_len R; phase when
+ *                 sync_len == 0; W when a sync word was asked for and not
+ *                 found. n_out = #{j >= 0 : first_window + jR < W}.
+ *                 out[j] = sym[first_window + jR] for j < n_written =
+ *                 min(n_out, cap); nothing is written past n_written.
+ *
+ * The sums' order depends on the shape (W, R) alone and no floating-point
+ * atomic is used: results are bit-identical from run to run.
+ */
+#define DEMOD_MAX_PHASES   64
+#define DEMOD_MAX_SYNC     64
+#define DEMOD_ACQUIRE_TILE 1024   /* windows per workgroup tile of the scan */
+typedef struct demod_acquire_result {
+    double   metric[DEMOD_MAX_PHASES];  /* M[r], r < phases; the rest 0 */
+    uint32_t phases, phase;
+    uint64_t per_phase;                 /* J */
+    int64_t  sync_window;               /* -1: none (or sync_len == 0) */
+    uint32_t sync_errors, reserved;
+    uint64_t first_window, n_out, n_written;
+} demod_acquire_result_t;
+
+/* Bytes of d_work an acquisition of this configuration needs (any W); 0 when
+ * the configuration is invalid, n % hop != 0 or R > DEMOD_MAX_PHASES. No
+ * device needed. */
+size_t demod_acquire_workspace_size(const demod_cfg_t *cfg);
+
+/*
+ * Acquisition over a batch's device outputs, enqueued on `stream` (three short
+ * launches; two when cap == 0). All d_* arguments are device pointers (d_work
+ * and d_result 8-byte aligned); d_out may be NULL with cap 0. Nothing is
+ * synchronised and nothing allocated, and the handle holds no state of it: the
+ * caller owns d_work (demod_acquire_workspace_size bytes, contents arbitrary:
+ * every word read is written first), so two acquisitions of one handle may run
+ * on different streams, as batches may, and demod_batch_async followed by this
+ * call can be captured into a HIP graph. Every byte of *d_result is written.
+ * Returns DEMOD_OK once enqueued; DEMOD_BAD_ARG, before any launch, for
+ * n % hop != 0, R > 64, W < R (or W >= 2^31), sync_len > 64, a sync symbol
+ * >= K, max_errors >= sync_len when sync_len > 0, a NULL sync with sync_len
+ * > 0, a NULL d_out with cap > 0, or a NULL d_symbols, d_mags, d_result or
+ * d_work.
+ */
+int demod_acquire_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                        size_t n_windows, const uint8_t *sync, size_t sync_len,
+                        uint32_t max_errors, uint8_t *d_out, size_t cap,
+                        demod_acquire_result_t *d_result, void *d_work, void *stream);
+
+/*
+ * The handle's detector over the n_windows sliding windows of pcm (a host or
+ * device pointer, detected as demod_batch does), then the acquisition of its
+ * outputs; out[0 .. n_written) and *result are copied to host memory.
+ * Synchronous; uses the handle's own device buffers and a handle-owned
+ * workspace allocated on first use. Returns n_written or a negative code.
+ */
+int demod_acquire(demod_t *st, const int16_t *pcm, size_t n_windows,
+                  const uint8_t *sync, size_t sync_len, uint32_t max_errors,
+                  uint8_t *out, size_t cap, demod_acquire_result_t *result);
+
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
  * n_streams independent streams that share one configuration, each behaving
