@@ -302,6 +302,32 @@ void build_plan(const demod_cfg_t &c, Plan &pl)
     }
 }
 
+void build_fft_tables(uint32_t n, FftTables &t)
+{
+    t.tw512.resize(1024);
+    t.tw1024.resize(1024);
+    for (int m = 0; m < 512; ++m) {
+        t.tw512[2 * m] = (float)std::cos(-2.0 * M_PI * m / 512.0);
+        t.tw512[2 * m + 1] = (float)std::sin(-2.0 * M_PI * m / 512.0);
+        t.tw1024[2 * m] = (float)std::cos(-2.0 * M_PI * m / 1024.0);
+        t.tw1024[2 * m + 1] = (float)std::sin(-2.0 * M_PI * m / 1024.0);
+    }
+    // the rescue's radix-2 twiddles: stage len (2 .. n), j < len / 2 at
+    // len / 2 - 1 + j, each the (cos, sin) of (-2 pi / len) j exactly as
+    // the double FFT of the definition evaluates it (one libm sincos of
+    // the same rounded argument)
+    t.rtw.resize(2 * (size_t)(n - 1));
+    for (uint32_t len = 2; len <= n; len <<= 1) {
+        const double ang = -(2.0 * M_PI) / (double)len;
+        for (uint32_t j = 0; j < len / 2; ++j) {
+            double sn, cs;
+            sincos(ang * (double)j, &sn, &cs);
+            t.rtw[2 * (len / 2 - 1 + j)] = cs;
+            t.rtw[2 * (len / 2 - 1 + j) + 1] = sn;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // The bound engine.
 namespace {

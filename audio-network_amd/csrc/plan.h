@@ -52,6 +52,14 @@ bool fold_eligible(const demod_cfg_t &c);     // ... on a multiple of 8 bins (fo
 // Fills pl from a validated configuration.
 void build_plan(const demod_cfg_t &c, Plan &pl);
 
+// The FFT detector's host tables (n = 1024), as uploaded.
+struct FftTables {
+    std::vector<float> tw512;   // [512][2]  e^{-2 pi i m / 512}
+    std::vector<float> tw1024;  // [512][2]  e^{-2 pi i m / 1024}
+    std::vector<double> rtw;    // the rescue's radix-2 twiddles (cos, sin)(-2 pi j / len), [n - 1]
+};
+void build_fft_tables(uint32_t n, FftTables &t);
+
 // The rescue's thresholds. With E the energy the kernel's
 // stage 2 sums (raw sum x^2; fold detector: sum xf^2 of the N/8-fold; FFT:
 // Parseval's 2 sum_b P_b >= n sum x^2) a window is flagged when
@@ -75,11 +83,12 @@ struct ErrModel {
 // runs pass 0 (n = 1024, K >= 2, not switched off).
 void error_model(const demod_cfg_t &c, const Plan &pl, bool first_pass, ErrModel &m);
 
-// demod_api.cpp helpers for demod_group.cpp: every argument refusal of
+// demod_streams.cpp helpers for demod_group.cpp: every argument refusal of
 // demod_streams_push (its code) or the per-stream symbol counts the push
-// emits (nullable counts; returns their total), and a streams handle's device
+// emits (nullable counts; returns their total; first / Wb: the push's own use),
+// and a streams handle's device
 long long streams_check(const demod_streams_t *ms, const int16_t *const *pcm, const size_t *n_frames,
-                        uint32_t *counts);
+                        uint32_t *counts, size_t *first = nullptr, size_t *Wb = nullptr);
 int streams_device(const demod_streams_t *ms);
 
 }  // namespace fskd

@@ -92,6 +92,21 @@ def test_group_agreement_protocol_over_threads():
     assert "group flow OK" in r.stdout
 
 
+def test_stream_staging_against_naive_model():
+    """demod_streams_push's host staging (csrc/stream_stage.h: batch layout,
+    carry + packet into a stream's run, gap fill, new carry, rollback) against
+    a naive concatenate-and-slice model (tests/native/stream_stage_test.cpp,
+    ASan + UBSan, exact-size packet, run and carry buffers): hops that do and
+    do not divide n, mono and the three stereo modes, lead-ins up to longer
+    than the first packet, packets from 0 to 3n + 7 frames, 1 / 3 / 9
+    streams, several pushes each and a rollback in between."""
+    _make("stream_stage_test")
+    r = subprocess.run([os.path.join(NATIVE, "stream_stage_test")], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "stream stage OK" in r.stdout
+
+
 def test_rescue_bounds_checking_build_compiles(tmp_path):
     """the bounds-checking build of the rescue launch
     (FSKD_BOUNDS_DEBUG: RS_CHECK reports and clamps an out-of-range index,
