@@ -138,6 +138,7 @@ ENERGY_RAW, ENERGY_FOLDED, ENERGY_PARSEVAL = 0, 1, 2
 DEMOD_MAX_PHASES = 64
 DEMOD_MAX_SYNC = 64
 ACQUIRE_TILE = 1024   # DEMOD_ACQUIRE_TILE: windows per workgroup tile of the acquisition scan
+DEMOD_MAX_SEGMENTS = 65536
 
 
 class DemodAcquireResult(ctypes.Structure):
@@ -221,6 +222,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                _P, _P, _P]),
         "demod_acquire": (ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _P, _SZ,
                                          ctypes.POINTER(DemodAcquireResult)]),
+        "demod_acquire_segments_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), _SZ, _SZ]),
+        "demod_acquire_segments_async": (ctypes.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _P, _SZ,
+                                                        ctypes.c_uint32, _P, _SZ, _P, _P, _SZ, _P]),
+        "demod_acquire_segments": (ctypes.c_int, [_P, _P, _SZ, _P, _P, _SZ, _P, _SZ, ctypes.c_uint32,
+                                                  _P, _SZ, _P]),
+        "demod_segments_layout": (ctypes.c_int, [ctypes.POINTER(DemodCfg), _SZ, _P, _P, _P,
+                                                 ctypes.POINTER(_SZ)]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -370,6 +378,37 @@ def acquire_workspace_size(cfg: DemodCfg) -> int:
     if size == 0:
         raise DemodError(DEMOD_BAD_ARG, "demod_acquire_workspace_size")
     return size
+
+
+def acquire_segments_workspace_size(cfg: DemodCfg, max_segments: int, max_windows: int) -> int:
+    """demod_acquire_segments_workspace_size: bytes of d_work a segmented
+    acquisition of up to max_segments segments over a batch of up to max_windows
+    windows needs (no GPU); monotone in both. Raises DemodError(DEMOD_BAD_ARG)
+    where it is 0 (no acquisition for cfg, max_segments not in 1 ..
+    DEMOD_MAX_SEGMENTS, max_windows >= 2^31)."""
+    if max_segments < 0 or max_windows < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_acquire_segments_workspace_size")
+    size = int(load_library().demod_acquire_segments_workspace_size(ctypes.byref(cfg), int(max_segments),
+                                                                   int(max_windows)))
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_acquire_segments_workspace_size")
+    return size
+
+
+def segments_layout(cfg: DemodCfg, n_samples):
+    """demod_segments_layout: the batch layout demod_streams_push builds, from
+    the runs' lengths in mono samples. Returns (first uint64 [S], count uint32
+    [S], n_windows): run s is batch windows first[s] .. first[s] + count[s] - 1
+    and starts at sample first[s] * hop of the batch (no GPU)."""
+    lens = np.ascontiguousarray(n_samples, dtype=np.uint64).reshape(-1)
+    first = np.zeros(lens.size, np.uint64)
+    count = np.zeros(lens.size, np.uint32)
+    W = _SZ(0)
+    rc = load_library().demod_segments_layout(ctypes.byref(cfg), lens.size, _ptr(lens) if lens.size else None,
+                                              _ptr(first), _ptr(count), ctypes.byref(W))
+    if rc != DEMOD_OK:
+        raise DemodError(rc, "demod_segments_layout")
+    return first, count, int(W.value)
 
 
 def _sync_bytes(sync) -> np.ndarray:
@@ -630,6 +669,88 @@ class Demodulator:
                                            _ptr(d_result), _ptr(d_work), stream or None)
         if rc < 0:
             raise DemodError(rc, "demod_acquire_async")
+
+    def acquire_segments(self, pcm, first, count, sync=None, max_errors: int = 0,
+                         cap: Optional[int] = None, n_windows: Optional[int] = None):
+        """demod_acquire_segments: the detector over the sliding windows of pcm
+        (a host int16 array or a device tensor), then the acquisition of each
+        segment first[s] .. first[s] + count[s] - 1 as a batch of its own.
+        Returns (out uint8 [S][cap], row s valid up to its n_written and 0xFF
+        after it; [result dict per segment])."""
+        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
+        if host:
+            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+            size = flat.size
+        else:
+            size = int(pcm.numel())
+        if n_windows is None:
+            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
+        n_windows = int(n_windows)
+        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
+        if host:
+            if need > size:
+                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
+            buf = flat
+            if flat.ctypes.data % 16:
+                buf = np.empty(flat.size + 8, dtype=np.int16)
+                off = (-buf.ctypes.data % 16) // 2
+                buf = buf[off:off + flat.size]
+                buf[:] = flat
+        else:
+            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
+            buf = pcm
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+        if first.size != count.size or first.size == 0:
+            raise DemodError(DEMOD_BAD_ARG, "first and count: one entry per segment, at least one")
+        S = first.size
+        sync = _sync_bytes(sync)
+        if cap is None:
+            cap = int(count.max()) // max(self.n // self.hop, 1) + 1
+        cap = int(cap)
+        out = np.full((S, max(cap, 1)), 0xFF, dtype=np.uint8)[:, :cap]
+        results = (DemodAcquireResult * S)()
+        rc = self._lib.demod_acquire_segments(self._h, _ptr(buf), n_windows, _ptr(first), _ptr(count), S,
+                                              _ptr(sync) if sync.size else None, sync.size,
+                                              int(max_errors), out.ctypes.data if cap else None, cap,
+                                              ctypes.cast(results, _P))
+        if rc < 0:
+            raise DemodError(rc, "demod_acquire_segments")
+        return out, [acquire_result_dict(r) for r in results]
+
+    def acquire_segments_async(self, d_sym, d_mag, n_windows: int, d_first, d_count, n_segments: int,
+                               sync, max_errors: int, d_out, d_results, d_work,
+                               stream: int = 0) -> None:
+        """demod_acquire_segments_async on a batch's device outputs. d_first
+        (int64 tensor holding the uint64 table) and d_count (int32 tensor
+        holding the uint32 table) have n_segments entries; d_out (uint8,
+        n_segments * cap bytes: cap is its numel // n_segments; None: no rows),
+        d_results (uint8, n_segments * sizeof(DemodAcquireResult) bytes) and
+        d_work (uint8, at least acquire_segments_workspace_size(cfg,
+        n_segments, n_windows) bytes; all of it is handed over, a larger one
+        raises the tile budget) are device tensors, checked like the batch
+        calls' (dtype, contiguity, device, size)."""
+        n_windows, S = int(n_windows), int(n_segments)
+        if n_windows < 0 or S < 1 or S > DEMOD_MAX_SEGMENTS:
+            raise DemodError(DEMOD_BAD_ARG, "n_windows < 0 or n_segments not in 1 .. DEMOD_MAX_SEGMENTS")
+        dev = int(self.cfg.device)
+        _check_dev(d_sym, "d_sym", "uint8", max(n_windows, 1), dev)
+        _check_dev(d_mag, "d_mag", "float32", max(n_windows, 1) * self.k, dev)
+        _check_dev(d_first, "d_first", "int64", S, dev)
+        _check_dev(d_count, "d_count", "int32", S, dev)
+        _check_dev(d_out, "d_out", "uint8", 0, dev, nullable=True)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodAcquireResult), dev)
+        _check_dev(d_work, "d_work", "uint8",
+                   acquire_segments_workspace_size(self.cfg, S, n_windows), dev)
+        sync = _sync_bytes(sync)
+        cap = 0 if d_out is None else int(d_out.numel()) // S
+        rc = self._lib.demod_acquire_segments_async(
+            self._h, _ptr(d_sym), _ptr(d_mag), n_windows, _ptr(d_first), _ptr(d_count), S,
+            _ptr(sync) if sync.size else None, sync.size, int(max_errors),
+            _ptr(d_out) if cap else None, cap, _ptr(d_results), _ptr(d_work), int(d_work.numel()),
+            stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_acquire_segments_async")
 
 
 class Streams:

@@ -1,0 +1,337 @@
+// acquire_segments.hip — the acquisition of acquire.hip over S segments of one
+// batch in one call (include/demod.h "segmented acquisition", DESIGN.md §4.9
+// "Segments"). Segment s is batch windows first[s] .. first[s] + count[s] - 1
+// and is treated exactly as a batch of its own: its own phase metric, phase,
+// sync word position and symbol-rate row. The tables are device memory, so the
+// kernels clamp them (first' = min(first, Wb), count' = min(count, Wb - first'))
+// and every index below is bounded by the clamped values alone.
+//
+// The unit of work is a segment-relative tile of kAcqTile windows, taken by ONE
+// WAVE: the workload is many short segments (a 60 ms packet is ~11 windows at
+// hop 256), and a wave per tile puts four segments in a workgroup where a
+// workgroup per tile would idle 245 threads; a 4 M-window segment is 4096
+// tiles, i.e. 4096 waves. 64 is a multiple of R (a power of two <= 64), so
+// lane l's windows l + 64 i of a tile are all on phase l mod R, relative to the
+// segment's start.
+//
+//  plan      one workgroup: clamps the tables, counts each segment's tiles (0
+//            for fewer than R windows) and writes to d_work the clamped table,
+//            the exclusive prefix of tiles and the call's total. A segment is
+//            kept while the tiles of segments 0 .. s together fit the
+//            workspace's tile budget; the others are reported as short ones.
+//  scan      waves walk the call's tiles (wave-stride), find (segment, tile)
+//            by binary search in the prefix, add the decided tone's power per
+//            lane in window order, then across the lanes of a phase by a
+//            butterfly (xor 32, 16, .. R: a fixed tree). The sync word is
+//            compared from LDS (the tile's symbols and the (sync_len - 1) R
+//            after it, 0xFF past the segment's end); a lane's windows ascend,
+//            so its first match is its lowest, and the butterfly takes the
+//            minimum. One partial and one first-match word per phase per tile
+//            go to d_work by plain stores.
+//  finalise  one wave per segment: its tiles' partials [tiles][R] read as one
+//            array, lane l adding entries l, l + 64, .., then the butterfly;
+//            segments of more than kSegWaveTiles tiles are added by the whole
+//            workgroup instead (thread t entries t, t + 256, .., then thread r
+//            its phase's threads in order, as acquire_final_kernel; the
+//            first-match words of its phase likewise, an integer atomicMin in
+//            LDS). Argmax with ties to the lowest phase, the phase's lowest
+//            first-match word, every byte of result[s].
+//  gather    out[s cap + j] = sym[first' + first_window + j R], j < n_written.
+//
+// Every sum's order depends on the segment's (count, R) alone: not on first[s],
+// the slot s, S or the grid. No floating-point atomics. Every word of d_work a
+// launch reads was stored by an earlier launch of the same call.
+#include "../../include/demod.h"
+#include "demod_internal.h"
+
+namespace fskd {
+
+constexpr int kSegThreads = 256;
+constexpr int kSegLanes = 64;
+constexpr int kSegWaves = kSegThreads / kSegLanes;
+constexpr int kSegPerLane = kAcqTile / kSegLanes;
+constexpr int kSegHalo = (DEMOD_MAX_SYNC - 1) * DEMOD_MAX_PHASES;
+constexpr int kSegMaxBlocks = 2048;      // the scan's grid: min(ceil(budget / 4), this)
+constexpr unsigned kSegWaveTiles = 64;   // finalise: up to this many tiles by one wave
+constexpr int kSegPlanThreads = 1024;
+constexpr unsigned long long kSegNone = ~0ull;
+
+static_assert(kSegLanes % DEMOD_MAX_PHASES == 0 && kAcqTile % kSegLanes == 0,
+              "a lane's windows must stay on one phase");
+static_assert(kSegThreads % DEMOD_MAX_PHASES == 0, "finalise: a thread's entries stay on one phase");
+
+__global__ __launch_bounds__(kSegPlanThreads) void acquire_seg_plan_kernel(AcquireSegParams p)
+{
+    __shared__ unsigned long long s_wave[kSegPlanThreads / kSegLanes];
+    __shared__ unsigned s_total;
+    const int t = threadIdx.x, wave = t / kSegLanes, lane = t % kSegLanes;
+    const unsigned long long Wb = (unsigned long long)p.n_windows;
+    if (t == 0) s_total = 0;
+    unsigned long long carry = 0;   // tiles of the segments before this round (same in every thread)
+    for (unsigned base = 0; base < p.n_segments; base += kSegPlanThreads) {
+        const unsigned s = base + t;
+        const bool in = s < p.n_segments;
+        unsigned long long f = 0, c = 0, tiles = 0;
+        if (in) {
+            f = p.seg_first[s];
+            f = f < Wb ? f : Wb;
+            c = p.seg_count[s];
+            c = c < Wb - f ? c : Wb - f;
+            tiles = c >= (unsigned long long)p.phases ? (c + kAcqTile - 1) / kAcqTile : 0;
+        }
+        unsigned long long x = tiles;   // inclusive scan within the wave
+        for (int d = 1; d < kSegLanes; d <<= 1) {
+            const unsigned long long y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == kSegLanes - 1) s_wave[wave] = x;
+        __syncthreads();
+        unsigned long long before = 0, all = 0;
+        for (int w = 0; w < kSegPlanThreads / kSegLanes; ++w) {
+            const unsigned long long v = s_wave[w];
+            before += w < wave ? v : 0;
+            all += v;
+        }
+        if (in) {
+            const unsigned long long incl = carry + before + x, excl = incl - tiles;
+            const bool kept = tiles > 0 && incl <= p.budget;
+            p.w_first[s] = f;
+            p.w_count[s] = (unsigned)c;
+            p.w_tile0[s] = excl < 0xFFFFFFFFull ? (unsigned)excl : 0xFFFFFFFFu;
+            p.w_tiles[s] = kept ? (unsigned)tiles : 0u;
+            if (kept) atomicMax(&s_total, (unsigned)incl);   // integer, LDS
+        }
+        carry += all;
+        __syncthreads();  // s_wave is rewritten by the next round
+    }
+    __syncthreads();
+    if (t == 0) *p.w_total = s_total;
+}
+
+__global__ __launch_bounds__(kSegThreads) void acquire_seg_scan_kernel(AcquireSegParams p)
+{
+    __shared__ uint8_t s_sym[kSegWaves][kAcqTile + kSegHalo];
+    __shared__ uint8_t s_sync[DEMOD_MAX_SYNC];
+    const int t = threadIdx.x, wave = t / kSegLanes, lane = t % kSegLanes;
+    const int R = p.phases, L = p.sync_len;
+    const int halo = L > 0 ? (L - 1) * R : 0;
+    if (t < DEMOD_MAX_SYNC) s_sync[t] = p.sync[t];
+    const unsigned total = *p.w_total;
+    for (unsigned g0 = blockIdx.x * kSegWaves; g0 < total; g0 += gridDim.x * kSegWaves) {
+        const unsigned g = g0 + wave;
+        const bool live = g < total;
+        // the last segment whose first tile is <= g: zero-tile segments share a
+        // successor's first tile and lie before it, dropped ones start at total
+        unsigned s = 0;
+        if (live) {
+            unsigned lo = 0, hi = p.n_segments;
+            while (hi - lo > 1) {
+                const unsigned mid = lo + (hi - lo) / 2;
+                if (p.w_tile0[mid] <= g) lo = mid; else hi = mid;
+            }
+            s = lo;
+        }
+        const long long cnt = live ? (long long)p.w_count[s] : 0;
+        const unsigned long long f = live ? p.w_first[s] : 0;
+        const long long base = live ? (long long)(g - p.w_tile0[s]) * kAcqTile : 0;
+        const long long Wm = cnt / R * R;
+        if (L > 0) __syncthreads();  // the previous tile's compares have read s_sym
+        uint8_t sv[kSegPerLane];
+#pragma unroll
+        for (int i = 0; i < kSegPerLane; ++i) {
+            const long long w = base + lane + kSegLanes * i;
+            sv[i] = w < cnt ? p.sym[f + w] : (uint8_t)0xFF;
+            if (L > 0) s_sym[wave][lane + kSegLanes * i] = sv[i];
+        }
+        for (int h = lane; h < halo; h += kSegLanes) {
+            const long long w = base + kAcqTile + h;
+            s_sym[wave][kAcqTile + h] = w < cnt ? p.sym[f + w] : (uint8_t)0xFF;
+        }
+        // the decided tone's power; a byte >= K reads nothing and adds nothing
+        float pw[kSegPerLane];
+#pragma unroll
+        for (int i = 0; i < kSegPerLane; ++i) {
+            const long long w = base + lane + kSegLanes * i;
+            pw[i] = (w < Wm && sv[i] < p.k) ? p.mag[(f + w) * p.k + sv[i]] : 0.f;
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < kSegPerLane; ++i) acc += (double)pw[i];
+        unsigned long long best = kSegNone;
+        if (L > 0) {
+            __syncthreads();
+#pragma unroll 1
+            for (int i = 0; i < kSegPerLane; ++i) {
+                const int local = lane + kSegLanes * i;
+                const long long w = base + local;
+                if (w + halo >= cnt) break;  // the word would run past the segment
+                unsigned err = 0;
+                for (int j = 0; j < L; ++j) {
+                    err += s_sym[wave][local + j * R] != s_sync[j];
+                    if (err > p.max_errors) break;
+                }
+                if (err <= p.max_errors) {   // the lane's windows ascend: its first match is its lowest
+                    best = ((unsigned long long)w << 8) | err;
+                    break;
+                }
+            }
+        }
+        // the lanes of a phase: a fixed tree, the same value in every lane of it
+        for (int off = kSegLanes / 2; off >= R; off >>= 1) {
+            acc += __shfl_xor(acc, off);
+            const unsigned long long o = __shfl_xor(best, off);
+            best = o < best ? o : best;
+        }
+        if (live && lane < R) {
+            p.part[(size_t)g * R + lane] = acc;
+            p.first[(size_t)g * R + lane] = best;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kSegThreads) void acquire_seg_final_kernel(AcquireSegParams p)
+{
+    __shared__ double s_acc[kSegThreads];
+    __shared__ double s_big[kSegWaves][DEMOD_MAX_PHASES];
+    __shared__ unsigned s_nt[kSegWaves], s_t0[kSegWaves];
+    __shared__ unsigned long long s_best[kSegWaves];
+    __shared__ int s_phase[kSegWaves];
+    const int t = threadIdx.x, wave = t / kSegLanes, lane = t % kSegLanes, R = p.phases;
+    const unsigned s = blockIdx.x * kSegWaves + wave;
+    const bool valid = s < p.n_segments;
+    const unsigned nt = valid ? p.w_tiles[s] : 0u;
+    const unsigned t0 = valid ? p.w_tile0[s] : 0u;
+    const unsigned long long cnt = valid ? p.w_count[s] : 0u;
+    if (lane == 0) {
+        s_nt[wave] = nt;
+        s_t0[wave] = t0;
+        s_best[wave] = kSegNone;
+    }
+    __syncthreads();
+    double m = 0.0;   // lane l: the metric of phase l mod R
+    if (nt <= kSegWaveTiles) {
+        const double *q = p.part + (size_t)t0 * R;
+        const unsigned total = nt * (unsigned)R;
+#pragma unroll 4
+        for (unsigned i = lane; i < total; i += kSegLanes) m += q[i];
+        for (int off = kSegLanes / 2; off >= R; off >>= 1) m += __shfl_xor(m, off);
+    }
+    // long segments: the whole workgroup, one after the other (uniform branches)
+    for (int w = 0; w < kSegWaves; ++w) {
+        const unsigned ntw = s_nt[w];
+        if (ntw <= kSegWaveTiles) continue;
+        const double *q = p.part + (size_t)s_t0[w] * R;
+        const unsigned long long total = (unsigned long long)ntw * R;
+        double a = 0.0;
+#pragma unroll 8
+        for (unsigned long long i = t; i < total; i += kSegThreads) a += q[i];
+        s_acc[t] = a;
+        __syncthreads();
+        if (t < R) {
+            double v = 0.0;
+#pragma unroll 8
+            for (int g = t; g < kSegThreads; g += R) v += s_acc[g];
+            s_big[w][t] = v;
+        }
+        __syncthreads();
+        // its phase and that phase's lowest first-match word, by the workgroup too:
+        // one wave would wait for tiles / 64 loads one after the other
+        if (t == 0) {
+            int best = 0;
+            for (int r = 1; r < R; ++r)
+                if (s_big[w][r] > s_big[w][best]) best = r;
+            s_phase[w] = best;
+        }
+        __syncthreads();
+        if (p.sync_len > 0) {
+            const unsigned long long *f = p.first + (size_t)s_t0[w] * R + s_phase[w];
+            unsigned long long v = kSegNone;
+#pragma unroll 4
+            for (unsigned b = t; b < ntw; b += kSegThreads) {
+                const unsigned long long o = f[(size_t)b * R];
+                v = o < v ? o : v;
+            }
+            if (v != kSegNone) atomicMin(&s_best[w], v);   // integer, LDS
+        }
+        __syncthreads();
+    }
+    if (nt > kSegWaveTiles) m = s_big[wave][lane & (R - 1)];
+    // argmax over the phases, ties to the lowest
+    double bm = m;
+    int br = lane & (R - 1);
+    for (int off = R >> 1; off >= 1; off >>= 1) {
+        const double om = __shfl_xor(bm, off);
+        const int orr = __shfl_xor(br, off);
+        if (om > bm || (om == bm && orr < br)) {
+            bm = om;
+            br = orr;
+        }
+    }
+    const int phase = nt > kSegWaveTiles ? s_phase[wave] : __shfl(br, 0);
+    unsigned long long best = nt > kSegWaveTiles ? s_best[wave] : kSegNone;
+    if (p.sync_len > 0 && nt <= kSegWaveTiles) {
+        for (unsigned b = lane; b < nt; b += kSegLanes) {
+            const unsigned long long v = p.first[((size_t)t0 + b) * R + phase];
+            best = v < best ? v : best;
+        }
+        for (int off = kSegLanes / 2; off >= 1; off >>= 1) {
+            const unsigned long long o = __shfl_xor(best, off);
+            best = o < best ? o : best;
+        }
+    }
+    if (!valid) return;
+    demod_acquire_result_t *res = p.res + s;
+    res->metric[lane] = (lane < R && nt > 0) ? m : 0.0;
+    if (lane == 0) {
+        const bool is_short = nt == 0;   // fewer than R windows, or past the tile budget
+        const bool found = !is_short && p.sync_len > 0 && best != kSegNone;
+        unsigned long long fw = (unsigned long long)phase;
+        if (p.sync_len > 0) fw = found ? (best >> 8) + (unsigned long long)p.sync_len * R : cnt;
+        if (is_short) fw = cnt;
+        const unsigned long long n_out = fw < cnt ? (cnt - fw + R - 1) / R : 0;
+        res->phases = (uint32_t)R;
+        res->phase = is_short ? 0u : (uint32_t)phase;
+        res->per_phase = is_short ? 0u : (uint64_t)(cnt / R);
+        res->sync_window = found ? (int64_t)(best >> 8) : -1;
+        res->sync_errors = found ? (uint32_t)(best & 0xFF) : 0u;
+        res->reserved = 0;
+        res->first_window = fw;
+        res->n_out = n_out;
+        res->n_written = n_out < p.cap ? n_out : p.cap;
+    }
+}
+
+// wps waves per segment: wave c of segment s writes j = 64 c + lane, + 64 wps, ..
+__global__ __launch_bounds__(kSegThreads) void acquire_seg_gather_kernel(AcquireSegParams p, unsigned wps)
+{
+    const int wave = threadIdx.x / kSegLanes, lane = threadIdx.x % kSegLanes;
+    const unsigned long long gw = (unsigned long long)blockIdx.x * kSegWaves + wave;
+    const unsigned long long s = gw / wps, c = gw % wps;
+    if (s >= p.n_segments) return;
+    const unsigned long long n = p.res[s].n_written, fw = p.w_first[s] + p.res[s].first_window;
+    uint8_t *row = p.out + s * p.cap;
+    for (unsigned long long j = c * kSegLanes + lane; j < n; j += (unsigned long long)wps * kSegLanes)
+        row[j] = p.sym[fw + j * p.phases];
+}
+
+hipError_t launch_acquire_segments(const AcquireSegParams &p, hipStream_t s)
+{
+    const unsigned S = p.n_segments;
+    hipLaunchKernelGGL(acquire_seg_plan_kernel, dim3(1), dim3(kSegPlanThreads), 0, s, p);
+    const unsigned long long blocks = ((unsigned long long)p.budget + kSegWaves - 1) / kSegWaves;
+    const unsigned grid = (unsigned)(blocks < kSegMaxBlocks ? (blocks ? blocks : 1) : kSegMaxBlocks);
+    hipLaunchKernelGGL(acquire_seg_scan_kernel, dim3(grid), dim3(kSegThreads), 0, s, p);
+    hipLaunchKernelGGL(acquire_seg_final_kernel, dim3((S + kSegWaves - 1) / kSegWaves),
+                       dim3(kSegThreads), 0, s, p);
+    if (p.cap > 0) {
+        const unsigned long long want = (p.cap + kSegLanes - 1) / kSegLanes;
+        const unsigned long long most = 16384 / S ? 16384 / S : 1;
+        const unsigned wps = (unsigned)(want < most ? want : most);
+        const unsigned long long gblocks = ((unsigned long long)S * wps + kSegWaves - 1) / kSegWaves;
+        hipLaunchKernelGGL(acquire_seg_gather_kernel, dim3((unsigned)gblocks), dim3(kSegThreads), 0, s,
+                           p, wps);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace fskd

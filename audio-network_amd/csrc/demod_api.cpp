@@ -649,12 +649,14 @@ size_t demod_acquire_workspace_size(const demod_cfg_t *cfg)
 }
 
 // The handle's R when the shape and the sync word are acceptable, else 0.
+// whole: the batch is acquired as one stream and needs R windows (a segment
+// with fewer is an outcome of the segmented call, not a refusal).
 static uint32_t acquire_check(const demod_t *st, size_t n_windows, const uint8_t *sync,
-                              size_t sync_len, uint32_t max_errors)
+                              size_t sync_len, uint32_t max_errors, bool whole = true)
 {
     if (!st) return 0;
     const uint32_t R = acquire_phases(st->cfg);
-    if (R == 0 || n_windows < R || n_windows > 0x7FFFFFFF) return 0;
+    if (R == 0 || (whole && n_windows < R) || n_windows > 0x7FFFFFFF) return 0;
     if (sync_len > DEMOD_MAX_SYNC || (sync_len && (!sync || max_errors >= sync_len))) return 0;
     for (size_t i = 0; i < sync_len; ++i)
         if (sync[i] >= st->cfg.k) return 0;
@@ -724,6 +726,157 @@ int demod_acquire(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8
     if (result->n_written)
         HIP_TRY(hipMemcpy(out, st->d_acq_out.p, result->n_written, hipMemcpyDeviceToHost));
     return (int)result->n_written;
+}
+
+// ---- segmented acquisition (acquire_segments.hip) --------------------------
+
+size_t demod_acquire_segments_workspace_size(const demod_cfg_t *cfg, size_t max_segments,
+                                             size_t max_windows)
+{
+    if (validate_cfg(cfg) != DEMOD_OK) return 0;
+    const uint32_t R = acquire_phases(*cfg);
+    if (R == 0 || max_segments == 0 || max_segments > DEMOD_MAX_SEGMENTS || max_windows > 0x7FFFFFFF)
+        return 0;
+    const size_t tiles = (max_windows + kAcqTile - 1) / kAcqTile + max_segments;
+    return acquire_seg_header_bytes(max_segments) + tiles * acquire_seg_tile_bytes(R);
+}
+
+int demod_acquire_segments_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                                 size_t n_windows, const uint64_t *d_first,
+                                 const uint32_t *d_count, size_t n_segments, const uint8_t *sync,
+                                 size_t sync_len, uint32_t max_errors, uint8_t *d_out, size_t cap,
+                                 demod_acquire_result_t *d_results, void *d_work,
+                                 size_t work_bytes, void *stream)
+{
+    if (!d_symbols || !d_mags || !d_results || !d_work || !d_first || !d_count) return DEMOD_BAD_ARG;
+    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors, false);
+    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
+    if ((cap && !d_out) || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_work & 7) != 0 ||
+        ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_count & 3) != 0)
+        return DEMOD_BAD_ARG;
+    const size_t need = demod_acquire_segments_workspace_size(&st->cfg, n_segments, n_windows);
+    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
+    const size_t head = acquire_seg_header_bytes(n_segments);
+    const size_t budget = (work_bytes - head) / acquire_seg_tile_bytes(R);
+    AcquireSegParams p;
+    std::memset(&p, 0, sizeof(p));
+    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
+    p.sym = d_symbols;
+    p.mag = d_mags;
+    p.seg_first = reinterpret_cast<const unsigned long long *>(d_first);
+    p.seg_count = d_count;
+    p.n_windows = (long long)n_windows;
+    p.n_segments = (unsigned)n_segments;
+    p.budget = (unsigned)std::min<size_t>(budget, 0xFFFFFFFFu);
+    p.phases = (int)R;
+    p.k = (int)st->cfg.k;
+    p.sync_len = (int)sync_len;
+    p.max_errors = max_errors;
+    p.cap = cap;
+    p.out = d_out;
+    p.res = d_results;
+    // the header: first'[S] (8 bytes each), then count', first tile and tiles
+    // [S] and the call's total (4 bytes each); then the tiles' words
+    unsigned char *w = static_cast<unsigned char *>(d_work);
+    p.w_first = reinterpret_cast<unsigned long long *>(w);
+    p.w_count = reinterpret_cast<unsigned *>(w + 8 * n_segments);
+    p.w_tile0 = p.w_count + n_segments;
+    p.w_tiles = p.w_tile0 + n_segments;
+    p.w_total = p.w_tiles + n_segments;
+    p.part = reinterpret_cast<double *>(w + head);
+    p.first = reinterpret_cast<unsigned long long *>(p.part + (size_t)p.budget * R);
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_acquire_segments(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+int demod_acquire_segments(demod_t *st, const int16_t *pcm, size_t n_windows,
+                           const uint64_t *first, const uint32_t *count, size_t n_segments,
+                           const uint8_t *sync, size_t sync_len, uint32_t max_errors,
+                           uint8_t *out, size_t cap, demod_acquire_result_t *results)
+{
+    if (!pcm || !results || !first || !count || (cap && !out) || ((uintptr_t)pcm & 15) != 0)
+        return DEMOD_BAD_ARG;
+    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
+    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
+    // the tables are host memory here: refuse what the kernels would clamp
+    size_t longest = 0;
+    unsigned long long tiles = 0, rows = 0;
+    for (size_t s = 0; s < n_segments; ++s) {
+        if (count[s] < R || first[s] > n_windows || count[s] > n_windows - first[s])
+            return DEMOD_BAD_ARG;
+        longest = std::max<size_t>(longest, count[s]);
+        tiles += (count[s] + (size_t)kAcqTile - 1) / kAcqTile;
+        rows += std::min<unsigned long long>(cap, count[s] / R + 1);
+    }
+    if (rows > 0x7FFFFFFF) return DEMOD_BAD_ARG;   // the return value is their sum at most
+    // a workspace for every tile: ceil(cover / T) + S of them. Disjoint segments
+    // fit cover = n_windows; overlapping ones may hold more tiles than the batch
+    const unsigned long long cover = std::max<unsigned long long>(
+        n_windows, tiles > n_segments ? (tiles - n_segments) * kAcqTile : 0);
+    if (cover > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const size_t work = demod_acquire_segments_workspace_size(&st->cfg, n_segments, (size_t)cover);
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
+    const bool din = is_device_ptr(pcm);
+    int rc;
+    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
+    HIP_TRY(st->d_seg_work.reserve(work));  // bytes
+    HIP_TRY(st->d_seg_first.reserve(n_segments));
+    HIP_TRY(st->d_seg_count.reserve(n_segments));
+    HIP_TRY(st->d_seg_res.reserve(n_segments));
+    const size_t dcap = std::min(cap, longest / R + 1);  // n_out <= ceil(count / R)
+    HIP_TRY(st->d_seg_out.reserve(dcap * n_segments, 16));
+    HIP_TRY(st->h_seg_out.reserve(dcap * n_segments));
+    HIP_TRY(hipMemcpyAsync(st->d_seg_first.p, first, n_segments * sizeof(uint64_t),
+                           hipMemcpyHostToDevice, st->stream));
+    HIP_TRY(hipMemcpyAsync(st->d_seg_count.p, count, n_segments * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, st->stream));
+    if (!din)
+        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
+                               st->stream));
+    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
+    if (rc < 0) return rc;
+    rc = demod_acquire_segments_async(st, st->d_sym.p, st->d_mag.p, n_windows, st->d_seg_first.p,
+                                      st->d_seg_count.p, n_segments, sync, sync_len, max_errors,
+                                      dcap ? st->d_seg_out.p : nullptr, dcap, st->d_seg_res.p,
+                                      st->d_seg_work.p, work, st->stream);
+    if (rc < 0) return rc;
+    HIP_TRY(hipMemcpyAsync(results, st->d_seg_res.p, n_segments * sizeof(*results),
+                           hipMemcpyDeviceToHost, st->stream));
+    // the rows through pinned staging in the same pass, then each row's written
+    // bytes to the caller's [S][cap]
+    if (dcap)
+        HIP_TRY(hipMemcpyAsync(st->h_seg_out.p, st->d_seg_out.p, dcap * n_segments,
+                               hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    unsigned long long total = 0;
+    for (size_t s = 0; s < n_segments; ++s) {
+        const size_t nw = (size_t)results[s].n_written;
+        if (nw) std::memcpy(out + s * cap, st->h_seg_out.p + s * dcap, nw);
+        total += nw;
+    }
+    return (int)total;
+}
+
+int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,
+                          uint64_t *first, uint32_t *count, size_t *n_windows)
+{
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "run_layout writes first[] as size_t");
+    if (validate_cfg(cfg) != DEMOD_OK || !n_samples || !n_windows) return DEMOD_BAD_ARG;
+    if (n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
+    // a batch below 2^31 windows: refused before anything is written
+    size_t W = 0;
+    const auto total = [&](size_t s) { return n_samples[s]; };
+    for (size_t s = 0; s < n_segments; ++s)
+        if (n_samples[s] / cfg->hop > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    if (run_layout(n_segments, cfg->n, cfg->hop, total, nullptr, nullptr, &W) > 0x7FFFFFFF)
+        return DEMOD_BAD_ARG;
+    *n_windows = run_layout(n_segments, cfg->n, cfg->hop, total, reinterpret_cast<size_t *>(first),
+                            count, &W);
+    return DEMOD_OK;
 }
 
 int demodulate_mags(demod_t *st, const int16_t *pcm, size_t n_frames, uint8_t *symbols,

@@ -142,6 +142,13 @@ struct demod {
     fskd::DevBuf<unsigned char> d_acq_work;
     fskd::DevBuf<demod_acquire_result_t> d_acq_res;
     fskd::DevBuf<uint8_t> d_acq_out;
+    // demod_acquire_segments: the tables, workspace, results and rows (first use)
+    fskd::DevBuf<uint64_t> d_seg_first;
+    fskd::DevBuf<uint32_t> d_seg_count;
+    fskd::DevBuf<unsigned char> d_seg_work;
+    fskd::DevBuf<demod_acquire_result_t> d_seg_res;
+    fskd::DevBuf<uint8_t> d_seg_out;
+    fskd::PinnedBuf<uint8_t> h_seg_out; // the rows on their way to the caller's [S][cap]
     fskd::PinnedBuf<int16_t> h_in;      // pinned staging for small host calls
     fskd::PinnedBuf<uint8_t> h_sym;
     fskd::PinnedBuf<float> h_mag;       // [h_sym.cap][k]

@@ -635,4 +635,38 @@ struct AcquireParams {
 int acquire_grid(long long n_windows);
 hipError_t launch_acquire(AcquireParams p, hipStream_t s);
 
+// acquire_segments.hip: the same acquisition over S segments of a batch, each
+// treated as a batch of its own. d_work is a header written by the plan launch
+// (per segment: clamped first and count, first tile, tiles) followed by one
+// partial and one first-match word per phase per tile.
+struct AcquireSegParams {
+    const uint8_t *sym;               // [n_windows]
+    const float *mag;                 // [n_windows][k]
+    const unsigned long long *seg_first;  // [n_segments], device, as the caller wrote it
+    const unsigned *seg_count;        // [n_segments]
+    long long n_windows;              // Wb
+    unsigned n_segments;
+    unsigned budget;                  // tiles the workspace holds
+    int phases;                       // R
+    int k;
+    int sync_len;
+    unsigned max_errors;
+    unsigned long long cap;
+    uint8_t *out;                     // [n_segments][cap] or nullptr (cap == 0)
+    ::demod_acquire_result *res;      // [n_segments]
+    // d_work
+    unsigned long long *w_first;      // [n_segments] min(first, Wb)
+    unsigned *w_count;                // [n_segments] min(count, Wb - first')
+    unsigned *w_tile0;                // [n_segments] tiles of the segments before it
+    unsigned *w_tiles;                // [n_segments] 0: a short segment
+    unsigned *w_total;                // [1] tiles of the call
+    double *part;                     // [budget][phases]
+    unsigned long long *first;        // [budget][phases] (w << 8 | errors), ~0: no match
+    uint8_t sync[64];
+};
+// Bytes of the header for S segments, and of one tile's words (8-byte multiples).
+constexpr size_t acquire_seg_header_bytes(size_t S) { return (20 * S + 4 + 7) / 8 * 8; }
+constexpr size_t acquire_seg_tile_bytes(size_t R) { return 16 * R; }
+hipError_t launch_acquire_segments(const AcquireSegParams &p, hipStream_t s);
+
 }  // namespace fskd

@@ -403,6 +403,105 @@ int demod_acquire(demod_t *st, const int16_t *pcm, size_t n_windows,
                   const uint8_t *sync, size_t sync_len, uint32_t max_errors,
                   uint8_t *out, size_t cap, demod_acquire_result_t *result);
 
+/* ---- segmented acquisition: S segments of one batch in one call -------- */
+/*
+ * The acquisition above treats a batch as one stream whose timing never
+ * moves. Here the batch holds S segments, segment s being batch windows
+ * first[s] .. first[s] + count[s] - 1, and each is acquired exactly as a batch
+ * of its own: with W = count[s] and window indices relative to first[s],
+ * results[s] and out[s cap + j], j < n_written, are what the definitions above
+ * give on (sym + first[s], P + first[s] K, count[s]); sync_window and
+ * first_window are segment-relative, the tail w >= J R of a segment is left
+ * out of its metric, and the sync word is compared only where
+ * w + (sync_len - 1) R < count[s]: it never reads past its segment. Segments
+ * that are the runs of many streams in one batch (demod_segments_layout) give
+ * per-stream acquisition; consecutive blocks of one long stream give a phase
+ * per block, so timing that moves (a dropped buffer, clock drift) is tracked.
+ * Segments may touch, leave gaps, come in any order and overlap.
+ *
+ * d_first (uint64) and d_count (uint32) are DEVICE arrays, read when the
+ * launches run: a captured graph may be replayed after they are rewritten in
+ * place. The host never sees them, so the kernels clamp: first' = min(first,
+ * n_windows), count' = min(count, n_windows - first'); no table content makes
+ * them read outside the inputs or write outside the outputs and d_work.
+ *
+ * Short segments: a segment with count' < R reports phases = R, phase = 0,
+ * per_phase = 0, metric all 0, sync_window = -1, sync_errors = 0,
+ * first_window = count', n_out = n_written = 0 and writes nothing to out.
+ *
+ * Tile budget: the workspace stores per tile of DEMOD_ACQUIRE_TILE windows
+ * (segment-relative; a segment of count' >= R windows has ceil(count' /
+ * DEMOD_ACQUIRE_TILE) tiles, a shorter one none) and
+ * demod_acquire_segments_workspace_size(cfg, S, Wmax) is a header for S
+ * segments plus B = ceil(Wmax / DEMOD_ACQUIRE_TILE) + S tiles, which disjoint
+ * segments of Wmax windows never exceed. A call's budget is the tiles its
+ * work_bytes hold beyond the header for n_segments. Segment s is acquired
+ * when the tiles of segments 0 .. s together are within the budget; the
+ * others are reported as short segments are (first_window = count'). Callers
+ * with overlapping segments size the workspace with a larger Wmax.
+ *
+ * Every sum's order depends on the segment's own (count', R): the same
+ * contents at another first[s], in another slot or beside other segments give
+ * bit-identical result and output bytes. No floating-point atomics.
+ */
+#define DEMOD_MAX_SEGMENTS 65536
+
+/* Bytes of d_work for up to max_segments segments of a batch of up to
+ * max_windows windows; monotone in both. 0 when the configuration is invalid
+ * (as demod_acquire_workspace_size), max_segments is 0 or above
+ * DEMOD_MAX_SEGMENTS, or max_windows >= 2^31. No device needed. */
+size_t demod_acquire_segments_workspace_size(const demod_cfg_t *cfg, size_t max_segments,
+                                             size_t max_windows);
+
+/*
+ * Enqueued on `stream`: four short launches whatever n_segments is (plan,
+ * scan, finalise, gather; three when cap == 0). Nothing is allocated or
+ * synchronised and the handle holds no state of the call; d_work may hold
+ * anything on entry (every word read is written first by the same call).
+ * d_out is [n_segments][cap] (NULL with cap 0); bytes of a row past its
+ * n_written are not written. Every byte of d_results[0 .. n_segments) is.
+ * Returns DEMOD_OK once enqueued; DEMOD_BAD_ARG, before any launch, for what
+ * demod_acquire_async refuses except n_windows < R (a per-segment outcome
+ * here), n_segments == 0 or > DEMOD_MAX_SEGMENTS, a NULL d_first or d_count,
+ * work_bytes below demod_acquire_segments_workspace_size(cfg, n_segments,
+ * n_windows), or a misaligned d_results, d_work, d_first (8 bytes) or d_count
+ * (4 bytes).
+ */
+int demod_acquire_segments_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                                 size_t n_windows, const uint64_t *d_first,
+                                 const uint32_t *d_count, size_t n_segments, const uint8_t *sync,
+                                 size_t sync_len, uint32_t max_errors, uint8_t *d_out, size_t cap,
+                                 demod_acquire_result_t *d_results, void *d_work,
+                                 size_t work_bytes, void *stream);
+
+/*
+ * The handle's detector over the n_windows sliding windows of pcm (a host or
+ * device pointer, as demod_acquire), then the segmented acquisition of its
+ * outputs. first, count, out ([n_segments][cap]; bytes of a row past its
+ * n_written are left alone) and results are HOST memory. The tables are
+ * checked here: a segment that leaves the batch or holds fewer than R windows
+ * is refused with DEMOD_BAD_ARG before the detector runs. Synchronous;
+ * handle-owned buffers grow on first use. Returns the sum of n_written or a
+ * negative code.
+ */
+int demod_acquire_segments(demod_t *st, const int16_t *pcm, size_t n_windows,
+                           const uint64_t *first, const uint32_t *count, size_t n_segments,
+                           const uint8_t *sync, size_t sync_len, uint32_t max_errors,
+                           uint8_t *out, size_t cap, demod_acquire_result_t *results);
+
+/*
+ * The batch layout demod_streams_push builds, for callers that hold S
+ * recordings: run s of n_samples[s] mono samples has count[s] = its complete
+ * windows, starts at batch window first[s] (sample first[s] hop of the batch)
+ * and takes ceil(((count[s] - 1) hop + n) / hop) batch windows; the windows
+ * between a run's last and the next run's first straddle two runs and belong
+ * to no segment. *n_windows receives the batch's windows. first and count may
+ * be NULL. Host only. DEMOD_OK, or DEMOD_BAD_ARG (an invalid configuration,
+ * n_segments == 0 or > DEMOD_MAX_SEGMENTS, a batch of 2^31 windows or more).
+ */
+int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,
+                          uint64_t *first, uint32_t *count, size_t *n_windows);
+
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
  * n_streams independent streams that share one configuration, each behaving
