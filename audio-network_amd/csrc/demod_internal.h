@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lane_ops.h"
+
 struct demod_acquire_result;  // include/demod.h
 
 namespace fskd {
@@ -177,19 +179,17 @@ __device__ __forceinline__ int chain_decide(const float (&P)[K], bool live, floa
 // read by `chunk(i)` (i < 8), as fp32 (each square and partial sum rounded:
 // relative error < 100 u, covered by error_model.cpp's safety factor in
 // amb_t2e).
-typedef unsigned int u32x4e __attribute__((ext_vector_type(4)));
-typedef float f32x2e __attribute__((ext_vector_type(2)));
 template <typename Chunk>
 __device__ __forceinline__ float seg_energy(Chunk chunk)
 {
-    f32x2e a = {0.f, 0.f}, b = {0.f, 0.f};
+    f2 a = {0.f, 0.f}, b = {0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const u32x4e d = chunk(i);
+        const u32x4 d = chunk(i);
         const unsigned d4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f32x2e x = {(float)(int)(short)(d4[q] & 0xFFFFu), (float)((int)d4[q] >> 16)};
+            const f2 x = {(float)(int)(short)(d4[q] & 0xFFFFu), (float)((int)d4[q] >> 16)};
             if (q & 1) b = __builtin_elementwise_fma(x, x, b);
             else a = __builtin_elementwise_fma(x, x, a);
         }
@@ -201,14 +201,14 @@ __device__ __forceinline__ float seg_energy(Chunk chunk)
 template <int U, typename Chunk>
 __device__ __forceinline__ float seg_energy_lowreg(Chunk chunk)
 {
-    f32x2e a = {0.f, 0.f}, b = {0.f, 0.f};
+    f2 a = {0.f, 0.f}, b = {0.f, 0.f};
 #pragma unroll U
     for (int i = 0; i < 8; ++i) {
-        const u32x4e d = chunk(i);
+        const u32x4 d = chunk(i);
         const unsigned d4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f32x2e x = {(float)(int)(short)(d4[q] & 0xFFFFu), (float)((int)d4[q] >> 16)};
+            const f2 x = {(float)(int)(short)(d4[q] & 0xFFFFu), (float)((int)d4[q] >> 16)};
             if (q & 1) b = __builtin_elementwise_fma(x, x, b);
             else a = __builtin_elementwise_fma(x, x, a);
         }
@@ -224,7 +224,7 @@ __device__ __forceinline__ float seg_energy_serial(Chunk chunk)
     float e = 0.f;
 #pragma unroll 1
     for (int i = 0; i < 8; ++i) {
-        const u32x4e d = chunk(i);
+        const u32x4 d = chunk(i);
         const unsigned d4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -266,16 +266,6 @@ __device__ __forceinline__ double row_sum16d(double v)
     v += dpp_d<0x141>(v);
     v += dpp_d<0x140>(v);
     return v;
-}
-
-// Output store; NTS = non-temporal (streamed once, never re-read by the kernel).
-template <bool NTS, typename T>
-__device__ __forceinline__ void out_store(T *ptr, T v)
-{
-    if (NTS)
-        __builtin_nontemporal_store(v, ptr);
-    else
-        *ptr = v;
 }
 
 // Tile-group index of this block. Blocks are dealt round-robin to the 8 XCDs
@@ -365,7 +355,7 @@ __device__ __forceinline__ bool rescue_rows_fold0(const GoertzelParams &p, long 
     for (int i = 0; i < 8; ++i) xf[i] = 0;
 #pragma unroll 1
     for (int m = 0; m < 8; ++m) {
-        const u32x4e d = chunk(16 * m + seg);
+        const u32x4 d = chunk(16 * m + seg);
         const unsigned d4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
         for (int i = 0; i < 8; ++i) xf[i] += (int)(short)((d4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
@@ -444,7 +434,7 @@ __device__ __forceinline__ void rescue_rows(const GoertzelParams &p, long long w
             if (run) {
 #pragma unroll 1
                 for (int q = q0; q < q1; ++q) {
-                    const u32x4e d = chunk(q);
+                    const u32x4 d = chunk(q);
                     const unsigned d4[4] = {d.x, d.y, d.z, d.w};
                     if (!exact && t == 0) e += dot_energy4(d4);
 #pragma unroll
@@ -598,7 +588,7 @@ constexpr int kDetResidue = 4;   // residue.hip: per-residue-class folding (any 
 hipError_t launch_detector(int detector, const GoertzelParams &p, hipStream_t s);
 // residue.hip: rotation table is [k][g][2] float4 {C1, C2}, {C3, C4}
 const void *residue_kernel_ptr(int k, int log2g, int dcls = 0, bool nt = true);
-size_t residue_lds_bytes(int k, int log2g, int qp = 2);
+size_t residue_lds_bytes(int k, int log2g);
 int tile_grid(long long n_windows, int log2g, int wpb = kWavesPerBlock, int wins_per_tile = 0);
 hipError_t synth_prepare();  // upload the sine table to the current device (once, locked)
 hipError_t launch_synth(const SynthParams &p, hipStream_t s);

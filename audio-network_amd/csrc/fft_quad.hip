@@ -34,118 +34,11 @@
 namespace fskd {
 namespace quad {
 
-// A complex number as a packed fp32 pair: complex add/sub is one v_pk_add_f32,
-// a complex product two packed ops. CDNA4 runs a packed op at the same flop
-// rate as two plain ones, but one wave issues half as many instructions — and
-// this kernel is issue-bound (one wave/SIMD issues a VALU op every 4 cycles).
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-// a * w (w in VGPRs): lo = a.x w.x - a.y w.y, hi = a.x w.y + a.y w.x
-__device__ __forceinline__ f2 cmul(f2 a, f2 w)
-{
-    f2 t, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(w));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] neg_lo:[0,0,1]" : "=v"(r) : "v"(a), "v"(w), "v"(t));
-    return r;
-}
-// a * w with w a compile-time constant (SGPR pair)
-__device__ __forceinline__ f2 cmulk(f2 a, f2 w)
-{
-    f2 t, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "s"(w));
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] neg_lo:[0,0,1]" : "=v"(r) : "v"(a), "s"(w), "v"(t));
-    return r;
-}
-// Two independent complex products in one block, ordered mul0 mul1 fma0 fma1.
-// gfx950 needs a wait state between a packed-fp32 VGPR write and an
-// immediately dependent packed read: the compiler pads every single cmul
-// (mul -> dependent fma) with an s_nop, which this ordering avoids.
-__device__ __forceinline__ void cmul2(f2 &r0, f2 a0, f2 w0, f2 &r1, f2 a1, f2 w1)
-{
-    f2 t0, t1;
-    asm("v_pk_mul_f32 %2, %4, %5 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-        "v_pk_mul_f32 %3, %6, %7 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-        "v_pk_fma_f32 %0, %4, %5, %2 op_sel_hi:[0,1,1] neg_lo:[0,0,1]\n\t"
-        "v_pk_fma_f32 %1, %6, %7, %3 op_sel_hi:[0,1,1] neg_lo:[0,0,1]"
-        : "=&v"(r0), "=&v"(r1), "=&v"(t0), "=&v"(t1)
-        : "v"(a0), "v"(w0), "v"(a1), "v"(w1));
-}
-// the same with both twiddles compile-time constants (SGPR pairs)
-__device__ __forceinline__ void cmulk2(f2 &r0, f2 a0, f2 w0, f2 &r1, f2 a1, f2 w1)
-{
-    f2 t0, t1;
-    asm("v_pk_mul_f32 %2, %4, %5 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-        "v_pk_mul_f32 %3, %6, %7 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-        "v_pk_fma_f32 %0, %4, %5, %2 op_sel_hi:[0,1,1] neg_lo:[0,0,1]\n\t"
-        "v_pk_fma_f32 %1, %6, %7, %3 op_sel_hi:[0,1,1] neg_lo:[0,0,1]"
-        : "=&v"(r0), "=&v"(r1), "=&v"(t0), "=&v"(t1)
-        : "v"(a0), "s"(w0), "v"(a1), "s"(w1));
-}
-// (|u|^2 of two pairs): p = (re.x^2 + im.x^2, re.y^2 + im.y^2) for two
-// independent (re, im), interleaved like cmul2
-__device__ __forceinline__ void pwr2(f2 &p0, f2 re0, f2 im0, f2 &p1, f2 re1, f2 im1)
-{
-    f2 t0, t1;
-    asm("v_pk_mul_f32 %2, %5, %5\n\t"
-        "v_pk_mul_f32 %3, %7, %7\n\t"
-        "v_pk_fma_f32 %0, %4, %4, %2\n\t"
-        "v_pk_fma_f32 %1, %6, %6, %3"
-        : "=&v"(p0), "=&v"(p1), "=&v"(t0), "=&v"(t1)
-        : "v"(re0), "v"(im0), "v"(re1), "v"(im1));
-}
-// x + (-i) y = (x.x + y.y, x.y - y.x)
-__device__ __forceinline__ f2 add_mj(f2 x, f2 y)
-{
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
-// x - (-i) y = (x.x - y.y, x.y + y.x)
-__device__ __forceinline__ f2 sub_mj(f2 x, f2 y)
-{
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
-// (-i) a = (a.y, -a.x), as a * (1, -1) with the halves swapped
-__device__ __forceinline__ f2 mj(f2 a)
-{
-    f2 r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,1]" : "=v"(r) : "v"(a), "s"((f2){1.0f, -1.0f}));
-    return r;
-}
-
-// Real-FFT post-pass pieces (fft1024_quad_kernel step 3), one packed op each:
-// S = P + conj Q
-__device__ __forceinline__ f2 pp_s(f2 P, f2 Q)
-{
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(P), "v"(Q));
-    return r;
-}
-// D = -i (P - conj Q) = (P.y + Q.y, Q.x - P.x)
-__device__ __forceinline__ f2 pp_d(f2 P, f2 Q)
-{
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,0] neg_hi:[1,0]" : "=v"(r) : "v"(P), "v"(Q));
-    return r;
-}
-// (S.x + T.x, S.x - T.x) and (S.y + T.y, S.y - T.y): the real / imaginary
-// parts of U = S + T and V = S - T side by side
-__device__ __forceinline__ f2 pp_re(f2 S, f2 T)
-{
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(r) : "v"(S), "v"(T));
-    return r;
-}
-__device__ __forceinline__ f2 pp_im(f2 S, f2 T)
-{
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] neg_hi:[0,1]" : "=v"(r) : "v"(S), "v"(T));
-    return r;
-}
-
+// A complex number as a packed fp32 pair (lane_ops.h f2): complex add/sub is
+// one v_pk_add_f32, a complex product two packed ops. CDNA4 runs a packed op at
+// the same flop rate as two plain ones, but one wave issues half as many
+// instructions — and this kernel is issue-bound (one wave/SIMD issues a VALU op
+// every 4 cycles).
 
 // lane % 16 == 0 ? a : b (lanes 0, 16, 32, 48 of the wave)
 __device__ __forceinline__ f2 sel_l0(f2 a, f2 b)
@@ -178,107 +71,12 @@ constexpr float kW32i[32] = {
     1.0f, 0.98078528040323043f, 0.92387953251128674f, 0.83146961230254524f,
     0.70710678118654752f, 0.55557023301960218f, 0.38268343236508977f, 0.19509032201612827f};
 
-// a * W32^J; the half and quarter turns are sign/swap operations.
-template <int J>
-__device__ __forceinline__ f2 w32(f2 a)
-{
-    constexpr int j = ((J % 32) + 32) % 32;
-    if constexpr (j == 0) return a;
-    else if constexpr (j == 8) return mj(a);
-    else if constexpr (j == 16) return -a;
-    else if constexpr (j == 24) return -mj(a);
-    else return cmulk(a, (f2){kW32r[j], kW32i[j]});
-}
-
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F &&f)
 {
     if constexpr (I < N) {
         f(std::integral_constant<int, I>{});
         static_for<I + 1, N>(f);
-    }
-}
-
-// The non-trivial twiddles W_N^{i2 k1} (not a multiple of a quarter turn) of
-// one dft<N> level: slot i2 + N2 k1 and the W32 exponent.
-template <int N>
-struct TwList {
-    static constexpr int N1 = (N == 32) ? 8 : 4, N2 = N / N1;
-    int slot[N];
-    int j[N];
-    int n;
-    constexpr TwList() : slot(), j(), n(0)
-    {
-        for (int i2 = 0; i2 < N2; ++i2)
-            for (int k1 = 1; k1 < N1; ++k1) {
-                const int jj = ((i2 * k1) * (32 / N)) % 32;
-                if (jj % 8) {
-                    slot[n] = i2 + N2 * k1;
-                    j[n] = jj;
-                    ++n;
-                }
-            }
-    }
-};
-
-// In-register DFT of x[0], x[S], ..., x[(N-1) S] (N = 2, 4, 8, 16, 32), result
-// in natural order in the same slots. Mixed radix N = N1 x N2 (N1 = 4 or 8):
-//   X[k1 + N1 k2] = sum_i2 W_N^{i2 k1} W_N2^{i2 k2} sum_i1 x[N2 i1 + i2] W_N1^{i1 k1}
-template <int N, int S = 1>
-__device__ __forceinline__ void dft(f2 *x)
-{
-    if constexpr (N == 2) {
-        const f2 a = x[0], b = x[S];
-        x[0] = a + b;
-        x[S] = a - b;
-    } else if constexpr (N == 4) {
-        const f2 a0 = x[0] + x[2 * S], a1 = x[0] - x[2 * S];
-        const f2 b0 = x[S] + x[3 * S], b1 = x[S] - x[3 * S];
-        x[0] = a0 + b0;
-        x[2 * S] = a0 - b0;
-        x[S] = add_mj(a1, b1);
-        x[3 * S] = sub_mj(a1, b1);
-    } else {
-        constexpr int N1 = (N == 32) ? 8 : 4;
-        constexpr int N2 = N / N1;
-        // DFT-N1 over i1 for every i2 (stride N2 S), then twiddle W_N^{i2 k1}:
-        // the quarter turns in place, the rest two at a time (cmulk2)
-        static_for<0, N2>([&](auto c) {
-            constexpr int i2 = decltype(c)::value;
-            dft<N1, N2 * S>(x + i2 * S);
-            static_for<1, N1>([&](auto d) {
-                constexpr int k1 = decltype(d)::value;
-                if constexpr (((i2 * k1) * (32 / N)) % 8 == 0)
-                    x[(i2 + N2 * k1) * S] = w32<(i2 * k1) * (32 / N)>(x[(i2 + N2 * k1) * S]);
-            });
-        });
-        constexpr TwList<N> L{};
-        static_for<0, (L.n + 1) / 2>([&](auto pc) {
-            constexpr int i0 = 2 * decltype(pc)::value, i1 = i0 + 1;
-            constexpr int s0 = L.slot[i0] * S, j0 = L.j[i0];
-            if constexpr (i1 < L.n) {
-                constexpr int s1 = L.slot[i1] * S, j1 = L.j[i1];
-                cmulk2(x[s0], x[s0], (f2){kW32r[j0], kW32i[j0]},
-                       x[s1], x[s1], (f2){kW32r[j1], kW32i[j1]});
-            } else {
-                x[s0] = cmulk(x[s0], (f2){kW32r[j0], kW32i[j0]});
-            }
-        });
-        // DFT-N2 over i2 for every k1 (contiguous run of N2 at N2 k1)
-        static_for<0, N1>([&](auto d) {
-            constexpr int k1 = decltype(d)::value;
-            dft<N2, S>(x + N2 * k1 * S);
-        });
-        // slot (N2 k1 + k2) S holds X[k1 + N1 k2]: rename to natural order
-        f2 t[N];
-        static_for<0, N>([&](auto e) {
-            constexpr int m = decltype(e)::value;  // m = N2 k1 + k2
-            t[(m / N2) + N1 * (m % N2)] = x[m * S];
-        });
-        static_for<0, N>([&](auto e) {
-            constexpr int m = decltype(e)::value;
-            x[m * S] = t[m];
-        });
     }
 }
 
@@ -299,129 +97,27 @@ __device__ __forceinline__ void dft(f2 *x)
 #define QTB_UM(U, Y, W) "v_pk_fma_f32 " U ", " Y ", " W ", " U " op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[0,1,0]\n\t"
 #define QTB_V(V, X, TWO, U) "v_pk_fma_f32 " V ", " X ", " TWO ", " U " neg_lo:[0,0,1] neg_hi:[0,0,1]"
 
-// pair 0 with w0, pair 1 with w1 (both SGPR pairs: compile-time constants)
-__device__ __forceinline__ void tbk2(f2 &u0, f2 &v0, f2 x0, f2 y0, f2 w0, f2 &u1, f2 &v1, f2 x1,
-                                     f2 y1, f2 w1)
-{
-    asm(QTB_T("%0", "%5", "%6", "%4") QTB_T("%2", "%8", "%9", "%7")
-        QTB_U("%0", "%5", "%6") QTB_U("%2", "%8", "%9")
-        QTB_V("%1", "%4", "%10", "%0") "\n\t" QTB_V("%3", "%7", "%10", "%2")
-        : "=&v"(u0), "=&v"(v0), "=&v"(u1), "=&v"(v1)
-        : "v"(x0), "v"(y0), "s"(w0), "v"(x1), "v"(y1), "s"(w1), "s"((f2){2.0f, 2.0f}));
-}
-// pair 0 with w, pair 1 with -j w (MJ1) or w (!MJ1); w a VGPR pair (per-lane table)
-template <bool MJ1>
-__device__ __forceinline__ void tbv2(f2 &u0, f2 &v0, f2 x0, f2 y0, f2 &u1, f2 &v1, f2 x1, f2 y1,
-                                     f2 w)
-{
-    if constexpr (MJ1)
-        asm(QTB_T("%0", "%5", "%8", "%4") QTB_TM("%2", "%7", "%8", "%6")
-            QTB_U("%0", "%5", "%8") QTB_UM("%2", "%7", "%8")
-            QTB_V("%1", "%4", "%9", "%0") "\n\t" QTB_V("%3", "%6", "%9", "%2")
-            : "=&v"(u0), "=&v"(v0), "=&v"(u1), "=&v"(v1)
-            : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "v"(w), "s"((f2){2.0f, 2.0f}));
-    else
-        asm(QTB_T("%0", "%5", "%8", "%4") QTB_T("%2", "%7", "%8", "%6")
-            QTB_U("%0", "%5", "%8") QTB_U("%2", "%7", "%8")
-            QTB_V("%1", "%4", "%9", "%0") "\n\t" QTB_V("%3", "%6", "%9", "%2")
-            : "=&v"(u0), "=&v"(v0), "=&v"(u1), "=&v"(v1)
-            : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "v"(w), "s"((f2){2.0f, 2.0f}));
-}
-
-// W32^E trivial (a quarter turn)?
-constexpr bool w32_trivial(int e) { return (((e % 32) + 32) % 32) % 8 == 0; }
+// W32^E (a compile-time constant: an SGPR pair)
 template <int E>
 __device__ __forceinline__ f2 w32c()
 {
     constexpr int j = ((E % 32) + 32) % 32;
     return (f2){kW32r[j], kW32i[j]};
 }
-// (u, v) = (x + W32^E y, x - W32^E y) for a quarter-turn E
-template <int E>
-__device__ __forceinline__ void tb_triv(f2 &u, f2 &v, f2 x, f2 y)
-{
-    constexpr int j = ((E % 32) + 32) % 32;
-    static_assert(j % 8 == 0, "quarter turn");
-    if constexpr (j == 0) { u = x + y; v = x - y; }
-    else if constexpr (j == 16) { u = x - y; v = x + y; }
-    else if constexpr (j == 8) { u = add_mj(x, y); v = sub_mj(x, y); }   // w = -j
-    else { u = sub_mj(x, y); v = add_mj(x, y); }                          // w = +j
-}
-// two pairs, W32^E0 and W32^E1, both trivial or both not
-template <int E0, int E1>
-__device__ __forceinline__ void tbk2c(f2 &u0, f2 &v0, f2 x0, f2 y0, f2 &u1, f2 &v1, f2 x1, f2 y1)
-{
-    static_assert(w32_trivial(E0) == w32_trivial(E1), "pair kinds");
-    if constexpr (w32_trivial(E0)) {
-        tb_triv<E0>(u0, v0, x0, y0);
-        tb_triv<E1>(u1, v1, x1, y1);
-    } else {
-        tbk2(u0, v0, x0, y0, w32c<E0>(), u1, v1, x1, y1, w32c<E1>());
-    }
-}
 
-// DFT-4 of (y0, w y1, w^2 y2, w^3 y3) at x[0], x[S], x[2S], x[3S] (natural
-// order out), w = W32^E: four fused butterflies,
+// The geometric DFT-4: of (y0, w y1, w^2 y2, w^3 y3) at x[0], x[S], x[2S],
+// x[3S] (natural order out), four fused butterflies in two stages,
 //   a = y0 +- w^2 y2, c = y1 +- w^2 y3, X0/X2 = a0 +- w c0, X1/X3 = a1 +- (-j w) c1.
-template <int E, int S>
-__device__ __forceinline__ void dft4_geo_k(f2 *x)
-{
-    f2 a0, a1, c0, c1;
-    tbk2c<2 * E, 2 * E>(a0, a1, x[0], x[2 * S], c0, c1, x[S], x[3 * S]);
-    f2 X0, X1, X2, X3;
-    tbk2c<E, E + 8>(X0, X2, a0, c0, X1, X3, a1, c1);
-    x[0] = X0;
-    x[S] = X1;
-    x[2 * S] = X2;
-    x[3 * S] = X3;
-}
-// the same with a per-lane w (VGPRs) and its square w2
-template <int S>
-__device__ __forceinline__ void dft4_geo_v(f2 *x, f2 w, f2 w2)
-{
-    f2 a0, a1, c0, c1;
-    tbv2<false>(a0, a1, x[0], x[2 * S], c0, c1, x[S], x[3 * S], w2);
-    f2 X0, X1, X2, X3;
-    tbv2<true>(X0, X2, a0, c0, X1, X3, a1, c1, w);
-    x[0] = X0;
-    x[S] = X1;
-    x[2 * S] = X2;
-    x[3 * S] = X3;
-}
-
-// The same two butterfly stages as ONE asm block (12 packed FMAs): every
-// result is read two or more instructions after it is written, so the block
-// needs none of the packed-write s_nops the two separate blocks cost at their
-// seam (the second block's first pairs read the first block's last results).
-// Operands: %0-%3 X0..X3 (out), %4-%7 a0 a1 c0 c1 (scratch), %8-%11 x0..x3,
-// %12 w (second stage; the -j w pair by modifiers), %13 w^2 (first stage),
-// %14 (2, 2).
-#define QF_STAGES(WA, WB, TMB, UMB)                                                        \
-    QTB_T("%4", "%10", WA, "%8") QTB_T("%6", "%11", WA, "%9")                              \
-    QTB_U("%4", "%10", WA) QTB_U("%6", "%11", WA)                                          \
-    QTB_V("%5", "%8", "%14", "%4") "\n\t" QTB_V("%7", "%9", "%14", "%6") "\n\t"         \
-    QTB_T("%0", "%6", WB, "%4") TMB("%1", "%7", WB, "%5")                                   \
-    QTB_U("%0", "%6", WB) UMB("%1", "%7", WB)                                               \
-    QTB_V("%2", "%4", "%14", "%0") "\n\t" QTB_V("%3", "%5", "%14", "%1")
-template <int S>
-__device__ __forceinline__ void dft4_fused_v(f2 *x, f2 w, f2 w2)
-{
-    f2 X0, X1, X2, X3, a0, a1, c0, c1;
-    asm(QF_STAGES("%13", "%12", QTB_TM, QTB_UM)
-        : "=&v"(X0), "=&v"(X1), "=&v"(X2), "=&v"(X3), "=&v"(a0), "=&v"(a1), "=&v"(c0), "=&v"(c1)
-        : "v"(x[0]), "v"(x[S]), "v"(x[2 * S]), "v"(x[3 * S]), "v"(w), "v"(w2),
-          "s"((f2){2.0f, 2.0f}));
-    x[0] = X0;
-    x[S] = X1;
-    x[2 * S] = X2;
-    x[3 * S] = X3;
-}
-
-// Two independent dft4_fused_v, interleaved instruction by instruction
-// (dependent results four instructions apart) and updated in place (the
-// first stage's inputs are dead once it has run): %0-%3 / %4-%7 the two
-// DFT-4s' x0..x3 (in / out), %8-%15 scratch a0 a1 c0 c1 of each, %16 / %17
-// w / w^2 of the first, %18 / %19 of the second, %20 (2, 2).
+// Every form below is ONE asm block in which each result is read two or more
+// instructions after it is written, so it needs none of the packed-write
+// s_nops (and scheduling barriers) that separate blocks cost at their seams.
+//
+// Two independent geometric DFT-4s, each with a per-lane w (VGPRs) and its
+// square w2, interleaved instruction by instruction (dependent results four
+// instructions apart) and updated in place (the first stage's inputs are dead
+// once it has run); the -j w pair by modifiers (QTB_TM / QTB_UM).
+// %0-%3 / %4-%7 the two DFT-4s' x0..x3 (in / out), %8-%15 scratch a0 a1 c0 c1
+// of each, %16 / %17 w / w^2 of the first, %18 / %19 of the second, %20 (2, 2).
 template <int S>
 __device__ __forceinline__ void dft4x2_fused_v(f2 *xa, f2 *xb, f2 wa, f2 w2a, f2 wb, f2 w2b)
 {
@@ -446,7 +142,7 @@ __device__ __forceinline__ void dft4x2_fused_v(f2 *xa, f2 *xb, f2 wa, f2 w2a, f2
         : "v"(wa), "v"(w2a), "v"(wb), "v"(w2b), "s"((f2){2.0f, 2.0f}));
 }
 
-// dft4_geo_k<E, S> as one block when neither w^2 = W32^{2E} nor w is a
+// The geometric DFT-4 with w = W32^E when neither w^2 = W32^{2E} nor w is a
 // quarter turn: first stage both pairs with w^2, second stage w and -j w =
 // W32^{E+8}, all SGPR constants (%12 w, %13 w^2, %15 -j w).
 #define QF_STAGES_K                                                                         \
@@ -470,13 +166,13 @@ __device__ __forceinline__ void dft4_fused_k(f2 *x)
     x[3 * S] = X3;
 }
 
-// FUSED 3: the trivial-twiddle pieces of the DFT-32 as single blocks too.
-// x + (-j) y and x - (-j) y as instruction text (add_mj / sub_mj)
+// The trivial-twiddle pieces of the DFT-32 as single blocks too.
+// x + (-j) y and x - (-j) y as instruction text
 #define QA_MJ(R, X, Y) "v_pk_add_f32 " R ", " X ", " Y " op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]\n\t"
 #define QS_MJ(R, X, Y) "v_pk_add_f32 " R ", " X ", " Y " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
 #define QADD(R, X, Y) "v_pk_add_f32 " R ", " X ", " Y "\n\t"
 #define QSUB(R, X, Y) "v_pk_add_f32 " R ", " X ", " Y " neg_lo:[0,1] neg_hi:[0,1]\n\t"
-// DFT-4 with no twiddles (dft4_geo_k<0>): 8 packed adds.
+// DFT-4 with no twiddles (w = 1): 8 packed adds.
 // %0-%3 X0..X3, %4-%7 a0 a1 c0 c1, %8-%11 x0..x3
 template <int S>
 __device__ __forceinline__ void dft4_triv(f2 *x)
@@ -492,7 +188,7 @@ __device__ __forceinline__ void dft4_triv(f2 *x)
     x[2 * S] = X2;
     x[3 * S] = X3;
 }
-// dft4_geo_k<E> with w^2 = -j (E = 4): first stage add_mj / sub_mj, second
+// The geometric DFT-4 with w^2 = -j (E = 4): first stage QA_MJ / QS_MJ, second
 // stage w = W32^E and -j w = W32^{E+8} (%12, %13 SGPR pairs, %14 (2, 2)).
 template <int E, int S>
 __device__ __forceinline__ void dft4_fused_kq(f2 *x)
@@ -535,48 +231,35 @@ __device__ __forceinline__ void dft8_last(f2 *x)
 // order out, every twiddle fused into the butterfly that consumes it.
 // Mixed radix N = N1 x N2 (N2 = 4, or 2 at N = 8): DFT-N1 over i1 for each i2,
 // then per k1 a DFT-N2 over i2 of the twiddled column, which is geometric in
-// w = W_N^{k1} (dft4_geo_k).
-// L (FUSED level): >= 1 both-nontrivial DFT-4s as one block, >= 3 the
-// trivial pieces too.
-template <int N, int S = 1, int L = 0>
+// w = W_N^{k1}: the asm block written for its twiddles (w = 1: dft4_triv;
+// w^2 = -j: dft4_fused_kq; else dft4_fused_k; the DFT-8's last stage:
+// dft8_last).
+template <int N, int S = 1>
 __device__ __forceinline__ void dftf(f2 *x)
 {
     if constexpr (N == 4) {
-        if constexpr (L >= 3)
-            dft4_triv<S>(x);
-        else
-            dft4_geo_k<0, S>(x);
+        dft4_triv<S>(x);
     } else if constexpr (N == 8) {
-        dftf<4, 2 * S, L>(x);       // i2 = 0: X[k1] at slot 2 k1
-        dftf<4, 2 * S, L>(x + S);   // i2 = 1: X[k1] at slot 2 k1 + 1
+        dftf<4, 2 * S>(x);       // i2 = 0: X[k1] at slot 2 k1
+        dftf<4, 2 * S>(x + S);   // i2 = 1: X[k1] at slot 2 k1 + 1
         // per k1: (slot 2k1, slot 2k1+1) -> X[k1], X[k1 + 4], twiddle W8^k1 = W32^{4 k1}
-        if constexpr (L >= 3) {
-            dft8_last<S>(x);
-            return;
-        }
-        f2 u0, v0, u1, v1, u2, v2, u3, v3;
-        tb_triv<0>(u0, v0, x[0], x[S]);
-        tb_triv<8>(u2, v2, x[4 * S], x[5 * S]);
-        tbk2c<4, 12>(u1, v1, x[2 * S], x[3 * S], u3, v3, x[6 * S], x[7 * S]);
-        x[0] = u0; x[S] = u1; x[2 * S] = u2; x[3 * S] = u3;
-        x[4 * S] = v0; x[5 * S] = v1; x[6 * S] = v2; x[7 * S] = v3;
+        dft8_last<S>(x);
     } else {
         constexpr int N1 = N / 4;   // 8 (N = 32) or 4 (N = 16)
         static_for<0, 4>([&](auto c) {
             constexpr int i2 = decltype(c)::value;
-            dftf<N1, 4 * S, L>(x + i2 * S);   // X[k1] of column i2 at slot i2 + 4 k1
+            dftf<N1, 4 * S>(x + i2 * S);   // X[k1] of column i2 at slot i2 + 4 k1
         });
         static_for<0, N1>([&](auto d) {
             constexpr int k1 = decltype(d)::value;
             constexpr int E = k1 * (32 / N);
-            if constexpr (L >= 1 && !w32_trivial(E) && !w32_trivial(2 * E))
-                dft4_fused_k<E, S>(x + 4 * k1 * S);
-            else if constexpr (L >= 3 && ((E % 32) + 32) % 32 == 0)
+            static_assert(E >= 0 && E < 8, "w = W32^E short of a quarter turn");
+            if constexpr (E == 0)
                 dft4_triv<S>(x + 4 * k1 * S);
-            else if constexpr (L >= 3 && !w32_trivial(E) && ((2 * E) % 32 + 32) % 32 == 8)
+            else if constexpr (E == 4)
                 dft4_fused_kq<E, S>(x + 4 * k1 * S);
             else
-                dft4_geo_k<E, S>(x + 4 * k1 * S);   // slot 4 k1 + k2 = X[k1 + N1 k2]
+                dft4_fused_k<E, S>(x + 4 * k1 * S);   // slot 4 k1 + k2 = X[k1 + N1 k2]
         });
         f2 t[N];
         static_for<0, N>([&](auto e) {
@@ -588,23 +271,6 @@ __device__ __forceinline__ void dftf(f2 *x)
             x[m * S] = t[m];
         });
     }
-}
-
-// Real post-pass with the 1/2 of X = (S + W D)/2 folded into two FMAs (T
-// carries W/2): (S.x/2 + T.x, S.x/2 - T.x) and (S.y/2 + T.y, S.y/2 - T.y)
-__device__ __forceinline__ f2 pp_re_h(f2 S, f2 T)
-{
-    f2 r;
-    asm("v_pk_fma_f32 %0, %1, %3, %2 op_sel_hi:[0,1,0] neg_hi:[0,0,1]"
-        : "=v"(r) : "v"(S), "v"(T), "s"((f2){0.5f, 0.5f}));
-    return r;
-}
-__device__ __forceinline__ f2 pp_im_h(f2 S, f2 T)
-{
-    f2 r;
-    asm("v_pk_fma_f32 %0, %1, %3, %2 op_sel:[1,0,1] neg_hi:[0,0,1]"
-        : "=v"(r) : "v"(S), "v"(T), "s"((f2){0.5f, 0.5f}));
-    return r;
 }
 
 // Two mirror pairs of the real post-pass as one block (16 packed ops):
@@ -668,18 +334,8 @@ constexpr int kQWin = 16 * kQRow;    // complex per window
 constexpr int kQSlab = 4 * kQWin;    // complex per wave
 static_assert(4 * kQPow <= 2 * kQSlab, "bin powers of 4 windows must fit the slab");
 
-// Typed (format) buffer loads, for the FMT variant below.
-namespace quad {
-typedef int i4 __attribute__((ext_vector_type(4)));
-__device__ f2 raw_buffer_load_format_v2f32(i4 rsrc, int voffset, int soffset, int aux)
-    __asm("llvm.amdgcn.raw.buffer.load.format.v2f32");
-// buffer descriptor word 3: DST_SEL x,y,z,w = 4,5,6,7; NUM_FORMAT 3 (SSCALED);
-// DATA_FORMAT 5 (16_16)
-constexpr int kFmtWord3 = 0xFAC | (3 << 12) | (5 << 15);
-}  // namespace quad
-
 // fft1024_quad_kernel (round 2): the quad layout with every twiddle fused into the
-// butterfly that consumes it (dftf, dft4_geo_*), the stage-1 twiddle moved
+// butterfly that consumes it (dftf, dft4x2_fused_v), the stage-1 twiddle moved
 // behind the transpose and the 1/2 of the real split folded into the
 // post-pass FMAs:
 //   * stage 1: DFT-32 over n1 (compile-time twiddles fused), transposed raw;
@@ -691,67 +347,69 @@ constexpr int kFmtWord3 = 0xFAC | (3 << 12) | (5 << 15);
 //     lane and column v, v^2, g_k1, g_k1^2 come from a 2.5 KiB LDS table
 //     (tw2), -j w by operand modifiers;
 //   * post-pass: T = (W/2) D (tw3 holds W1024^kP / 2), (re, im) pairs by FMA
-//     with 1/2 (pp_re_h / pp_im_h).
+//     with 1/2 (postpair2).
 // 514 instead of 575 packed instructions per group of 4 windows.
-// PF: 1 = the next group's 32 loads go out during the transpose (32 VGPRs live
-// across stage 2 and the post-pass), 0 = each group loads at the top of its
-// iteration and the co-resident waves cover the latency (4 waves/SIMD at
-// MINW = 4 without spills: 104-116 VGPRs), 2 (SPEC + SPL) = the next group's
-// loads go out after the post-pass, ahead of the spectrum stores.
+// 4-wave blocks, 4 waves per SIMD asked for (104-116 VGPRs without spills);
+// each group loads at the top of its iteration and the co-resident waves
+// cover the latency; every DFT-4 stage pair, the DFT-32's trivial pieces and
+// the post-pass pairs are single asm blocks (stage 2: two DFT-4s per block).
 // SPEC: false = symbols (+ tone powers) only: the tone powers are picked
 // from the registers of the lanes that hold them (p.slot, a wave-uniform
 // index: s_set_gpr_idx) instead of going through the 2 KiB per-window power
 // slab in LDS; true = the slab, for the full-spectrum store.
-// PICK (SPEC false): 0 = each lane keeps the best and second tone it owns
-// (per tone: a compare chain, selects and an exec-masked magnitude store),
-// then the row argmax; 1 = tone i's power is gathered into lane i of its row
-// by one ds_bpermute, so lanes t < K hold tone t like the slab pick leaves
-// them (4 VALU per tone instead of ~27, one coalesced magnitude store).
-// AUX: the loads' cache-policy bits (2 = nt, 1 = sc0, 0 = plain; launch_fft_quad).
-// FUSED: 1 = each DFT-4's two butterfly stages as one asm block
-// (dft4_fused_v / _k), 2 = also the post-pass pairs (postpair2), 3 = also
-// the DFT-32's trivial-twiddle DFT-4s and DFT-8 stages (dft4_triv,
-// dft4_fused_kq, dft8_last), 4 = stage 2's DFT-4s two per block,
-// interleaved (dft4x2_fused_v); the separate blocks cost an s_nop and a
-// scheduling barrier at every seam.
-// FMT (PF = 0 only): typed buffer loads (16_16 SSCALED) convert both int16
-// halves to fp32 in the texture path instead of 64 VALU converts per group
-// (measured neutral).
-// SPL (with SPEC): 1 = the bin powers go to the slab as the output's own
+// PICK (SPEC false; 0 with SPEC): 1 = tone i's power is gathered into lane i
+// of its row by one ds_bpermute, so lanes t < K hold tone t like the slab pick
+// leaves them (4 VALU per tone, one coalesced magnitude store); 2 = the same
+// over only the post-pass pair blocks that hold a tone bin (p.pmask).
+// AUX: the loads' cache-policy bits (2 = nt, 0 = plain; launch_fft_quad).
+// SPL (with SPEC): 2 = the bin powers go to the slab as the output's own
 // layout (4 windows x 513 floats, contiguous, bin b of window q at float
 // 513 q + b; each lane's pair j lands at its bins by immediate offsets), and
-// the group's live windows leave as one contiguous run of 16-byte stores
-// (9 ds_read_b128 + 9 dwordx4 stores per lane, 1 KiB per wave instruction);
-// 2 = the same with non-temporal stores (the spectrum is written once);
+// the group's live windows leave as one contiguous run of non-temporal
+// 16-byte stores (9 ds_read_b128 + 9 dwordx4 stores per lane, 1 KiB per wave
+// instruction; the spectrum is written once);
 // 0 = the quad_slot layout, 33 scattered dword stores per lane.
-// OVL (FUSED 4): round 1 of the transpose overlaps column 0's DFT-16. Column
+// OVL: round 1 of the transpose overlaps column 0's DFT-16. Column
 // 0's twiddles are read right behind round 0's column reads, round 1's writes
 // and reads follow, and column 0's DFT-16 runs while they are in flight (the
 // waits land on the first use of round 1's data, not before column 0's
 // math); the next group's round-0 writes are ordered behind them.
-// TW3R: the post-pass twiddles W1024^kP / 2 from registers instead of the
-// LDS table tw3: kP = te + 32 j, so the twiddle is a per-lane base
-// W1024^te / 2 (te = t, or 16 for lane 0's pairs j < 8) times the
-// compile-time W32^j — one packed complex product (29 VALU per group) in
-// place of 8 ds_read2_b64.
-template <int WPB = 4, int MINW = 4, int PF = 0, bool SPEC = true, bool FMT = false, int AUX = 2,
-          int FUSED = 0, int RD = 0, int SPL = 0, int OVL = 0, int TW3R = 0, int RSC = 1, int PICK = 0>
+// Variants scripts/fft_probe.hip tried and did not ship; their source is in
+// git history at f48c2d8 (the measurements: DESIGN.md §4.4):
+//   PF 1 / 2   the next group's 32 loads during the transpose, or after the
+//              post-pass ahead of the spectrum stores: 1.71-1.94 ms against
+//              1.71 ms at hop 256 with 3 or 4 waves per SIMD.
+//   WPB, MINW  other block sizes and waves-per-SIMD requests (as above).
+//   FMT        typed buffer loads (16_16 SSCALED) convert both int16 halves
+//              in the texture path, 64 VALU converts fewer per group: +-2 %.
+//   FUSED < 4  fewer pieces as single asm blocks (the separate blocks cost an
+//              s_nop and a scheduling barrier at every seam): launch_fft_quad
+//              has the numbers.
+//   RD 1 / 2   (fft1024_quad_kernel_r64) the backend's LDS-access pairing off,
+//              and the twiddle tables lane-major, one ds_read_b128 per pair:
+//              1.699 / 1.660 ms against 1.661 ms.
+//   SPL 1      the linear slab with plain stores: 2.85-2.89 ms against 2.73 ms
+//              non-temporal.
+//   TW3R       the post-pass twiddles W1024^kP / 2 from registers (a per-lane
+//              base times the compile-time W32^j) instead of the LDS table
+//              tw3: -1 %, but other bits than the table's.
+//   RSC 0 / 2  no in-kernel rescue (probe A/B), and the block's flagged
+//              windows dealt round-robin to its waves.
+//   PICK 0     without SPEC: each lane keeps the best and second tone it owns
+//              (~27 VALU per tone), then the row argmax: +1.7 to 1.8 %.
+template <bool SPEC, int AUX, int SPL, int OVL, int PICK>
 __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const FftParams &p)
 {
-    static_assert(!OVL || (FUSED >= 4 && PF != 1), "OVL: the FUSED 4 column DFT-16");
-    static_assert(PF != 2 || (SPEC && SPL), "PF 2: ahead of the linear-slab spectrum stores");
-    static_assert(!SPL || SPEC, "SPL: the linear power slab of the spectrum store");
+    constexpr int WPB = 4;
+    static_assert(SPL == 0 || (SPEC && SPL == 2), "SPL: the linear power slab of the spectrum store");
+    static_assert(SPEC ? PICK == 0 && !OVL : PICK == 1 || PICK == 2, "PICK: the tones-only tone pick");
     using namespace quad;
     __shared__ __attribute__((aligned(16))) f2 slab[WPB][kQSlab];
-    // RD < 2: tw2 [column slot][v, v2, g0, g0^2, .., g3, g3^2][t], tw3 [j][t];
-    // RD 2: lane-major, [slot][t][m] and [t][j] (row padded to 18), so each
-    // pair used together is one 16-byte read; the row strides (20 and 36
-    // dwords) put a ds_read_b128 group's 16 addresses on distinct banks
-    constexpr int kT3 = RD >= 2 ? 18 : 16;
+    // tw2 [column slot][v, v2, g0, g0^2, .., g3, g3^2][t], tw3 [j][t]
     __shared__ __attribute__((aligned(16))) f2 tw2[2 * 10 * 16];
-    __shared__ __attribute__((aligned(16))) f2 tw3[16 * kT3];
-    auto tw2_at = [](int sl, int m, int tt) { return RD >= 2 ? sl * 160 + tt * 10 + m : sl * 160 + m * 16 + tt; };
-    auto tw3_at = [](int j, int tt) { return RD >= 2 ? tt * kT3 + j : j * 16 + tt; };
+    __shared__ __attribute__((aligned(16))) f2 tw3[16 * 16];
+    auto tw2_at = [](int sl, int m, int tt) { return sl * 160 + m * 16 + tt; };
+    auto tw3_at = [](int j, int tt) { return j * 16 + tt; };
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int q = lane >> 4;   // window of the wave
@@ -778,12 +436,6 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
     const int mybin = t < p.k ? p.bins[t] : 0;
     const int myslot = SPL ? q * 513 + mybin : quad_slot(mybin);
     float *pw = reinterpret_cast<float *>(slab[wave]);
-    // TW3R: this lane's post-pass twiddle bases (pairs j < 8 and j >= 8)
-    f2 tb_lo = (f2){0.f, 0.f}, tb_hi = (f2){0.f, 0.f};
-    if constexpr (TW3R) {
-        tb_lo = 0.5f * t1024[t == 0 ? 16 : t];
-        tb_hi = 0.5f * t1024[t];
-    }
     const int rowaddr = (lane & 48) * 4;  // byte address of this window row's lane 0 (ds_bpermute)
     __syncthreads();
 
@@ -791,9 +443,7 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
     const long long stride = (long long)gridDim.x * WPB;
     long long g = tile_block(p.xcd_swizzle) * WPB + wave;
     const long long g_first = g;
-    static_assert(!FMT || PF == 0, "FMT loads straight into a[]");
-    uint32_t nx[FMT ? 1 : 32];
-    f2 nxf[FMT ? 32 : 1];
+    uint32_t nx[32];
     // One buffer descriptor per group (wave-uniform base = its first window);
     // the lane offset is the window's start + 4 t bytes, and z[t + 16 n1] is
     // the immediate offset 64 n1 (< 4 KiB). Windows past the end are clamped
@@ -802,41 +452,29 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
         const long long w0 = 4 * gg;
         const long long left = p.n_windows - w0;  // >= 1
         const long long wq = q < left ? q : left - 1;
+        // (lane_ops.h tile_rsrc, spelled out: through it the compiler orders
+        // the kernel's scalar loads differently)
         long long bytes = ((left - 1) * p.hop + 1024) * 2;
         if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             (void *)(p.pcm + w0 * p.hop), (short)0, (int)bytes, 0x00020000);
         const int voff = (int)(wq * p.hop * 2) + 4 * t;
-        if constexpr (FMT) {
-            const unsigned long long base = (unsigned long long)(p.pcm + w0 * p.hop);
-            const i4 rf = {(int)(unsigned)base, (int)((base >> 32) & 0xFFFF), (int)bytes, kFmtWord3};
 #pragma unroll
-            for (int n1 = 0; n1 < 32; ++n1)
-                nxf[n1] = raw_buffer_load_format_v2f32(rf, voff + 64 * n1, 0, AUX);
-        } else {
-#pragma unroll
-            for (int n1 = 0; n1 < 32; ++n1)
-                nx[n1] = __builtin_amdgcn_raw_buffer_load_b32(rs, voff + 64 * n1, 0, AUX);
-        }
+        for (int n1 = 0; n1 < 32; ++n1)
+            nx[n1] = __builtin_amdgcn_raw_buffer_load_b32(rs, voff + 64 * n1, 0, AUX);
     };
-    if (PF && g < n_groups) load_group(g);
     for (; g < n_groups; g += stride) {
         const long long w = 4 * g + q;
-        if (!PF) load_group(g);
+        load_group(g);
         f2 a[32];
 #pragma unroll
         for (int n1 = 0; n1 < 32; ++n1) {
-            if constexpr (FMT) {
-                a[n1] = nxf[n1];
-                continue;
-            }
-            a[n1] = (f2){(float)(int)(short)(nx[FMT ? 0 : n1] & 0xFFFFu),
-                         (float)((int)nx[FMT ? 0 : n1] >> 16)};
+            a[n1] = (f2){(float)(int)(short)(nx[n1] & 0xFFFFu), (float)((int)nx[n1] >> 16)};
             asm("" : "+v"(a[n1]));  // opaque: keep (float)a + (float)b a packed add
         }
 
         // 1. DFT-32 over n1 (fused twiddles), no stage-1 twiddle here
-        dftf<32, 1, FUSED>(a);
+        dftf<32>(a);
 
         // 2. transpose in two column rounds; lane (q, t') gets columns
         //    k1 = t' (round 0) and k1b (round 1) of its window
@@ -844,23 +482,11 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
         f2 *win = slab[wave] + q * kQWin;
         // twp(sl, m): the pair (m, m + 1) of slot sl, m even
         auto twp = [&](int sl, int m, f2 &lo, f2 &hi) {
-            if constexpr (RD >= 2) {
-                const f4 x = *reinterpret_cast<const f4 *>(&tw2[tw2_at(sl, m, t)]);
-                lo = (f2){x.x, x.y};
-                hi = (f2){x.z, x.w};
-            } else {
-                lo = tw2[tw2_at(sl, m, t)];
-                hi = tw2[tw2_at(sl, m + 1, t)];
-            }
+            lo = tw2[tw2_at(sl, m, t)];
+            hi = tw2[tw2_at(sl, m + 1, t)];
         };
-        auto twv = [&](int sl, int m) -> f2 { return tw2[tw2_at(sl, m, t)]; };
-        // one column's DFT-16 (FUSED 4) with its ten twiddles given
-        auto col16 = [&](f2 *bb, f2 v, f2 v2, f2 g0, f2 g0s, f2 g1, f2 g1s, f2 g2, f2 g2s, f2 g3,
-                         f2 g3s) {
-            dft4x2_fused_v<4>(bb + 0, bb + 1, v, v2, v, v2);
-            dft4x2_fused_v<4>(bb + 2, bb + 3, v, v2, v, v2);
-            dft4x2_fused_v<1>(bb + 0, bb + 4, g0, g0s, g1, g1s);
-            dft4x2_fused_v<1>(bb + 8, bb + 12, g2, g2s, g3, g3s);
+        // natural order of one column's DFT-16 outputs
+        auto col16_order = [&](f2 *bb) {
             f2 tt[16];
             static_for<0, 16>([&](auto e) {
                 constexpr int m = decltype(e)::value;  // m = 4 k1 + k2 holds Z[col + 32 (k1 + 4 k2)]
@@ -872,15 +498,22 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
             });
         };
         if constexpr (OVL) {
+            // one column's DFT-16 with its ten twiddles given
+            auto col16 = [&](f2 *bb, f2 v, f2 v2, f2 g0, f2 g0s, f2 g1, f2 g1s, f2 g2, f2 g2s, f2 g3,
+                             f2 g3s) {
+                dft4x2_fused_v<4>(bb + 0, bb + 1, v, v2, v, v2);
+                dft4x2_fused_v<4>(bb + 2, bb + 3, v, v2, v, v2);
+                dft4x2_fused_v<1>(bb + 0, bb + 4, g0, g0s, g1, g1s);
+                dft4x2_fused_v<1>(bb + 8, bb + 12, g2, g2s, g3, g3s);
+                col16_order(bb);
+            };
             // the previous group's round-1 reads stay ahead of these writes
             // (LDS executes one wave's operations in order)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int c = 0; c < 16; ++c) win[t * kQRow + c] = a[c];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
 #pragma unroll
             for (int n2 = 0; n2 < 16; ++n2) b[n2] = win[n2 * kQRow + t];
             f2 v, v2, g0, g0s, g1, g1s, g2, g2s, g3, g3s;
@@ -893,9 +526,7 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int c = 0; c < 16; ++c) win[t * kQRow + c] = a[16 + c];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
 #pragma unroll
             for (int n2 = 0; n2 < 16; ++n2) b[16 + n2] = win[n2 * kQRow + k1b - 16];
             col16(b, v, v2, g0, g0s, g1, g1s, g2, g2s, g3, g3s);
@@ -905,28 +536,24 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
             twp(1, 6, g2, g2s);
             twp(1, 8, g3, g3s);
             col16(b + 16, v, v2, g0, g0s, g1, g1s, g2, g2s, g3, g3s);
-        }
+        } else {
 #pragma unroll
-        for (int r = 0; r < (OVL ? 0 : 2); ++r) {
+            for (int r = 0; r < 2; ++r) {
 #pragma unroll
-            for (int c = 0; c < 16; ++c) win[t * kQRow + c] = a[16 * r + c];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (PF == 1 && r == 0) load_group(g + stride < n_groups ? g + stride : g);
-            const int col = r == 0 ? t : k1b - 16;
+                for (int c = 0; c < 16; ++c) win[t * kQRow + c] = a[16 * r + c];
+                wave_sync();
+                const int col = r == 0 ? t : k1b - 16;
 #pragma unroll
-            for (int n2 = 0; n2 < 16; ++n2) b[16 * r + n2] = win[n2 * kQRow + col];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        // 3. per column: DFT-16 over t of A_t[col] W512^{t col}, twiddles fused
+                for (int n2 = 0; n2 < 16; ++n2) b[16 * r + n2] = win[n2 * kQRow + col];
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+            // 3. per column: DFT-16 over t of A_t[col] W512^{t col}, twiddles fused
 #pragma unroll
-        for (int sl = 0; sl < (OVL ? 0 : 2); ++sl) {
-            f2 *bb = b + 16 * sl;
-            f2 v, v2;
-            twp(sl, 0, v, v2);
-            if constexpr (FUSED >= 4) {
+            for (int sl = 0; sl < 2; ++sl) {
+                f2 *bb = b + 16 * sl;
+                f2 v, v2;
+                twp(sl, 0, v, v2);
                 dft4x2_fused_v<4>(bb + 0, bb + 1, v, v2, v, v2);
                 dft4x2_fused_v<4>(bb + 2, bb + 3, v, v2, v, v2);
                 f2 g0, g0s, g1, g1s, g2, g2s, g3, g3s;
@@ -936,31 +563,8 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
                 twp(sl, 8, g3, g3s);
                 dft4x2_fused_v<1>(bb + 0, bb + 4, g0, g0s, g1, g1s);
                 dft4x2_fused_v<1>(bb + 8, bb + 12, g2, g2s, g3, g3s);
-            } else {
-            static_for<0, 4>([&](auto c) {
-                constexpr int i2 = decltype(c)::value;
-                if constexpr (FUSED >= 1)
-                    dft4_fused_v<4>(bb + i2, v, v2);
-                else
-                    dft4_geo_v<4>(bb + i2, v, v2);   // column i2's X[k1] at slot i2 + 4 k1
-            });
-            static_for<0, 4>([&](auto d) {
-                constexpr int k1 = decltype(d)::value;
-                if constexpr (FUSED >= 1)
-                    dft4_fused_v<1>(bb + 4 * k1, twv(sl, 2 + 2 * k1), twv(sl, 3 + 2 * k1));
-                else
-                    dft4_geo_v<1>(bb + 4 * k1, twv(sl, 2 + 2 * k1), twv(sl, 3 + 2 * k1));
-            });
+                col16_order(bb);
             }
-            f2 tt[16];
-            static_for<0, 16>([&](auto e) {
-                constexpr int m = decltype(e)::value;  // m = 4 k1 + k2 holds Z[col + 32 (k1 + 4 k2)]
-                tt[(m / 4) + 4 * (m % 4)] = bb[m];
-            });
-            static_for<0, 16>([&](auto e) {
-                constexpr int m = decltype(e)::value;
-                bb[m] = tt[m];
-            });
         }
         // b[k2] = Z[t + 32 k2], b[16 + k2] = Z[k1b + 32 k2] (unscaled)
 
@@ -1010,38 +614,8 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
                 Q0 = sel_l0(b[16 - j0], Q0);
                 Q1 = sel_l0(b[16 - j1], Q1);
             }
-            f2 w0, w1;
-            if constexpr (RD >= 2) {
-                const f4 x = *reinterpret_cast<const f4 *>(&tw3[tw3_at(j0, t)]);
-                w0 = (f2){x.x, x.y};
-                w1 = (f2){x.z, x.w};
-            } else if constexpr (TW3R) {
-                // W1024^kP / 2 = base x W32^j (j0 = 0 and j0 + 1 = 8 ... cheap cases)
-                const f2 b0 = j0 < 8 ? tb_lo : tb_hi, b1 = j1 < 8 ? tb_lo : tb_hi;
-                if constexpr (j0 == 0) {
-                    w0 = b0;
-                    w1 = cmulk(b1, w32c<j1>());
-                } else if constexpr (j0 == 8) {
-                    w0 = mj(b0);
-                    w1 = cmulk(b1, w32c<j1>());
-                } else {
-                    cmulk2(w0, b0, w32c<j0>(), w1, b1, w32c<j1>());
-                }
-            } else {
-                w0 = tw3[tw3_at(j0, t)];
-                w1 = tw3[tw3_at(j1, t)];
-            }
-            if constexpr (FUSED >= 2) {
-                postpair2(pw0, P0, Q0, w0, pw1, P1, Q1, w1);
-            } else {
-                const f2 S0 = pp_s(P0, Q0), S1 = pp_s(P1, Q1);
-                const f2 D0 = pp_d(P0, Q0), D1 = pp_d(P1, Q1);
-                f2 T0, T1;
-                cmul2(T0, D0, w0, T1, D1, w1);
-                const f2 re0 = pp_re_h(S0, T0), re1 = pp_re_h(S1, T1);
-                const f2 im0 = pp_im_h(S0, T0), im1 = pp_im_h(S1, T1);
-                pwr2(pw0, re0, im0, pw1, re1, im1);
-            }
+            const f2 w0 = tw3[tw3_at(j0, t)], w1 = tw3[tw3_at(j1, t)];
+            postpair2(pw0, P0, Q0, w0, pw1, P1, Q1, w1);
             }
             if constexpr (SPEC && SPL) {
                 const int a = j0 < 8 ? spl_a_lo : spl_a_hi, m = j0 < 8 ? spl_m_lo : spl_m_hi;
@@ -1064,7 +638,7 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
         asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(px) : "v"(b[0]));
         px = px * px;
         const bool live = w < p.n_windows;
-        float pk = -1.f, pk2 = -1.f;  // the best (and runner-up) tone power this lane holds
+        float pk = -1.f;  // lanes t < K: tone t's power
         int arg = t < p.k ? t : kMaxTones;  // kMaxTones: this lane holds no tone
         if constexpr (SPEC) {
             if (l0) {
@@ -1076,17 +650,16 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
                     pq[513] = px.y;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // 5. tone pick (as fft1024_quad_kernel step 4)
+            wave_sync();
+            // 5. tone pick from the slab
             if (t < p.k) pk = SPL ? pw[rowb + mybin] : pq[myslot];
             // SPL: the fenced lane id again, so the store address is formed
             // here rather than held across the loop
             if (live && t < p.k && p.mag) p.mag[w * p.k + (SPL ? tt : t)] = pk;
-        } else if constexpr (PICK == 1 || PICK == 2) {
-            // 5. tone pick, gathered: tone i's power (register slot and lane
-            //    from its uniform slot, as below) is read across the row with
+        } else {
+            // 5. tone pick, gathered: tone i's power sits in lane
+            //    (slot >> 1) & 15 of each window row at pv[slot >> 5 | half]
+            //    (p.slot: a uniform index) and is read across the row with
             //    one ds_bpermute into lane t = i, so lanes t < K end holding
             //    tone t's power, as the slab pick of the spectrum path leaves
             //    them: one coalesced magnitude store and the same row argmax
@@ -1102,34 +675,12 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
             }
             pk = mine;
             if (live && t < p.k && p.mag) p.mag[w * p.k + t] = pk;
-        } else {
-            // 5. tone pick from registers: tone i's power sits in lane
-            //    (slot >> 1) & 15 of each window row at pv[slot >> 5 | half]
-            //    (uniform index); each lane keeps the best tone it owns (first
-            //    index on ties), then the row argmax below
-            arg = kMaxTones;
-#pragma unroll
-            for (int i = 0; i < kMaxTones; ++i) {
-                if (i >= p.k) break;
-                const int f = p.slot[i];
-                const bool own = f >= 512 ? l0 : t == ((f >> 1) & 15);
-                const float val = f >= 512 ? (f == 512 ? px.x : px.y) : pv[((f >> 5) << 1) | (f & 1)];
-                if (own && live && p.mag) p.mag[w * p.k + i] = val;
-                if (own && val > pk) {
-                    pk2 = pk;
-                    pk = val;
-                    arg = i;
-                } else if (own && val > pk2) {
-                    pk2 = val;
-                }
-            }
         }
         // row argmax, ties to the lowest tone: the two DPP max passes of
         // window_sum.h (powers >= 0, so their bits order as unsigned)
         const bool owns = arg < kMaxTones;
         float mx;
         arg = (int)ws_argmax_m<false>(__float_as_uint(pk), owns, arg, 0u, false, 0, mx);
-        // decision rescue: a runner-up within the threshold
         // decision rescue, two stages: the int16 worst case,
         // then (only waves with a stage-1 flag) the window's energy by
         // Parseval, E = 2 x the sum of its 513 bin powers >= n sum x^2 (the
@@ -1169,18 +720,10 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
             }
             return 2.f * row_sum16(e);
         };
-        const bool amb = p.k >= 2 && ws_amb_two_stage(mx, pk, owns, pk2, pk2 >= 0.f, live, p.amb_tq,
+        const bool amb = p.k >= 2 && ws_amb_two_stage(mx, pk, owns, 0.f, false, live, p.amb_tq,
                                                       p.amb_floor, p.amb_t2e, efn);
         if (live && t == 0) p.sym[w] = (uint8_t)(arg | (amb ? kSymAmbiguous : 0));
         if constexpr (SPEC && SPL) {
-            if constexpr (PF == 2) {
-                // the next group's loads go out ahead of this group's spectrum
-                // stores: vmcnt retires in order, so waiting for those loads
-                // no longer waits for these stores to be acknowledged
-                __builtin_amdgcn_sched_barrier(0);
-                load_group(g + stride < n_groups ? g + stride : g);
-                __builtin_amdgcn_sched_barrier(0);
-            }
             if (p.spec) {
                 // the group's live windows: floats [0, L) of the slab = the
                 // output run from window 4 g (16-byte aligned: 4 g x 513 x 4 B)
@@ -1192,10 +735,7 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
                 for (int i = 0; i < 9; ++i) {
                     const int f = 64 * i + lane;
                     if (4 * f + 4 <= L) {
-                        if constexpr (SPL == 2)
-                            __builtin_nontemporal_store(src4[f], reinterpret_cast<f4 *>(dst + 4 * f));
-                        else
-                            *reinterpret_cast<f4 *>(dst + 4 * f) = src4[f];
+                        __builtin_nontemporal_store(src4[f], reinterpret_cast<f4 *>(dst + 4 * f));
                     } else if (4 * f < L) {
                         for (int e = 4 * f; e < L; ++e) dst[e] = pw[e];
                     }
@@ -1217,11 +757,7 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
     //    the bytes were written by this wave or its block) and every
     //    flagged window is decided again in double, one window per wave at a
     //    time through the wave's slab.
-    //    RSC 1: each wave its own groups' windows.
-    //    RSC 2: the block's flagged windows dealt round-robin to its waves, 64
-    //    groups per wave at a time; every wave reads a chunk's bytes before
-    //    any rescue rewrites them (the barrier), so all deal the same list.
-    //    RSC 0: no rescue code (probe A/B).
+    //    Each wave takes its own groups' windows.
     auto rescue_one = [&](long long ww, lds_double *xs) {
         rescue_fft_window(p.pcm + ww * p.hop, xs, reinterpret_cast<const double2 *>(p.rtw), p.bins, p.k,
                           p.sym + ww, p.mag ? p.mag + ww * p.k : nullptr, p.spec ? p.spec + ww * 513 : nullptr);
@@ -1237,131 +773,79 @@ __device__ __attribute__((always_inline)) inline void fft1024_quad_body(const Ff
         }
         return f;
     };
-    if constexpr (RSC == 1) {
-        if (p.rescue) {
-            // this wave's symbol stores have landed (in this XCD's L2, where
-            // the plain loads below find them) and are ordered before the loads
-            __builtin_amdgcn_s_waitcnt(0);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            lds_double *xs = (lds_double *)(slab[wave]);
-            bool rescan = true;  // the double FFTs' scan (below) has work
-            if (p.t2e64 > 0.0 && !p.spec) {
-                // first pass over each flagged group's windows, one per row
-                // (rescue_fft_seg), where it is cheaper than their double
-                // FFTs: it costs ~k x 200 double operations per lane for the
-                // whole group, a double FFT ~800 per flagged window (at k = 8
-                // and ~1.8 flagged windows per group both cost the same,
-                // profiles/round4/r4l/). It clears the flag of every window
-                // it decides; the loop below then finds only what it left.
-                // (A separate loop: folded into the one below it made that
-                // loop's double FFTs 30 % slower, profiles/round4/r4n/.)
-                // (a wave that finds no flagged window here, nearly all of
-                // them, skips the second scan of its symbol bytes)
-                bool any = false;
-                for (long long gb = g_first; gb < n_groups; gb += 64 * stride) {
-                    const unsigned f = flags4(gb + (long long)lane * stride);
-                    unsigned long long m = __ballot(f != 0);
-                    any = any || m != 0;
-                    while (m) {
-                        const int src = __builtin_ctzll(m);
-                        m &= m - 1;
-                        const unsigned fs = (unsigned)__builtin_amdgcn_readlane((int)f, src);
-                        if (p.k > 4 * __builtin_popcount(fs)) continue;
-                        const long long gs = gb + (long long)src * stride;
-                        const int row = lane >> 4;
-                        const long long ww = 4 * gs + row;
-                        const bool amb = (fs >> row) & 1u;
-                        (void)rescue_fft_seg(p.pcm + (amb ? ww : 0) * p.hop, p.rot64, p.t2e64, p.k, lane & 15,
-                                             amb, p.sym + ww, p.mag ? p.mag + ww * p.k : nullptr, p.fold64 != 0);
-                    }
-                }
-                __builtin_amdgcn_s_waitcnt(0);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-                rescan = any;
-            }
-            for (long long gb = g_first; rescan && gb < n_groups; gb += 64 * stride) {
+    if (p.rescue) {
+        // this wave's symbol stores have landed (in this XCD's L2, where
+        // the plain loads below find them) and are ordered before the loads
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        lds_double *xs = (lds_double *)(slab[wave]);
+        bool rescan = true;  // the double FFTs' scan (below) has work
+        if (p.t2e64 > 0.0 && !p.spec) {
+            // first pass over each flagged group's windows, one per row
+            // (rescue_fft_seg), where it is cheaper than their double
+            // FFTs: it costs ~k x 200 double operations per lane for the
+            // whole group, a double FFT ~800 per flagged window (at k = 8
+            // and ~1.8 flagged windows per group both cost the same,
+            // profiles/round4/r4l/). It clears the flag of every window
+            // it decides; the loop below then finds only what it left.
+            // (A separate loop: folded into the one below it made that
+            // loop's double FFTs 30 % slower, profiles/round4/r4n/.)
+            // (a wave that finds no flagged window here, nearly all of
+            // them, skips the second scan of its symbol bytes)
+            bool any = false;
+            for (long long gb = g_first; gb < n_groups; gb += 64 * stride) {
                 const unsigned f = flags4(gb + (long long)lane * stride);
                 unsigned long long m = __ballot(f != 0);
+                any = any || m != 0;
                 while (m) {
                     const int src = __builtin_ctzll(m);
                     m &= m - 1;
                     const unsigned fs = (unsigned)__builtin_amdgcn_readlane((int)f, src);
+                    if (p.k > 4 * __builtin_popcount(fs)) continue;
                     const long long gs = gb + (long long)src * stride;
-                    for (int q0 = 0; q0 < 4; ++q0)
-                        if ((fs >> q0) & 1u) rescue_one(4 * gs + q0, xs);
+                    const int row = lane >> 4;
+                    const long long ww = 4 * gs + row;
+                    const bool amb = (fs >> row) & 1u;
+                    (void)rescue_fft_seg(p.pcm + (amb ? ww : 0) * p.hop, p.rot64, p.t2e64, p.k, lane & 15,
+                                         amb, p.sym + ww, p.mag ? p.mag + ww * p.k : nullptr, p.fold64 != 0);
                 }
             }
+            __builtin_amdgcn_s_waitcnt(0);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            rescan = any;
         }
-    } else if constexpr (RSC == 2) {
-        if (p.rescue) {
-            __builtin_amdgcn_s_waitcnt(0);  // this wave's symbol stores have landed
-            __syncthreads();                // ... and every wave's of the block (a workgroup fence)
-            lds_double *xs = (lds_double *)(slab[wave]);
-            int seen = 0;                   // flagged windows dealt so far (wave-uniform)
-            for (long long gb0 = g_first - wave; gb0 < n_groups; gb0 += 64 * stride) {
-                unsigned f[WPB];
-#pragma unroll
-                for (int wv = 0; wv < WPB; ++wv) f[wv] = flags4(gb0 + wv + (long long)lane * stride);
-                __syncthreads();
-#pragma unroll
-                for (int wv = 0; wv < WPB; ++wv) {
-                    unsigned long long m = __ballot(f[wv] != 0);
-                    while (m) {
-                        const int src = __builtin_ctzll(m);
-                        m &= m - 1;
-                        const unsigned fs = (unsigned)__builtin_amdgcn_readlane((int)f[wv], src);
-                        const long long gs = gb0 + wv + (long long)src * stride;
-                        for (int q0 = 0; q0 < 4; ++q0)
-                            if ((fs >> q0) & 1u) {
-                                if (seen++ % WPB != wave) continue;
-                                rescue_one(4 * gs + q0, xs);
-                            }
-                    }
-                }
+        for (long long gb = g_first; rescan && gb < n_groups; gb += 64 * stride) {
+            const unsigned f = flags4(gb + (long long)lane * stride);
+            unsigned long long m = __ballot(f != 0);
+            while (m) {
+                const int src = __builtin_ctzll(m);
+                m &= m - 1;
+                const unsigned fs = (unsigned)__builtin_amdgcn_readlane((int)f, src);
+                const long long gs = gb + (long long)src * stride;
+                for (int q0 = 0; q0 < 4; ++q0)
+                    if ((fs >> q0) & 1u) rescue_one(4 * gs + q0, xs);
             }
         }
     }
 }
 
-template <int WPB = 4, int MINW = 4, int PF = 0, bool SPEC = true, bool FMT = false, int AUX = 2,
-          int FUSED = 0, int SPL = 0, int OVL = 0, int TW3R = 0, int RSC = 1, int PICK = 0>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MINW > 0 ? MINW : 1)))
+// (The body stays a function of its own, taking the parameter block by
+// reference: written straight into the kernel, the compiler orders its scalar
+// loads differently.)
+template <bool SPEC, int AUX, int SPL = 0, int OVL = 0, int PICK = 0>
+__global__ __launch_bounds__(64 * 4) __attribute__((amdgpu_waves_per_eu(4)))
 void fft1024_quad_kernel(FftParams p)
 {
-    fft1024_quad_body<WPB, MINW, PF, SPEC, FMT, AUX, FUSED, 0, SPL, OVL, TW3R, RSC, PICK>(p);
-}
-
-// (a device-code attribute: the host pass of hipcc does not know the feature)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FSKD_NO_LDS_PAIRING __attribute__((target("no-load-store-opt")))
-#else
-#define FSKD_NO_LDS_PAIRING
-#endif
-// The same kernel without the backend's LDS-access pairing: the transpose's
-// column reads and the twiddle-table reads stay ds_read_b64 (2 LDS cycles per
-// wave, 256 B/clk) instead of being merged into ds_read2_b64 (8 cycles for
-// twice the bytes, 128 B/clk; MI355X_MICROARCH.md §LDS). RD 2: also the
-// twiddle tables lane-major, one ds_read_b128 (4 cycles) per twiddle pair.
-template <int WPB = 4, int MINW = 4, int PF = 0, bool SPEC = true, bool FMT = false, int AUX = 2,
-          int FUSED = 0, int RD = 1>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MINW > 0 ? MINW : 1)))
-FSKD_NO_LDS_PAIRING void fft1024_quad_kernel_r64(FftParams p)
-{
-    fft1024_quad_body<WPB, MINW, PF, SPEC, FMT, AUX, FUSED, RD>(p);
+    fft1024_quad_body<SPEC, AUX, SPL, OVL, PICK>(p);
 }
 
 // Persistent grid: as many blocks as fit the chip, each wave strides over
 // groups of 4 windows (the LDS twiddle tables are built once per block).
-template <int WPB, int MINW, int PF, bool SPEC, bool FMT = false, int AUX = 2, int FUSED = 0, int RD = 0,
-          int SPL = 0, int OVL = 0, int TW3R = 0, int RSC = 1, int PICK = 0>
+template <bool SPEC, int AUX, int SPL = 0, int OVL = 0, int PICK = 0>
 hipError_t launch_fft_quad_t(const FftParams &p, hipStream_t s)
 {
-    void (*kern)(FftParams);
-    static_assert(!(RD > 0 && (SPL > 0 || OVL > 0 || TW3R > 0)), "SPL / OVL / TW3R: fft1024_quad_kernel only");
-    if constexpr (RD > 0)
-        kern = fft1024_quad_kernel_r64<WPB, MINW, PF, SPEC, FMT, AUX, FUSED, RD>;
-    else
-        kern = fft1024_quad_kernel<WPB, MINW, PF, SPEC, FMT, AUX, FUSED, SPL, OVL, TW3R, RSC, PICK>;
+    constexpr int WPB = 4;
+    void (*kern)(FftParams) = fft1024_quad_kernel<SPEC, AUX, SPL, OVL, PICK>;
     int dev = 0, cus = 256, per_cu = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1375,16 +859,15 @@ hipError_t launch_fft_quad_t(const FftParams &p, hipStream_t s)
     return hipGetLastError();
 }
 
-// Shipped: 4-wave blocks, 4 waves/SIMD, loads at the top of each group, the
-// register tone pick unless the full spectrum is asked for
+// What ships: 4-wave blocks, 4 waves/SIMD, loads at the top of each group
 // (scripts/fft_probe.hip, profiles/round2/fft/). Load policy: windows that
 // overlap (hop < n) are read by up to n / hop groups, so their loads keep the
 // lines in L2 (plain cached loads, AUX 0: FETCH 1.06x the stream at hop 256,
 // 3-6 % faster; sc0 measured the same or slower); disjoint windows stream
 // through with nt (AUX 2; nt at hop 256 re-fetches 1.55x the stream).
-// FUSED 4: the DFT-4 stages (stage 2: two interleaved per block), the
-// DFT-32's trivial pieces and the post-pass pairs as single asm blocks
-// (-3 to -4.5 % at hop 256, -2 to -4 % at hop 1024 against separate blocks;
+// The DFT-4 stages (stage 2: two interleaved per block), the DFT-32's trivial
+// pieces and the post-pass pairs are single asm blocks (probe FUSED 4:
+// -3 to -4.5 % at hop 256, -2 to -4 % at hop 1024 against separate blocks;
 // scripts/fft_probe.hip, profiles/round2/fft_fused/).
 // The full-spectrum store (p.spec) goes through the linear slab with
 // non-temporal 16-byte stores (SPL 2) when the output is 16-byte aligned,
@@ -1398,21 +881,21 @@ hipError_t launch_fft_quad_t(const FftParams &p, hipStream_t s)
 // (profiles/round3/r3s/); round 5: only the post-pass blocks holding a tone
 // bin (PICK 2, -13 %), with round 1 of the transpose overlapping column 0's
 // DFT-16 (OVL: within +-0.5 % on the full post-pass, -2.7 % once the VALU
-// stream had shrunk; the twiddles from registers, TW3R, another -1 % but
-// other bits than the table's, not taken; profiles/round5/r5zp/).
+// stream had shrunk; profiles/round5/r5zp/).
+//                                          <SPEC, AUX, SPL, OVL, PICK>
 hipError_t launch_fft_quad(const FftParams &p, hipStream_t s)
 {
     const bool lin = p.spec && ((uintptr_t)p.spec & 15) == 0;
     if (p.hop < 1024) {
-        if (lin) return launch_fft_quad_t<4, 4, 0, true, false, 0, 4, 0, 2>(p, s);
-        if (p.spec) return launch_fft_quad_t<4, 4, 0, true, false, 0, 4>(p, s);
-        return p.pmask == 0xFFu ? launch_fft_quad_t<4, 4, 0, false, false, 0, 4, 0, 0, 0, 0, 1, 1>(p, s)
-                                : launch_fft_quad_t<4, 4, 0, false, false, 0, 4, 0, 0, 1, 0, 1, 2>(p, s);
+        if (lin) return launch_fft_quad_t<true, 0, 2>(p, s);
+        if (p.spec) return launch_fft_quad_t<true, 0>(p, s);
+        return p.pmask == 0xFFu ? launch_fft_quad_t<false, 0, 0, 0, 1>(p, s)
+                                : launch_fft_quad_t<false, 0, 0, 1, 2>(p, s);
     }
-    if (lin) return launch_fft_quad_t<4, 4, 0, true, false, 2, 4, 0, 2>(p, s);
-    if (p.spec) return launch_fft_quad_t<4, 4, 0, true, false, 2, 4>(p, s);
-    return p.pmask == 0xFFu ? launch_fft_quad_t<4, 4, 0, false, false, 2, 4, 0, 0, 0, 0, 1, 1>(p, s)
-                            : launch_fft_quad_t<4, 4, 0, false, false, 2, 4, 0, 0, 1, 0, 1, 2>(p, s);
+    if (lin) return launch_fft_quad_t<true, 2, 2>(p, s);
+    if (p.spec) return launch_fft_quad_t<true, 2>(p, s);
+    return p.pmask == 0xFFu ? launch_fft_quad_t<false, 2, 0, 0, 1>(p, s)
+                            : launch_fft_quad_t<false, 2, 0, 1, 2>(p, s);
 }
 
 int fft_quad_slot(int bin) { return quad_slot(bin); }

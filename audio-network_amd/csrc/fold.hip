@@ -22,26 +22,6 @@
 
 namespace fskd {
 
-typedef unsigned int u32x4f __attribute__((ext_vector_type(4)));
-typedef float f32x2f __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-__device__ __forceinline__ float dppf_(float v)
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ float group_sum_f(float v, int log2g)
-{
-    if (log2g > 0) v += dppf_<0xB1>(v);
-    if (log2g > 1) v += dppf_<0x4E>(v);
-    if (log2g > 2) v += dppf_<0x141>(v);
-    if (log2g > 3) v += dppf_<0x140>(v);
-    if (log2g > 4) v += __shfl_xor(v, 16);
-    if (log2g > 5) v += __shfl_xor(v, 32);
-    return v;
-}
-
 // The energy stage 2 compares against: the folded window's, E_f = sum xf^2.
 // Where it is 0 (every folded sum zero, so every fp32 tone power is too) the
 // row is a candidate only if the window itself is not digital silence:
@@ -87,10 +67,10 @@ __device__ __forceinline__ bool fold_decide(const int (&acc)[8], const float4 *r
 #pragma unroll
     for (int q = 0; q < 8; ++q) xf[q] = (float)acc[q];
     auto efn = [&]() {
-        f32x2f a = {0.f, 0.f};
+        f2 a = {0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < 8; q += 2)
-            a = __builtin_elementwise_fma(f32x2f{xf[q], xf[q + 1]}, f32x2f{xf[q], xf[q + 1]}, a);
+            a = __builtin_elementwise_fma(f2{xf[q], xf[q + 1]}, f2{xf[q], xf[q + 1]}, a);
         return fold_energy(row_sum16(a.x + a.y), live, p.amb_d, rawfn);
     };
     const AmbTest at{p.amb_tq, p.amb_floor, p.amb_t2e, defer};
@@ -99,25 +79,25 @@ __device__ __forceinline__ bool fold_decide(const int (&acc)[8], const float4 *r
         float y[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q)  // lanes < 8: E + O = Z0; lanes >= 8: E - O = Z8
-            y[q] = fmaf(sg, xf[q], dppf_<0x128>(xf[q]));
+            y[q] = fmaf(sg, xf[q], dpp_f<0x128>(xf[q]));
         float xr[4], xi[4];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {  // tone pairs in packed fp32 (2 ops per pair-sample)
-            const f32x2f c2 = f32x2f{c16[2 * h], c16[2 * h + 1]};
-            f32x2f a1 = f32x2f{0.f, 0.f}, a2 = f32x2f{0.f, 0.f};
+            const f2 c2 = f2{c16[2 * h], c16[2 * h + 1]};
+            f2 a1 = f2{0.f, 0.f}, a2 = f2{0.f, 0.f};
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const f32x2f a = __builtin_elementwise_fma(c2, a1, f32x2f{y[q], y[q]} - a2);
+                const f2 a = __builtin_elementwise_fma(c2, a1, f2{y[q], y[q]} - a2);
                 a2 = a1;
                 a1 = a;
             }
             // rotation as packed (re, im) pairs: X = (A s1) - (B s2), 2 ops per tone
-            const f32x2f X0 = __builtin_elementwise_fma(
-                f32x2f{-r[2 * h].z, -r[2 * h].w}, f32x2f{a2.x, a2.x},
-                f32x2f{r[2 * h].x, r[2 * h].y} * f32x2f{a1.x, a1.x});
-            const f32x2f X1 = __builtin_elementwise_fma(
-                f32x2f{-r[2 * h + 1].z, -r[2 * h + 1].w}, f32x2f{a2.y, a2.y},
-                f32x2f{r[2 * h + 1].x, r[2 * h + 1].y} * f32x2f{a1.y, a1.y});
+            const f2 X0 = __builtin_elementwise_fma(
+                f2{-r[2 * h].z, -r[2 * h].w}, f2{a2.x, a2.x},
+                f2{r[2 * h].x, r[2 * h].y} * f2{a1.x, a1.x});
+            const f2 X1 = __builtin_elementwise_fma(
+                f2{-r[2 * h + 1].z, -r[2 * h + 1].w}, f2{a2.y, a2.y},
+                f2{r[2 * h + 1].x, r[2 * h + 1].y} * f2{a1.y, a1.y});
             xr[2 * h] = X0.x;
             xi[2 * h] = X0.y;
             xr[2 * h + 1] = X1.x;
@@ -129,11 +109,11 @@ __device__ __forceinline__ bool fold_decide(const int (&acc)[8], const float4 *r
         constexpr int HP = K / 2;  // packed tone pairs; an odd last tone runs scalar
 #pragma unroll
         for (int h = 0; h < HP; ++h) {
-            const f32x2f c2 = f32x2f{p.coef[2 * h], p.coef[2 * h + 1]};
-            f32x2f a1 = f32x2f{0.f, 0.f}, a2 = f32x2f{0.f, 0.f};
+            const f2 c2 = f2{p.coef[2 * h], p.coef[2 * h + 1]};
+            f2 a1 = f2{0.f, 0.f}, a2 = f2{0.f, 0.f};
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                const f32x2f a = __builtin_elementwise_fma(c2, a1, f32x2f{xf[q], xf[q]} - a2);
+                const f2 a = __builtin_elementwise_fma(c2, a1, f2{xf[q], xf[q]} - a2);
                 a2 = a1;
                 a1 = a;
             }
@@ -159,19 +139,24 @@ __device__ __forceinline__ bool fold_decide(const int (&acc)[8], const float4 *r
     }
 }
 
-//   ROTLDS: keep the per-lane rotation constants in a block LDS table instead
-//           of 4K VGPRs (raises occupancy for large K).
-//   NTS: non-temporal output stores.
-//   LAUX: (probe) the input loads' cache-policy bits; -1: nt when NT, else plain.
-//   WS: window_sum.h epilogue (reduce-scatter, packed-key argmax) at n = 1024.
-//   PK: (with WS) tone pairs in packed fp32, one v_pk_add_f32 + v_pk_fma_f32
-//       per pair per folded sample instead of 2 scalar instructions per tone.
-//   LDST: (n = 1024) load the tile as the plain bank does, 1 KiB contiguous per
-//       wave instruction, and regroup it through an 8 KiB wave-private LDS
-//       slice (linear: chunk q at 16 q, conflict-free for both the 64-chunk
-//       writes and the j + 16 m reads), instead of the direct per-lane
-//       layout whose instructions each touch four 256-byte pieces.
-//   F16: (K = 8, n = 1024, LDST) fold by 16. Tones on multiples of 16 bins
+// The tile kernel: 2-wave blocks (kPlainWPB), one tile of 64 >> log2g windows
+// per wave, the rotation constants in 4K VGPRs, plain output stores.
+// LOG2G >= 0: lane-group size fixed at compile time (4 <=> n = 1024);
+// LOG2G == -1: taken from p.log2g at run time.
+//   n = 1024 (LOG2G == 4): the tile is loaded as the plain bank does, 1 KiB
+//       contiguous per wave instruction, and regrouped through an 8 KiB
+//       wave-private LDS slice (linear: chunk q at 16 q, conflict-free for
+//       both the 64-chunk writes and the j + 16 m reads), instead of the
+//       direct per-lane layout whose instructions each touch four 256-byte
+//       pieces; the decision is fold_decide (packed tone pairs, window_sum.h
+//       epilogue: reduce-scatter, packed-key argmax) and flagged rows are
+//       rescued in the kernel from the slice. Any other n: the direct per-lane
+//       loads, scalar chains and the all-reduce epilogue.
+//   NT: non-temporal input loads (hop = n: each byte is read once).
+//   MST / LAUX: (scripts/mag_probe.hip only) the magnitude store policy of
+//       window_sum.h mag_store, and the input loads' cache-policy bits;
+//       -1: the shipped ones (kMagStore<K>; nt when NT, else plain).
+//   F16: (K = 8, n = 1024) fold by 16. Tones on multiples of 16 bins
 //       read Z0[r] = sum_{m<16} x[r + 64 m], tones on odd multiples of 8 read
 //       Z8[r] = sum (-1)^m x[r + 64 m] (W^{64 b} = +1 / -1). Lane j < 8 of a
 //       window holds the even-m half E of folded positions 8(j & 7) .. +7,
@@ -181,11 +166,23 @@ __device__ __forceinline__ bool fold_decide(const int (&acc)[8], const float4 *r
 //       run slots 0-3, lanes >= 8 slots 4-7: half the recurrences and
 //       rotations per lane, and the first reduce-scatter stage is already done
 //       (window_sum_decide_split8; perm maps slots back to the caller's tones).
-template <int K, int LOG2G, bool NT = true, int WPB = 4, bool ROTLDS = false, bool NTS = false,
-          bool WS = false, bool PK = false, bool LDST = false, bool F16 = false, int MST = -1,
-          int LAUX = -1>
-__global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
+// Variants the probes tried and did not ship; their source is in git history
+// at f48c2d8:
+//   ROTLDS: the per-lane rotation constants in a block LDS table instead of
+//       4K VGPRs (raises occupancy for large K).
+//   NTS: non-temporal output stores.
+//   WS / LDST off at n = 1024: the all-reduce epilogue (K = 8: 352 -> 347 us,
+//       K = 2: 335 -> 329 us with WS) and the direct per-lane loads (K = 8:
+//       345.8 -> 339.9 us, K = 2: 338.5 -> 319.9 us with LDST;
+//       profiles/round1/probe_ldst.log).
+//   PK in the kernel body: (WS without fold_decide) tone pairs in packed fp32
+//       there too; measured the same (`fold WS PK LDST`).
+//   WPB: 4-wave blocks (demod_internal.h kPlainWPB has the numbers).
+template <int K, int LOG2G, bool NT = true, bool F16 = false, int MST = -1, int LAUX = -1>
+__global__ __launch_bounds__(64 * kPlainWPB) void fold_tile_kernel(GoertzelParams p)
 {
+    constexpr int WPB = kPlainWPB;
+    constexpr bool LDST = LOG2G == 4;  // contiguous loads regrouped through LDS
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: tile bases stay in SGPRs (no waterfall loop per buffer load)
     const int log2g = LOG2G >= 0 ? LOG2G : p.log2g;
@@ -196,9 +193,8 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
     const long long wins_per_tile = 64 >> log2g;
     const long long n_tiles = (p.n_windows + wins_per_tile - 1) / wins_per_tile;
 
-    static_assert(!F16 || (K == 8 && LOG2G == 4 && LDST && WS && !ROTLDS), "F16: K = 8, n = 1024");
-    float4 r[ROTLDS ? 1 : K];
-    __shared__ float4 rot_lds[ROTLDS ? K * 64 : 1];
+    static_assert(!F16 || (K == 8 && LOG2G == 4), "F16: K = 8, n = 1024");
+    float4 r[K];
     float c16[4];
     if constexpr (F16) {
         // lane j runs slots 4 * (j >= 8) + s; rotation rows are per slot and lane
@@ -208,16 +204,12 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
             c16[s4] = up ? p.coef[4 + s4] : p.coef[s4];
             r[s4] = p.rot[(s4 + (up ? 4 : 0)) * 16 + (lane & 15)];
         }
-    } else if (ROTLDS) {
-        for (int i = threadIdx.x; i < K * g; i += 64 * WPB) rot_lds[i] = p.rot[i];
-        __syncthreads();
     } else {
 #pragma unroll
         for (int k = 0; k < K; ++k) r[k] = p.rot[k * g + j];
     }
-    static_assert(!LDST || LOG2G == 4, "LDST regrouping is written for n = 1024");
     __shared__ __attribute__((aligned(16))) unsigned char lds_t[LDST ? WPB * 8192 : 16];
-    u32x4f *wl = reinterpret_cast<u32x4f *>(lds_t + (LDST ? wave * 8192 : 0));
+    u32x4 *wl = reinterpret_cast<u32x4 *>(lds_t + (LDST ? wave * 8192 : 0));
     int goff[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
@@ -231,15 +223,9 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
 
     const long long stride = (long long)gridDim.x * WPB;
     // one tile's loads (a buffer resource clamped to the batch's bytes)
-    auto load_tile = [&](long long tt, u32x4f (&v)[8]) {
-        const long long wb = tt * wins_per_tile;
-        long long bytes = ((p.n_windows - wb - 1) * p.hop + n) * 2;
-        if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(p.pcm + wb * p.hop), (short)0, (int)bytes, 0x00020000);
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-            v[m] = __builtin_amdgcn_raw_buffer_load_b128(rs, goff[m], 0, LAUX >= 0 ? LAUX : NT ? 2 : 0);
+    auto load_tile = [&](long long tt, u32x4 (&v)[8]) {
+        tile_load<(LAUX >= 0 ? LAUX : NT ? 2 : 0)>(
+            tile_rsrc(p, tt * wins_per_tile, n), goff, v);
     };
     // PFN (LDST, K <= 2): the next tile's loads are issued as soon as this
     // tile is in LDS, so they are in flight during this tile's arithmetic (as
@@ -249,7 +235,7 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
     // instead of 84 / 5), measured 0.5 % faster at K = 2 (0.3033 vs 0.3048 ms,
     // interleaved; the plain bank 0.2967; profiles/round6/fold_k2_ab.log)
     constexpr bool PFN = LDST && K <= 2 && !F16;
-    u32x4f v[8];
+    u32x4 v[8];
     const long long t_first = tile_block(p.xcd_swizzle) * WPB + wave;
     if (PFN && t_first < n_tiles) load_tile(t_first, v);
     for (long long t = t_first; t < n_tiles; t += stride) {
@@ -265,21 +251,19 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
                 const int16_t *sp = p.pcm + w * p.hop + 8 * j;
                 const bool live = w < p.n_windows;
                 e = seg_energy_serial([&](int m) {
-                    return live ? *reinterpret_cast<const u32x4f *>(sp + 8 * g * m) : u32x4f{0u, 0u, 0u, 0u};
+                    return live ? *reinterpret_cast<const u32x4 *>(sp + 8 * g * m) : u32x4{0u, 0u, 0u, 0u};
                 });
             }
-            return group_sum_f(e, log2g);
+            return group_sum(e, log2g);
         };
         if (!PFN) load_tile(t, v);
         if (LDST) {
 #pragma unroll
             for (int m = 0; m < 8; ++m) wl[64 * m + lane] = v[m];
             if (PFN && t + stride < n_tiles) load_tile(t + stride, v);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
-        u32x4f cur[8];
+        u32x4 cur[8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) cur[m] = LDST ? wl[128 * win_in_tile + 16 * m + j] : v[m];
         if (LDST) {
@@ -299,12 +283,12 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
                 acc[2 * q + 1] += (int)d4[q] >> 16;
             }
         }
-        if constexpr (F16 || (WS && LOG2G == 4 && !PK && !ROTLDS)) {
+        if constexpr (LOG2G == 4) {
             const long long w = wbase + win_in_tile;
             const bool live = w < p.n_windows;
-            // in-kernel decision rescue (LDST: the tile is still in the wave's
-            // LDS slice, window u's chunks at 128 u ..)
-            constexpr bool kInline = LDST && K >= 2;
+            // in-kernel decision rescue (the tile is still in the wave's LDS
+            // slice, window u's chunks at 128 u ..)
+            constexpr bool kInline = K >= 2;
             const bool defer = kInline && p.rescue_inline;
             const bool amb = fold_decide<K, F16, MST>(acc, r, c16, lane, w, live, p, defer, rawfn);
             if constexpr (kInline) {
@@ -317,54 +301,6 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
 #pragma unroll
         for (int q = 0; q < 8; ++q) xf[q] = (float)acc[q];
 
-        if constexpr (WS && LOG2G == 4) {
-            float xr[K], xi[K];
-            float t1[K], t2[K];
-            constexpr int H = PK ? K / 2 : 0;  // packed tone pairs; the rest scalar
-#pragma unroll
-            for (int h = 0; h < H; ++h) {
-                const f32x2f c2 = f32x2f{p.coef[2 * h], p.coef[2 * h + 1]};
-                f32x2f a1 = f32x2f{0.f, 0.f}, a2 = f32x2f{0.f, 0.f};
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const f32x2f a = __builtin_elementwise_fma(c2, a1, f32x2f{xf[q], xf[q]} - a2);
-                    a2 = a1;
-                    a1 = a;
-                }
-                t1[2 * h] = a1.x;
-                t1[2 * h + 1] = a1.y;
-                t2[2 * h] = a2.x;
-                t2[2 * h + 1] = a2.y;
-            }
-#pragma unroll
-            for (int k = 2 * H; k < K; ++k) {
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float a = fmaf(p.coef[k], s1, xf[q] - s2);
-                    s2 = s1;
-                    s1 = a;
-                }
-                t1[k] = s1;
-                t2[k] = s2;
-            }
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const float4 rk = ROTLDS ? rot_lds[k * g + j] : r[ROTLDS ? 0 : k];
-                xr[k] = fmaf(rk.x, t1[k], -(rk.z * t2[k]));
-                xi[k] = fmaf(rk.y, t1[k], -(rk.w * t2[k]));
-            }
-            const long long w = wbase + win_in_tile;
-            auto efn = [&]() {
-                float e = 0.f;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) e = fmaf(xf[q], xf[q], e);
-                return fold_energy(row_sum16(e), w < p.n_windows, p.amb_d, rawfn);
-            };
-            window_sum_decide<K, false, MST>(xr, xi, lane, w, w < p.n_windows, p.sym, p.mag, 0,
-                                             AmbTest{p.amb_tq, p.amb_floor, p.amb_t2e, false}, efn);
-            continue;
-        }
         float P[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -375,11 +311,11 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
                 s2 = s1;
                 s1 = a;
             }
-            const float4 rk = ROTLDS ? rot_lds[k * g + j] : r[ROTLDS ? 0 : k];
+            const float4 rk = r[k];
             float re = fmaf(rk.x, s1, -(rk.z * s2));  // explicit, as fold_decide
             float im = fmaf(rk.y, s1, -(rk.w * s2));
-            re = group_sum_f(re, log2g);
-            im = group_sum_f(im, log2g);
+            re = group_sum(re, log2g);
+            im = group_sum(im, log2g);
             P[k] = fmaf(re, re, im * im);
         }
 
@@ -388,16 +324,19 @@ __global__ __launch_bounds__(64 * WPB) void fold_tile_kernel(GoertzelParams p)
             float e = 0.f;
 #pragma unroll
             for (int q = 0; q < 8; ++q) e = fmaf(xf[q], xf[q], e);
-            return fold_energy(group_sum_f(e, log2g), w < p.n_windows, p.amb_d, rawfn);
+            return fold_energy(group_sum(e, log2g), w < p.n_windows, p.amb_d, rawfn);
         };
         bool amb;
         const int arg = chain_decide<K>(P, w < p.n_windows, p.amb_tq, p.amb_floor, p.amb_t2e, efn, amb);
         if (w < p.n_windows) {
-            if (j == 0) out_store<NTS>(p.sym + w, (uint8_t)(arg | (amb ? kSymAmbiguous : 0)));
+            if (j == 0) {
+                uint8_t *const so = p.sym + w;  // address before value (goertzel.hip)
+                *so = (uint8_t)(arg | (amb ? kSymAmbiguous : 0));
+            }
             if (p.mag) {
 #pragma unroll
                 for (int k = 0; k < K; ++k)
-                    if ((k & (g - 1)) == j) out_store<NTS>(p.mag + w * K + k, P[k]);
+                    if ((k & (g - 1)) == j) p.mag[w * K + k] = P[k];
             }
         }
     }
@@ -478,25 +417,20 @@ __global__ __launch_bounds__(64 * kPlainWPB) void fold_slide_kernel(GoertzelPara
         for (int k = 0; k < K; ++k) r[k] = p.rot[k * 16 + j];
     }
     constexpr int kChunks = kFoldSlideSegs * 8;  // 16-byte chunks per tile
-    __shared__ __attribute__((aligned(16))) u32x4f lds_s[kPlainWPB * kChunks];
-    u32x4f *wl = lds_s + wave * kChunks;
+    __shared__ __attribute__((aligned(16))) u32x4 lds_s[kPlainWPB * kChunks];
+    u32x4 *wl = lds_s + wave * kChunks;
 
     const long long stride = (long long)gridDim.x * kPlainWPB;
     for (long long t = tile_block(p.xcd_swizzle) * kPlainWPB + wave; t < n_tiles; t += stride) {
         const long long wbase = t * wt;
-        long long bytes = ((p.n_windows - wbase - 1) * p.hop + 1024) * 2;
-        if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(p.pcm + wbase * p.hop), (short)0, (int)bytes, 0x00020000);
-        u32x4f v[kChunks / 64];
+        __amdgpu_buffer_rsrc_t rs = tile_rsrc(p, wbase, 1024);
+        u32x4 v[kChunks / 64];
 #pragma unroll
         for (int i = 0; i < kChunks / 64; ++i)  // cached: neighbouring tiles share their edge segments
             v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, (64 * i + lane) * 16, 0, 0);
 #pragma unroll
         for (int i = 0; i < kChunks / 64; ++i) wl[64 * i + lane] = v[i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
 
         int acc[8];
         for (int i = 0; i < R; ++i) {
@@ -506,7 +440,7 @@ __global__ __launch_bounds__(64 * kPlainWPB) void fold_slide_kernel(GoertzelPara
                 for (int q = 0; q < 8; ++q) acc[q] = 0;
 #pragma unroll
                 for (int m2 = 0; m2 < 8; ++m2) {
-                    const u32x4f d = wl[8 * (u * H + 2 * m2 + par) + chunk];
+                    const u32x4 d = wl[8 * (u * H + 2 * m2 + par) + chunk];
                     const uint32_t d4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
                     for (int q = 0; q < 4; ++q) slide_add(acc[2 * q], acc[2 * q + 1], d4[q]);
@@ -522,8 +456,8 @@ __global__ __launch_bounds__(64 * kPlainWPB) void fold_slide_kernel(GoertzelPara
                 for (int m2 = 0; 2 * m2 < H; ++m2) {
                     const int mm = 2 * m2 + pp;
                     if (mm < H) {
-                        const u32x4f o = wl[8 * (base + mm) + chunk];
-                        const u32x4f nw = wl[8 * (base + 16 + mm) + chunk];
+                        const u32x4 o = wl[8 * (base + mm) + chunk];
+                        const u32x4 nw = wl[8 * (base + 16 + mm) + chunk];
                         const uint32_t o4[4] = {o.x, o.y, o.z, o.w};
                         const uint32_t n4[4] = {nw.x, nw.y, nw.z, nw.w};
 #pragma unroll
@@ -545,20 +479,15 @@ __global__ __launch_bounds__(64 * kPlainWPB) void fold_slide_kernel(GoertzelPara
     }
 }
 
+// What ships: n = 1024 its own instantiation (LDS regrouping, fold_decide),
+// fold by 16 for K = 8 plans the host permuted for it (p.f16).
 template <int K, bool NT>
 static const void *fold_kernel_for_t(int log2g, bool f16)
 {
     if constexpr (K == 8)
-        if (log2g == 4 && f16)
-            return reinterpret_cast<const void *>(
-                &fold_tile_kernel<8, 4, NT, kPlainWPB, false, false, true, false, true, true>);
-    // n = 1024: window_sum.h epilogue (K = 8: 352 -> 347 us, K = 2: 335 -> 329 us)
-    // and LDS regrouping of contiguous loads (K = 8: 345.8 -> 339.9 us, K = 2:
-    // 338.5 -> 319.9 us; profiles/round1/probe_ldst.log)
-    if (log2g == 4)
-        return reinterpret_cast<const void *>(
-            &fold_tile_kernel<K, 4, NT, kPlainWPB, false, false, true, false, true>);
-    return reinterpret_cast<const void *>(&fold_tile_kernel<K, -1, NT, kPlainWPB>);
+        if (log2g == 4 && f16) return reinterpret_cast<const void *>(&fold_tile_kernel<8, 4, NT, true>);
+    if (log2g == 4) return reinterpret_cast<const void *>(&fold_tile_kernel<K, 4, NT>);
+    return reinterpret_cast<const void *>(&fold_tile_kernel<K, -1, NT>);
 }
 
 // nt: hop = n (each byte read once); overlapping windows keep their lines in L2
@@ -579,15 +508,10 @@ static const void *fold_slide_kernel_for(bool f16)
 const void *fold_kernel_ptr(int k, int log2g, bool f16, bool nt, bool slide)
 {
     if (slide && log2g != 4) return nullptr;
-    switch (k) {
-#define FSKD_CASE(K) case K: return slide ? fold_slide_kernel_for<K>(f16) : fold_kernel_for<K>(log2g, f16, nt);
-        FSKD_CASE(1) FSKD_CASE(2) FSKD_CASE(3) FSKD_CASE(4)
-        FSKD_CASE(5) FSKD_CASE(6) FSKD_CASE(7) FSKD_CASE(8)
-        FSKD_CASE(9) FSKD_CASE(10) FSKD_CASE(11) FSKD_CASE(12)
-        FSKD_CASE(13) FSKD_CASE(14) FSKD_CASE(15) FSKD_CASE(16)
-#undef FSKD_CASE
-    default: return nullptr;
-    }
+    return for_tone_count(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        return slide ? fold_slide_kernel_for<K>(f16) : fold_kernel_for<K>(log2g, f16, nt);
+    });
 }
 
 }  // namespace fskd

@@ -31,28 +31,6 @@
 
 namespace fskd {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v)
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-
-// Sum over aligned groups of 2^log2g lanes; every lane of a group gets the
-// bit-identical total (each step adds the same two operands in both lanes).
-__device__ __forceinline__ float group_sum(float v, int log2g)
-{
-    if (log2g > 0) v += dpp_f<0xB1>(v);   // quad_perm [1,0,3,2]: lane ^ 1
-    if (log2g > 1) v += dpp_f<0x4E>(v);   // quad_perm [2,3,0,1]: lane ^ 2
-    if (log2g > 2) v += dpp_f<0x141>(v);  // row_half_mirror: other quad of the 8
-    if (log2g > 3) v += dpp_f<0x140>(v);  // row_mirror: other half of the row
-    if (log2g > 4) v += __shfl_xor(v, 16);
-    if (log2g > 5) v += __shfl_xor(v, 32);
-    return v;
-}
-
 // 16-byte chunk i of the samples at sp (plain load: the lines were just
 // streamed in, L2 may still hold them)
 __device__ __forceinline__ u32x4 global_chunk(const int16_t *sp, int i)
@@ -62,19 +40,13 @@ __device__ __forceinline__ u32x4 global_chunk(const int16_t *sp, int i)
 
 // LOG2G >= 0: lane-group size fixed at compile time (4 <=> n = 1024);
 // LOG2G == -1: taken from p.log2g at run time.
-// Tunables (defaults are the shipped configuration, chosen by scripts/probe):
-//   PF  tiles prefetched per wave in registers (1 or 2),
-//   NT  non-temporal loads (the PCM is read exactly once),
-//   WPB waves per block (each wave owns a private LDS slice).
-//   DIRECT  no LDS: each lane loads its own 128-byte segment (8 x 16 B;
-//           per instruction 64 lines, each fully consumed over the 8).
-//   NTS     non-temporal output stores.
-//   PK      pair tones into packed fp32 (v_pk_fma_f32 / v_pk_add_f32).
-//   SB      sched_barrier after every sample's K-tone step, so the K independent
-//           recurrences stay interleaved (hipcc otherwise serialises one tone's
-//           whole chain after another: issue-stall bound at large K).
-//   WS      window_sum.h epilogue (reduce-scatter, packed-key argmax, one
-//           coalesced magnitude store) at n = 1024.
+// 2-wave blocks (kPlainWPB), each wave with a private LDS slice; one tile
+// prefetched per wave in registers; plain output stores.
+//   NT      non-temporal loads (the PCM is read exactly once).
+//   PK      (K >= 3) tone pairs in packed fp32 (v_pk_fma_f32 / v_pk_add_f32);
+//           an odd last tone runs as a scalar chain.
+//   WS      (K >= 3 at n = 1024) window_sum.h epilogue (reduce-scatter,
+//           packed-key argmax, one coalesced magnitude store).
 //   SLIDE   overlapping windows at n = 1024, hop = 64 H < n: a
 //           window's 16 segments are shared with the windows around it, so a
 //           tile is 64 CONTIGUOUS segments whose recurrence states (s1, s2)
@@ -94,15 +66,24 @@ __device__ __forceinline__ u32x4 global_chunk(const int16_t *sp, int i)
 //           (3 ops per sample-tone instead of 2). The kernel keeps s in s1 and
 //           d in s2; the host folds s2 = sgn (s1 - d) into the rotation
 //           constants: X += (A - sgn B) s1 + sgn B d.
-template <int K, int LOG2G, int PF = 1, bool NT = true, int WPB = kWavesPerBlock,
-          bool DIRECT = false, bool NTS = false, bool PK = false, bool SB = false,
-          bool WS = false, bool RS = false, bool SLIDE = false>
-__global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams p)
+// Variants the probes (scripts/probe.hip) tried and did not ship; their source
+// is in git history at f48c2d8:
+//   PF 2    two tiles prefetched per wave in registers (the va / vb loop).
+//   DIRECT  no LDS: each lane loads its own 128-byte segment (8 x 16 B; per
+//           instruction 64 lines, each fully consumed over the 8).
+//   NTS     non-temporal output stores.
+//   SB      sched_barrier after every sample's K-tone step, to keep the K
+//           recurrences interleaved: neutral to worse (probe "SB").
+//   WPB     other block sizes than kPlainWPB (demod_internal.h has the numbers).
+template <int K, int LOG2G, bool NT = true, bool RS = false, bool SLIDE = false>
+__global__ __launch_bounds__(64 * kPlainWPB) void goertzel_tile_kernel(GoertzelParams p)
 {
-    static_assert(PF == 1 || PF == 2, "prefetch depth");
-    static_assert(!SLIDE || (LOG2G == 4 && !DIRECT && PF == 1), "SLIDE: n = 1024");
+    constexpr int WPB = kPlainWPB;
+    constexpr bool PK = K >= 3;
+    constexpr bool WS = K >= 3 && LOG2G == 4;
+    static_assert(!SLIDE || LOG2G == 4, "SLIDE: n = 1024");
     static_assert(!SLIDE || K * 64 * 8 + 64 * 4 <= kLdsWaveBytes, "SLIDE: states + energies in the slice");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[DIRECT ? 16 : WPB * kLdsWaveBytes];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[WPB * kLdsWaveBytes];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: tile bases stay in SGPRs (no waterfall loop per buffer load)
     unsigned char *wl = lds + wave * kLdsWaveBytes;
@@ -127,11 +108,8 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int q = 64 * i + lane;
-        if (DIRECT)
-            goff[i] = (int)(((long long)win_in_tile * p.hop + seg * 64 + 8 * i) * 2);
-        else
-            goff[i] = (int)(((long long)(q >> cpw_log2) * lhop +
-                             (long long)(q & ((1 << cpw_log2) - 1)) * 8) * 2);
+        goff[i] = (int)(((long long)(q >> cpw_log2) * lhop +
+                         (long long)(q & ((1 << cpw_log2) - 1)) * 8) * 2);
     }
     // LDS write slot of chunk i: segment 8i + lane/8, chunk lane%8
     const int wr_off = (lane >> 3) * kLdsSegStride + (lane & 7) * 16;
@@ -140,52 +118,35 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
     const long long stride = (long long)gridDim.x * WPB;
     long long t = tile_block(p.xcd_swizzle) * WPB + wave;
 
-    auto load_tile = [&](long long tt, u32x4 v[8]) {
-        const long long wbase = tt * wins_per_tile;
-        const long long left = p.n_windows - wbase;  // >= 1
-        long long bytes = ((left - 1) * p.hop + n) * 2;
-        if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(p.pcm + wbase * p.hop), (short)0, (int)bytes, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, goff[i], 0, NT ? 2 : 0);
+    auto load_tile = [&](long long tt, u32x4 (&v)[8]) {
+        tile_load<NT ? 2 : 0>(tile_rsrc(p, tt * wins_per_tile, n), goff, v);
     };
 
     // One tile: stage v through LDS, refill v with tile `next`, then run the
     // recurrences, the rotation + lane-group reduction and the decision.
-    auto do_tile = [&](long long tt, u32x4 v[8], long long next) {
-        u32x4 cur[8];
-        if (DIRECT) {
+    auto do_tile = [&](long long tt, u32x4 (&v)[8], long long next) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) cur[i] = v[i];
-            if (next < n_tiles) load_tile(next, v);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                *reinterpret_cast<u32x4 *>(wl + wr_off + i * 8 * kLdsSegStride) = v[i];
-            if (next < n_tiles) load_tile(next, v);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
+        for (int i = 0; i < 8; ++i)
+            *reinterpret_cast<u32x4 *>(wl + wr_off + i * 8 * kLdsSegStride) = v[i];
+        if (next < n_tiles) load_tile(next, v);
+        wave_sync();
 
         float s1[K], s2[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) { s1[k] = 0.f; s2[k] = 0.f; }
 
-        if constexpr (PK && K >= 2) {
+        if constexpr (PK) {
             // tone pairs in packed fp32 (v_pk_add_f32 + v_pk_fma_f32 per sample
             // per pair); an odd last tone runs as a scalar chain
             constexpr int H = K / 2;
-            f32x2 c2[H], sg2[H], a1[H], a2[H];
+            f2 c2[H], sg2[H], a1[H], a2[H];
             float cs = 0.f, ss = 0.f, b1 = 0.f, b2 = 0.f;
 #pragma unroll
             for (int h = 0; h < H; ++h) {
-                c2[h] = f32x2{p.coef[2 * h], p.coef[2 * h + 1]};
-                if (RS) sg2[h] = f32x2{p.sgn[2 * h], p.sgn[2 * h + 1]};
-                a1[h] = f32x2{0.f, 0.f};
-                a2[h] = f32x2{0.f, 0.f};
+                c2[h] = f2{p.coef[2 * h], p.coef[2 * h + 1]};
+                if (RS) sg2[h] = f2{p.sgn[2 * h], p.sgn[2 * h + 1]};
+                a1[h] = f2{0.f, 0.f};
+                a2[h] = f2{0.f, 0.f};
             }
             if (K & 1) {
                 cs = p.coef[K - 1];
@@ -193,22 +154,22 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const u32x4 sj = DIRECT ? cur[j] : *reinterpret_cast<const u32x4 *>(wl + rd_off + j * 16);
+                const u32x4 sj = *reinterpret_cast<const u32x4 *>(wl + rd_off + j * 16);
                 const uint32_t d4[4] = {sj.x, sj.y, sj.z, sj.w};
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const uint32_t d = d4[q >> 1];
                     const float x = (q & 1) ? (float)((int)d >> 16) : (float)(int)(short)(d & 0xFFFFu);
-                    const f32x2 xx = f32x2{x, x};
+                    const f2 xx = f2{x, x};
 #pragma unroll
                     for (int h = 0; h < H; ++h) {
                         if constexpr (RS) {  // a1 = s, a2 = d
-                            const f32x2 d = __builtin_elementwise_fma(
+                            const f2 d = __builtin_elementwise_fma(
                                 c2[h], a1[h], __builtin_elementwise_fma(sg2[h], a2[h], xx));
                             a1[h] = __builtin_elementwise_fma(sg2[h], a1[h], d);
                             a2[h] = d;
                         } else {
-                            const f32x2 a = __builtin_elementwise_fma(c2[h], a1[h], xx - a2[h]);
+                            const f2 a = __builtin_elementwise_fma(c2[h], a1[h], xx - a2[h]);
                             a2[h] = a1[h];
                             a1[h] = a;
                         }
@@ -224,7 +185,6 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
                             b1 = a;
                         }
                     }
-                    if (SB) __builtin_amdgcn_sched_barrier(0);
                 }
             }
 #pragma unroll
@@ -241,7 +201,7 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
         } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const u32x4 sj = DIRECT ? cur[j] : *reinterpret_cast<const u32x4 *>(wl + rd_off + j * 16);
+            const u32x4 sj = *reinterpret_cast<const u32x4 *>(wl + rd_off + j * 16);
             const uint32_t d4[4] = {sj.x, sj.y, sj.z, sj.w};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -264,7 +224,6 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
                         }
                     }
                 }
-                if (SB) __builtin_amdgcn_sched_barrier(0);
             }
         }
         }
@@ -272,14 +231,10 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
         if constexpr (SLIDE) {
             // segment states -> LDS (the samples are consumed)
             float2 *lz = reinterpret_cast<float2 *>(wl);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
 #pragma unroll
             for (int k = 0; k < K; ++k) lz[k * 64 + lane] = make_float2(s1[k], s2[k]);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             const int H = (int)(p.hop >> 6);
             const int wt = (int)wins_per_tile;
             // stage 2's energies: the tile's segments' fp32 sums x^2, computed
@@ -300,9 +255,9 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
                     const float2 z = lz[k * 64 + sg];   // (s1, s2) of segment j of window u
                     if constexpr (WS) {
                         // packed (re, im): (A s1) - (B s2), as the direct WS path below
-                        const f32x2 X = __builtin_elementwise_fma(
-                            f32x2{-r[k].z, -r[k].w}, f32x2{z.y, z.y},
-                            f32x2{r[k].x, r[k].y} * f32x2{z.x, z.x});
+                        const f2 X = __builtin_elementwise_fma(
+                            f2{-r[k].z, -r[k].w}, f2{z.y, z.y},
+                            f2{r[k].x, r[k].y} * f2{z.x, z.x});
                         xr[k] = X.x;
                         xi[k] = X.y;
                     } else {  // as the direct K <= 2 path below
@@ -323,9 +278,7 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
                         le[lane] = seg_energy_lowreg<FSKD_SLIDE_EU>([&](int i) {
                             return real ? global_chunk(sp, i) : u32x4{0u, 0u, 0u, 0u};
                         });
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        wave_sync();
                         have_e = true;
                     }
                     return group_sum(live ? le[sg] : 0.f, 4);
@@ -343,11 +296,14 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
                     bool amb;
                     const int arg = chain_decide<K>(P, live, p.amb_tq, p.amb_floor, p.amb_t2e, efn, amb);
                     if (live) {
-                        if (seg == 0) out_store<NTS>(p.sym + w, (uint8_t)(arg | (amb ? kSymAmbiguous : 0)));
+                        if (seg == 0) {
+                            uint8_t *const so = p.sym + w;  // address before value, as below
+                            *so = (uint8_t)(arg | (amb ? kSymAmbiguous : 0));
+                        }
                         if (p.mag) {
 #pragma unroll
                             for (int k = 0; k < K; ++k)
-                                if ((k & 15) == seg) out_store<NTS>(p.mag + w * K + k, P[k]);
+                                if ((k & 15) == seg) p.mag[w * K + k] = P[k];
                         }
                     }
                 }
@@ -360,20 +316,14 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
         const long long w = tt * wins_per_tile + win_in_tile;
         const bool live = w < p.n_windows;
         // stage 2 of the ambiguity test (demod_internal.h): this lane's 64
-        // samples again (the tile is still in the wave's LDS slice, or from
-        // L2 for DIRECT), summed over the window's lanes
+        // samples again (the tile is still in the wave's LDS slice), summed
+        // over the window's lanes
         auto efn = [&]() {
-            float e;
-            if constexpr (DIRECT) {
-                const int16_t *sp = p.pcm + w * p.hop + 64 * seg;
-                e = seg_energy([&](int i) { return live ? global_chunk(sp, i) : u32x4{0u, 0u, 0u, 0u}; });
-            } else {
-                // an opaque offset: the recurrence read the same LDS bytes,
-                // and reusing those values would keep 32 VGPRs live across it
-                int off = rd_off;
-                asm volatile("" : "+v"(off));
-                e = seg_energy([&](int i) { return *reinterpret_cast<const u32x4 *>(wl + off + 16 * i); });
-            }
+            // an opaque offset: the recurrence read the same LDS bytes,
+            // and reusing those values would keep 32 VGPRs live across it
+            int off = rd_off;
+            asm volatile("" : "+v"(off));
+            const float e = seg_energy([&](int i) { return *reinterpret_cast<const u32x4 *>(wl + off + 16 * i); });
             return group_sum(e, log2g);
         };
         // in-kernel rescue (n = 1024, tile in LDS): the window's chunk q
@@ -381,16 +331,16 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
             return *reinterpret_cast<const u32x4 *>(wl + (16 * win_in_tile + (q >> 3)) * kLdsSegStride +
                                                     (q & 7) * 16);
         };
-        constexpr bool kInline = LOG2G == 4 && !DIRECT && K >= 2 && K <= 16;
+        constexpr bool kInline = LOG2G == 4 && K >= 2 && K <= 16;
         const bool defer = kInline && p.rescue_inline;
-        if constexpr (WS && LOG2G == 4) {
+        if constexpr (WS) {
             float xr[K], xi[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 // packed (re, im): (A s1) - (B s2), 2 ops per tone
-                const f32x2 X = __builtin_elementwise_fma(f32x2{-r[k].z, -r[k].w},
-                                                          f32x2{s2[k], s2[k]},
-                                                          f32x2{r[k].x, r[k].y} * f32x2{s1[k], s1[k]});
+                const f2 X = __builtin_elementwise_fma(f2{-r[k].z, -r[k].w},
+                                                       f2{s2[k], s2[k]},
+                                                       f2{r[k].x, r[k].y} * f2{s1[k], s1[k]});
                 xr[k] = X.x;
                 xi[k] = X.y;
             }
@@ -414,11 +364,16 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
         bool amb;
         const int arg = chain_decide<K>(P, live, p.amb_tq, p.amb_floor, p.amb_t2e, efn, amb);
         if (live && !(amb && defer)) {
-            if (seg == 0) out_store<NTS>(p.sym + w, (uint8_t)(arg | (amb ? kSymAmbiguous : 0)));
+            if (seg == 0) {
+                // the address is formed before the value: written as
+                // p.sym[w] = .. the compiler schedules this store differently
+                uint8_t *const so = p.sym + w;
+                *so = (uint8_t)(arg | (amb ? kSymAmbiguous : 0));
+            }
             if (p.mag) {
 #pragma unroll
                 for (int k = 0; k < K; ++k)
-                    if ((k & (g - 1)) == seg) out_store<NTS>(p.mag + w * K + k, P[k]);
+                    if ((k & (g - 1)) == seg) p.mag[w * K + k] = P[k];
             }
         }
         if constexpr (kInline) {
@@ -428,74 +383,41 @@ __global__ __launch_bounds__(64 * WPB) void goertzel_tile_kernel(GoertzelParams 
         }
     };
 
-    if (PF == 1) {
-        u32x4 v[8];
-        if (t < n_tiles) load_tile(t, v);
-        for (; t < n_tiles; t += stride) do_tile(t, v, t + stride);
-    } else {
-        u32x4 va[8], vb[8];
-        if (t < n_tiles) load_tile(t, va);
-        if (t + stride < n_tiles) load_tile(t + stride, vb);
-        for (; t < n_tiles; t += 2 * stride) {
-            do_tile(t, va, t + 2 * stride);
-            if (t + stride >= n_tiles) break;
-            do_tile(t + stride, vb, t + 3 * stride);
-        }
-    }
+    u32x4 v[8];
+    if (t < n_tiles) load_tile(t, v);
+    for (; t < n_tiles; t += stride) do_tile(t, v, t + stride);
     wb_burst(p.wb_bursts);
 }
 
-// Shipped configuration: packed tone pairs for K >= 3 (K = 4: 407 -> 336 us,
-// K = 8: 657 -> 506 us on 2^20 windows; K = 2 is HBM-bound either way) and the
-// window_sum.h epilogue for K >= 3 (K = 8: 484 -> 456 us; neutral at K <= 4,
-// profiles/round1/probe_window_sum.log).
-// RS (Reinsch form) only for plans with a tone near 0 or fs/2 (the host's
+// What ships, per tone count K: packed tone pairs for K >= 3 (K = 4: 407 ->
+// 336 us, K = 8: 657 -> 506 us on 2^20 windows; K = 2 is HBM-bound either way)
+// and the window_sum.h epilogue for K >= 3 at n = 1024 (K = 8: 484 -> 456 us;
+// neutral at K <= 4, profiles/round1/probe_window_sum.log), both fixed by K
+// and LOG2G inside the kernel.
+// rs (Reinsch form) only for plans with a tone near 0 or fs/2 (the host's
 // kReinschSin test): elsewhere the plain form is within the bar at 2 ops.
-template <int K, bool NT>
-static const void *kernel_for_t(int log2g, bool rs)
-{
-    constexpr bool PK = K >= 3;
-    if (log2g == 4)
-        return rs ? reinterpret_cast<const void *>(
-                        &goertzel_tile_kernel<K, 4, 1, NT, kPlainWPB, false, false, PK, false,
-                                              K >= 3, true>)
-                  : reinterpret_cast<const void *>(
-                        &goertzel_tile_kernel<K, 4, 1, NT, kPlainWPB, false, false, PK, false,
-                                              K >= 3>);
-    return rs ? reinterpret_cast<const void *>(
-                    &goertzel_tile_kernel<K, -1, 1, NT, kPlainWPB, false, false, PK, false,
-                                          false, true>)
-              : reinterpret_cast<const void *>(
-                    &goertzel_tile_kernel<K, -1, 1, NT, kPlainWPB, false, false, PK>);
-}
-
 // nt: the PCM is read once (hop = n); overlapping windows (hop < n) load with
 // the plain cache policy so neighbouring tiles find their shared lines in L2.
+template <int K, int LOG2G, bool NT>
+static const void *kernel_for_rs(bool rs)
+{
+    return rs ? reinterpret_cast<const void *>(&goertzel_tile_kernel<K, LOG2G, NT, true>)
+              : reinterpret_cast<const void *>(&goertzel_tile_kernel<K, LOG2G, NT, false>);
+}
+
 template <int K>
 static const void *kernel_for(int log2g, bool rs, bool slide, bool nt)
 {
-    constexpr bool PK = K >= 3;
     if (slide)  // cached loads: neighbouring tiles share their edge segments
-        return rs ? reinterpret_cast<const void *>(
-                        &goertzel_tile_kernel<K, 4, 1, false, kPlainWPB, false, false, PK, false,
-                                              K >= 3, true, true>)
-                  : reinterpret_cast<const void *>(
-                        &goertzel_tile_kernel<K, 4, 1, false, kPlainWPB, false, false, PK, false,
-                                              K >= 3, false, true>);
-    return nt ? kernel_for_t<K, true>(log2g, rs) : kernel_for_t<K, false>(log2g, rs);
+        return rs ? reinterpret_cast<const void *>(&goertzel_tile_kernel<K, 4, false, true, true>)
+                  : reinterpret_cast<const void *>(&goertzel_tile_kernel<K, 4, false, false, true>);
+    if (log2g == 4) return nt ? kernel_for_rs<K, 4, true>(rs) : kernel_for_rs<K, 4, false>(rs);
+    return nt ? kernel_for_rs<K, -1, true>(rs) : kernel_for_rs<K, -1, false>(rs);
 }
 
 static const void *kernel_ptr(int k, int log2g, bool rs, bool slide, bool nt)
 {
-    switch (k) {
-#define FSKD_CASE(K) case K: return kernel_for<K>(log2g, rs, slide, nt);
-        FSKD_CASE(1) FSKD_CASE(2) FSKD_CASE(3) FSKD_CASE(4)
-        FSKD_CASE(5) FSKD_CASE(6) FSKD_CASE(7) FSKD_CASE(8)
-        FSKD_CASE(9) FSKD_CASE(10) FSKD_CASE(11) FSKD_CASE(12)
-        FSKD_CASE(13) FSKD_CASE(14) FSKD_CASE(15) FSKD_CASE(16)
-#undef FSKD_CASE
-    default: return nullptr;
-    }
+    return for_tone_count(k, [&](auto kc) { return kernel_for<decltype(kc)::value>(log2g, rs, slide, nt); });
 }
 
 // One tile per wave (grid = tiles / waves-per-block): measured 317 us vs

@@ -44,8 +44,6 @@ constexpr int kRescueChunk = 512;
 constexpr int kRescueSplit = 4;
 constexpr int kRescueLdsBytes = 32768;    // Goertzel: staged samples per group
 
-typedef unsigned int u32x4q __attribute__((ext_vector_type(4)));
-
 __global__ __launch_bounds__(64) void rescue_kernel(RescueParams p)
 {
 #pragma clang fp contract(off)
@@ -100,14 +98,14 @@ __global__ __launch_bounds__(64) void rescue_kernel(RescueParams p)
             // 16-byte chunks, eight loads per lane in flight at a time (a
             // plain loop left one L2 round trip per chunk on the critical path)
             for (int c0 = 0; c0 < cnt * chunks; c0 += 8 * 64) {
-                u32x4q v[8];
+                u32x4 v[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int c = c0 + 64 * u + lane;
                     if (c < cnt * chunks) {
                         const int ff = c / chunks, q = c - ff * chunks;
                         const long long w = base + idx[g0 + ff];
-                        v[u] = reinterpret_cast<const u32x4q *>(p.pcm + w * p.hop)[q];
+                        v[u] = reinterpret_cast<const u32x4 *>(p.pcm + w * p.hop)[q];
                     }
                 }
 #pragma unroll
@@ -115,7 +113,7 @@ __global__ __launch_bounds__(64) void rescue_kernel(RescueParams p)
                     const int c = c0 + 64 * u + lane;
                     if (c < cnt * chunks) {
                         const int ff = c / chunks, q = c - ff * chunks;
-                        *reinterpret_cast<u32x4q *>(smp + ff * stride + 16 * q) = v[u];
+                        *reinterpret_cast<u32x4 *>(smp + ff * stride + 16 * q) = v[u];
                     }
                 }
             }
@@ -125,10 +123,10 @@ __global__ __launch_bounds__(64) void rescue_kernel(RescueParams p)
             if (act) {
                 const double c = p.coef[t];
                 double s1 = 0.0, s2 = 0.0;
-                const u32x4q *xs = reinterpret_cast<const u32x4q *>(smp + f * stride);
+                const u32x4 *xs = reinterpret_cast<const u32x4 *>(smp + f * stride);
 #pragma unroll 4
                 for (int q = 0; q < chunks; ++q) {
-                    const u32x4q d = xs[q];
+                    const u32x4 d = xs[q];
                     const unsigned d4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
@@ -216,7 +214,7 @@ constexpr int kSegStates = 256;
 // from zero: rescue_rows' pass-0 arithmetic, operation for operation.
 // v is made opaque first: the extractions are not shared with an earlier use
 // (seg_energy64's were kept live, 64 VGPRs, for these).
-__device__ __forceinline__ void seg_pair(u32x4q (&v)[8], double c0, double c1, double &a1,
+__device__ __forceinline__ void seg_pair(u32x4 (&v)[8], double c0, double c1, double &a1,
                                          double &a2, double &b1, double &b2)
 {
 #pragma clang fp contract(off)
@@ -250,7 +248,7 @@ __device__ __forceinline__ void seg_pair(u32x4q (&v)[8], double c0, double c1, d
 // instructions per 2 samples instead of 4, relative error < 36 u for the 32
 // non-negative terms (error_model.cpp's E allows 100 u)
 typedef short rs_short2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float seg_energy64(const u32x4q (&v)[8])
+__device__ __forceinline__ float seg_energy64(const u32x4 (&v)[8])
 {
     float e = 0.f;
 #pragma unroll
@@ -263,13 +261,6 @@ __device__ __forceinline__ float seg_energy64(const u32x4q (&v)[8])
         }
     }
     return e;
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // One tone of a row's pass-0 decision: rotation of the lane's segment state
@@ -351,9 +342,9 @@ __device__ __forceinline__ bool seg_residue_window(const RescueParams &p, long l
 #pragma clang fp contract(off)
     const int K = p.k;
     const int16_t *xs = p.pcm + w * p.hop + 8 * seg;
-    u32x4q v[8];
+    u32x4 v[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) v[m] = *reinterpret_cast<const u32x4q *>(xs + 128 * m);
+    for (int m = 0; m < 8; ++m) v[m] = *reinterpret_cast<const u32x4 *>(xs + 128 * m);
     auto smp = [&](int m, int i) {
         const unsigned d4[4] = {v[m].x, v[m].y, v[m].z, v[m].w};
         return (int)(short)((d4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
@@ -616,8 +607,8 @@ void rescue_seg_kernel(RescueParams p)
                     RS_CHECK(si, kSegStates, "sst");
                 }
 #endif
-                const u32x4q *src = reinterpret_cast<const u32x4q *>(s0 + 64 * s);
-                u32x4q v[8];
+                const u32x4 *src = reinterpret_cast<const u32x4 *>(s0 + 64 * s);
+                u32x4 v[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = src[q];
                 if (pp == 0) sen[s] = seg_energy64(v);
@@ -670,9 +661,9 @@ void rescue_seg_kernel(RescueParams p)
             // rescue_rows_fold0's arithmetic: lane seg's folded samples
             // 8 seg .. + 7 (samples 128 m + 8 seg + i, m < 8), 8-step chains
             const int16_t *xs = p.pcm + w * p.hop + 8 * seg;
-            u32x4q v[8];
+            u32x4 v[8];
 #pragma unroll
-            for (int m = 0; m < 8; ++m) v[m] = *reinterpret_cast<const u32x4q *>(xs + 128 * m);
+            for (int m = 0; m < 8; ++m) v[m] = *reinterpret_cast<const u32x4 *>(xs + 128 * m);
             int xf[8];
             float e = seg_energy64(v);
 #pragma unroll
@@ -722,8 +713,8 @@ void rescue_seg_kernel(RescueParams p)
             Tl += __popcll(lb);
             continue;
         }
-        const u32x4q *src = reinterpret_cast<const u32x4q *>(p.pcm + w * p.hop + 64 * seg);
-        u32x4q v[8];
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(p.pcm + w * p.hop + 64 * seg);
+        u32x4 v[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = src[q];
         const float e = seg_energy64(v);
@@ -760,11 +751,11 @@ void rescue_seg_kernel(RescueParams p)
         if (act) {
             const double c = p.coef[t];
             double s1 = 0.0, s2 = 0.0;
-            const u32x4q *xs = reinterpret_cast<const u32x4q *>(p.pcm + w * p.hop);
-            u32x4q nx = xs[0];
+            const u32x4 *xs = reinterpret_cast<const u32x4 *>(p.pcm + w * p.hop);
+            u32x4 nx = xs[0];
 #pragma unroll 1
             for (int q = 0; q < 128; ++q) {
-                const u32x4q d = nx;
+                const u32x4 d = nx;
                 if (q + 1 < 128) nx = xs[q + 1];
                 const unsigned d4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll

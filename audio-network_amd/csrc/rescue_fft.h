@@ -35,13 +35,6 @@ typedef __attribute__((address_space(3))) double lds_double;
 // LDS slot of FFT position q: one pad double per 16 (1088 slots)
 __device__ __forceinline__ int rfslot(int q) { return q + (q >> 4); }
 
-__device__ __forceinline__ void rf_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // the definition's radix-2 butterfly on (a, b) with twiddle (wr, wi)
 __device__ __forceinline__ void rf_bfly(double &ar, double &ai, double &br, double &bi, double wr, double wi)
 {
@@ -104,13 +97,13 @@ __device__ __attribute__((always_inline)) inline void rescue_fft_window(const in
     // exchange A -> B: lane l takes positions lo + 16 m + 256 hi
 #pragma unroll
     for (int e = 0; e < 16; ++e) xs[rfslot(16 * lane + e)] = ar[e];
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int m = 0; m < 16; ++m) ar[m] = xs[rfslot(lo + 16 * m + 256 * hi)];
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int e = 0; e < 16; ++e) xs[rfslot(16 * lane + e)] = ai[e];
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int m = 0; m < 16; ++m) ai[m] = xs[rfslot(lo + 16 * m + 256 * hi)];
     // pass B: stages len 32 .. 256 (half 16 h), j = lo + 16 (m & (h - 1))
@@ -123,18 +116,18 @@ __device__ __attribute__((always_inline)) inline void rescue_fft_window(const in
                 rf_bfly(ar[m], ai[m], ar[m + h], ai[m + h], t.x, t.y);
             }
     // exchange B -> C: lane l takes positions l + 64 q + 256 m (slot 4 q + m)
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int m = 0; m < 16; ++m) xs[rfslot(lo + 16 * m + 256 * hi)] = ar[m];
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int m = 0; m < 4; ++m) ar[4 * q + m] = xs[rfslot(lane + 64 * q + 256 * m)];
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int m = 0; m < 16; ++m) xs[rfslot(lo + 16 * m + 256 * hi)] = ai[m];
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -151,7 +144,7 @@ __device__ __attribute__((always_inline)) inline void rescue_fft_window(const in
     }
     // natural order now: slot 4 q + m holds bin g + 256 m. P = re^2 + im^2 for
     // bins 0 .. 512 into the slab (reads done above), the spectrum row as fp32
-    rf_wave_sync();
+    wave_sync();
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -166,7 +159,7 @@ __device__ __attribute__((always_inline)) inline void rescue_fft_window(const in
         xs[512] = P;
         if (spec) spec[512] = (float)P;
     }
-    rf_wave_sync();
+    wave_sync();
     // argmax over the tones (ties to the lowest), as the oracle's loop
     double best = -1.0;
     int arg = 0;
@@ -179,7 +172,7 @@ __device__ __attribute__((always_inline)) inline void rescue_fft_window(const in
         }
     }
     if (lane == 0) *sym = (uint8_t)arg;
-    rf_wave_sync();
+    wave_sync();
 }
 
 // The FFT rescue's first pass (round 4, tones only): the

@@ -40,51 +40,14 @@
 
 namespace fskd {
 
-typedef unsigned int u32x4r __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-template <int CTRL>
-__device__ __forceinline__ float dppr_(float v)
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ float group_sum_r(float v, int log2g)
-{
-    if (log2g > 0) v += dppr_<0xB1>(v);
-    if (log2g > 1) v += dppr_<0x4E>(v);
-    if (log2g > 2) v += dppr_<0x141>(v);
-    if (log2g > 3) v += dppr_<0x140>(v);
-    if (log2g > 4) v += __shfl_xor(v, 16);
-    if (log2g > 5) v += __shfl_xor(v, 32);
-    return v;
-}
-
 // Class pairs of one folded sample from its eight spaced samples x[m].
 //   a_m = x_m + x_{m+4}, d_m = x_m - x_{m+4}           (m < 4)
 //   e0 = a0 + a2, e1 = a0 - a2, e2 = a1 + a3, e3 = a1 - a3
 //   Z0 = e0 + e2, Z4 = e0 - e2, Z2 = e1 - j e3 (class 3 stores (e1, e3) = Z6)
 //   u = d1 - d3, v = d1 + d3
 //   Z1 = (d0 + u/sqrt2) - j (d2 + v/sqrt2),  Z3 = (d0 - u/sqrt2) + j (d2 - v/sqrt2)
-__device__ __forceinline__ void residue_classes(const float x[8], f2 &z04, f2 &z1, f2 &z3, f2 &z6)
-{
-    const float kr = 0.70710678118654752f;
-    const f2 a02 = f2{x[0], x[2]} + f2{x[4], x[6]};
-    const f2 d02 = f2{x[0], x[2]} - f2{x[4], x[6]};
-    const f2 a13 = f2{x[1], x[3]} + f2{x[5], x[7]};
-    const f2 d13 = f2{x[1], x[3]} - f2{x[5], x[7]};
-    const f2 e01 = f2{a02.x, a02.x} + f2{a02.y, -a02.y};
-    const f2 e23 = f2{a13.x, a13.x} + f2{a13.y, -a13.y};
-    z04 = f2{e01.x, e01.x} + f2{e23.x, -e23.x};
-    z6 = f2{e01.y, e23.y};
-    const f2 uv = f2{d13.x, d13.x} + f2{-d13.y, d13.y};
-    z1 = __builtin_elementwise_fma(uv, f2{kr, -kr}, f2{d02.x, -d02.y});
-    z3 = __builtin_elementwise_fma(uv, f2{-kr, -kr}, d02);
-}
-
-// The same butterflies as one asm block with the op_sel / neg modifiers
-// spelled out: hipcc builds per-half negations and half swaps from v_xor +
+// One asm block with the op_sel / neg modifiers spelled out: from plain C
+// hipcc builds per-half negations and half swaps from v_xor +
 // v_mov. Inputs are the pairs (x0, x2), (x4, x6), (x1, x3), (x5, x7); kk =
 // (1/sqrt2, 1/sqrt2). The sums are formed in place ((a0, a2) -> (e0, e1),
 // (a1, a3) -> (e2, e3), (d1, d3) -> (u, v)) to keep the register footprint at
@@ -150,18 +113,14 @@ __device__ __forceinline__ void residue_even_classes_asm(const f2 (&p02)[2], con
 // [4 classes][QP sample pairs][64 lanes] float4 (4 QP KiB).
 constexpr int kResidueQP = 2;  // shipped: two sample pairs per LDS round
 
-// Tunables (defaults = shipped, chosen with scripts/probe.hip, in git history at 8b49018):
-//   ASM   butterflies as residue_classes_asm (else the plain-C residue_classes),
-//   ROTV  rotation constants in VGPRs (8 per tone) instead of the LDS table,
-//   MINW  > 0: ask for MINW waves per SIMD (VGPR budget 512 / MINW),
-//   QP    sample pairs per LDS round (1, 2 or 4): 4 QP KiB of LDS per wave,
-//   PF    prefetch the wave's next tile before computing the current one
-//         (only matters on grids with more than one tile per wave),
-//   WS    window_sum.h epilogue (reduce-scatter, packed-key argmax) at n = 1024,
-//   LDST  (n = 1024, QP = 2) load the tile 1 KiB contiguous per wave
-//         instruction, as the plain bank does, and regroup it through the
-//         wave's LDS slice (linear chunk q at 16 q; the class pairs reuse the
-//         slice afterwards) instead of the direct per-lane layout.
+// The tile kernel: 4-wave blocks (kWavesPerBlock) sharing the rotation table
+// in LDS, the butterflies as residue_classes_asm, kResidueQP sample pairs per
+// LDS round, direct per-lane loads, 4 waves per SIMD asked for up to K = 8
+// (VGPR budget 128), and at n = 1024 the window_sum.h epilogue (reduce-scatter,
+// packed-key argmax) with the in-kernel rescue.
+// LOG2G >= 0: lane-group size fixed at compile time (4 <=> n = 1024);
+// LOG2G == -1: taken from p.log2g at run time.
+//   NT    non-temporal input loads (hop = n: each byte is read once).
 //   DC    compile-time classes: tone slot k reads its class straight from
 //         registers (no LDS class file), for plans the host has permuted
 //         into a fixed slot -> class pattern (window_sum maps slots back):
@@ -172,13 +131,24 @@ constexpr int kResidueQP = 2;  // shipped: two sample pairs per LDS round
 //         e.g. spacing 4 or 12 from an odd multiple of 4); 4 = every slot
 //         class 3 (residues 2 / 6). Modes 2-4 form only the classes they read
 //         (residue_even_classes_asm). 0 = the LDS class file (any plan).
-template <int K, int LOG2G, int WPB = kWavesPerBlock, bool ASM = true, bool ROTV = false,
-          int MINW = (K <= 8 ? 4 : 0), int QP = kResidueQP, bool PF = false, bool WS = true,
-          bool LDST = false, int DC = 0, bool NT = true>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(MINW > 0 ? MINW : 1)))
+// Variants scripts/probe.hip tried and did not ship; their source is in git
+// history at f48c2d8 (the probe itself at 8b49018):
+//   ASM off  the butterflies in plain C (residue_classes).
+//   ROTV     rotation constants in VGPRs (8 per tone) instead of the LDS table.
+//   MINW     other waves-per-SIMD requests than 4 up to K = 8, none above.
+//   QP 1, 4  one or four sample pairs per LDS round (4 QP KiB of LDS per wave).
+//   PF       prefetch the wave's next tile before computing the current one
+//            (only matters on grids with more than one tile per wave).
+//   WS off   the all-reduce epilogue at n = 1024.
+//   LDST     (n = 1024) the tile loaded 1 KiB contiguous per wave instruction
+//            and regrouped through the wave's LDS slice, as fold.hip does.
+template <int K, int LOG2G, int DC = 0, bool NT = true>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 4 : 1)))
 void residue_tile_kernel(GoertzelParams p)
 {
+    constexpr int WPB = kWavesPerBlock, QP = kResidueQP;
     constexpr bool DCLS = DC > 0;
+    static_assert(!DCLS || LOG2G == 4, "DCLS un-permutes in the window_sum epilogue");
     extern __shared__ f4 lds_r[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -193,26 +163,12 @@ void residue_tile_kernel(GoertzelParams p)
     f4 *rot = lds_r;
     f4 *zw = lds_r + K * g * 2 + wave * (4 * QP * 64) + lane;
     const f4 *grot = reinterpret_cast<const f4 *>(p.rot);
-    static_assert(!LDST || (LOG2G == 4 && QP == 2), "LDST regrouping: n = 1024, 8 KiB slice");
     int goff[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        if (LDST) {
-            const int q = 64 * m + lane;  // chunk q of the tile: window q / 128, chunk q % 128
-            goff[m] = (int)(((long long)(q >> 7) * p.hop + (long long)(q & 127) * 8) * 2);
-        } else {
-            goff[m] = (int)(((long long)win_in_tile * p.hop + (long long)(j + g * m) * 8) * 2);
-        }
-    }
-    auto load_tile = [&](long long tt, u32x4r v[8]) {
-        const long long wbase = tt * wins_per_tile;
-        long long bytes = ((p.n_windows - wbase - 1) * p.hop + n) * 2;
-        if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)(p.pcm + wbase * p.hop), (short)0, (int)bytes, 0x00020000);
-#pragma unroll
-        for (int m = 0; m < 8; ++m)
-            v[m] = __builtin_amdgcn_raw_buffer_load_b128(rs, goff[m], 0, NT ? 2 : 0);
+    for (int m = 0; m < 8; ++m)
+        goff[m] = (int)(((long long)win_in_tile * p.hop + (long long)(j + g * m) * 8) * 2);
+    auto load_tile = [&](long long tt, u32x4 (&v)[8]) {
+        tile_load<NT ? 2 : 0>(tile_rsrc(p, tt * wins_per_tile, n), goff, v);
     };
 
     const long long stride = (long long)gridDim.x * WPB;
@@ -220,45 +176,18 @@ void residue_tile_kernel(GoertzelParams p)
     // The first tile's loads go out before the rotation table is staged and
     // the block barrier, so the two latencies overlap: with one tile per wave
     // (the usual grid) this prologue is on every wave's critical path.
-    u32x4r v[8];
+    u32x4 v[8];
     if (t < n_tiles) load_tile(t, v);
-    f4 rv[ROTV ? 2 * K : 1];
-    if (ROTV) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            rv[2 * k] = grot[(k * g + j) * 2];
-            rv[2 * k + 1] = grot[(k * g + j) * 2 + 1];
-        }
-    } else {
-        for (int i = threadIdx.x; i < K * g * 2; i += 64 * WPB) rot[i] = grot[i];
-        __syncthreads();
-    }
+    for (int i = threadIdx.x; i < K * g * 2; i += 64 * WPB) rot[i] = grot[i];
+    __syncthreads();
     const f2 kk = f2{0.70710678118654752f, 0.70710678118654752f};
 
     for (bool first = true; t < n_tiles; t += stride, first = false) {
         const long long wbase = t * wins_per_tile;
-        u32x4r cur[8];
-        if (PF) {
+        u32x4 cur[8];
+        if (!first) load_tile(t, v);
 #pragma unroll
-            for (int m = 0; m < 8; ++m) cur[m] = v[m];
-            if (t + stride < n_tiles) load_tile(t + stride, v);
-        } else {
-            if (!first) load_tile(t, v);
-#pragma unroll
-            for (int m = 0; m < 8; ++m) cur[m] = v[m];
-        }
-        if (LDST) {
-            u32x4r *wl = reinterpret_cast<u32x4r *>(zw - lane);  // the wave's 8 KiB slice
-#pragma unroll
-            for (int m = 0; m < 8; ++m) wl[64 * m + lane] = cur[m];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int m = 0; m < 8; ++m) cur[m] = wl[128 * win_in_tile + 16 * m + j];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
+        for (int m = 0; m < 8; ++m) cur[m] = v[m];
 
         f2 s1[K], s2[K];
 #pragma unroll
@@ -292,15 +221,12 @@ void residue_tile_kernel(GoertzelParams p)
                         if constexpr (DC != 4) c[e][0] = z04[e];
                         if constexpr (DC != 3) c[e][3] = z6[e];
                     }
-                } else if (ASM) {
+                } else {
 #pragma unroll
                     for (int e = 0; e < 2; ++e)
                         residue_classes_asm(f2{x[e][0], x[e][2]}, f2{x[e][4], x[e][6]},
                                             f2{x[e][1], x[e][3]}, f2{x[e][5], x[e][7]}, kk,
                                             c[e][0], c[e][1], c[e][2], c[e][3]);
-                } else {
-                    residue_classes(x[0], c[0][0], c[0][1], c[0][2], c[0][3]);
-                    residue_classes(x[1], c[1][0], c[1][1], c[1][2], c[1][3]);
                 }
                 if constexpr (DCLS) {
 #pragma unroll
@@ -342,8 +268,8 @@ void residue_tile_kernel(GoertzelParams p)
         float xr[K], xi[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const f4 c12 = ROTV ? rv[2 * k] : rot[(k * g + j) * 2];
-            const f4 c34 = ROTV ? rv[2 * k + 1] : rot[(k * g + j) * 2 + 1];
+            const f4 c12 = rot[(k * g + j) * 2];
+            const f4 c34 = rot[(k * g + j) * 2 + 1];
             f2 X = f2{c12.x, c12.y} * s1[k].x;
             X = __builtin_elementwise_fma(f2{c12.z, c12.w}, f2{s1[k].y, s1[k].y}, X);
             X = __builtin_elementwise_fma(f2{c34.x, c34.y}, f2{s2[k].x, s2[k].x}, X);
@@ -353,20 +279,17 @@ void residue_tile_kernel(GoertzelParams p)
         }
         const long long w = wbase + win_in_tile;
         const bool live = w < p.n_windows;
-        if constexpr (WS && LOG2G == 4) {
+        if constexpr (LOG2G == 4) {
             // Stage 2 of the ambiguity test and the in-kernel rescue both need
             // the raw samples, which only lived in registers: the tile is read
             // again (L2 / HBM), only by waves with a stage-1 flag, into the
             // wave's LDS slice (the class file is dead by now) in the linear
             // layout (window u's chunks at 128 u ..); lane j of a row sums
             // chunks 8 j .. 8 j + 7 of its window.
-            u32x4r *wl = reinterpret_cast<u32x4r *>(zw - lane);
+            u32x4 *wl = reinterpret_cast<u32x4 *>(zw - lane);
             auto efn = [&]() {
-                long long bytes = ((p.n_windows - wbase - 1) * p.hop + n) * 2;
-                if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-                __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                    (void *)(p.pcm + wbase * p.hop), (short)0, (int)bytes, 0x00020000);
-                u32x4r v2[8];
+                __amdgpu_buffer_rsrc_t rs = tile_rsrc(p, wbase, n);
+                u32x4 v2[8];
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
                     const int q = 64 * m + lane;
@@ -377,9 +300,7 @@ void residue_tile_kernel(GoertzelParams p)
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int m = 0; m < 8; ++m) wl[64 * m + lane] = v2[m];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_sync();
                 return row_sum16(seg_energy([&](int i) { return wl[128 * win_in_tile + 8 * j + i]; }));
             };
             const bool defer = K >= 2 && p.rescue_inline;
@@ -395,19 +316,18 @@ void residue_tile_kernel(GoertzelParams p)
             __builtin_amdgcn_wave_barrier();
             continue;
         }
-        static_assert(!DCLS || (WS && LOG2G == 4), "DCLS un-permutes in the window_sum epilogue");
         float P[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const float re = group_sum_r(xr[k], log2g);
-            const float im = group_sum_r(xi[k], log2g);
+            const float re = group_sum(xr[k], log2g);
+            const float im = group_sum(xi[k], log2g);
             P[k] = fmaf(re, re, im * im);
         }
         // stage 2: the lane's chunks again (L2 / HBM), only on flagged waves
         auto efn = [&]() {
-            u32x4r v2[8];
+            u32x4 v2[8];
             load_tile(t, v2);
-            return group_sum_r(seg_energy([&](int i) { return v2[i]; }), log2g);
+            return group_sum(seg_energy([&](int i) { return v2[i]; }), log2g);
         };
         bool amb;
         const int arg = chain_decide<K>(P, live, p.amb_tq, p.amb_floor, p.amb_t2e, efn, amb);
@@ -423,9 +343,9 @@ void residue_tile_kernel(GoertzelParams p)
     wb_burst(p.wb_bursts);
 }
 
-size_t residue_lds_bytes(int k, int log2g, int qp)
+size_t residue_lds_bytes(int k, int log2g)
 {
-    return ((size_t)k * (1u << log2g) * 2 + (size_t)kWavesPerBlock * 4 * qp * 64) * sizeof(f4);
+    return ((size_t)k * (1u << log2g) * 2 + (size_t)kWavesPerBlock * 4 * kResidueQP * 64) * sizeof(f4);
 }
 
 // DC (K = 8, 16 at n = 1024, host-permuted plans): mode 1 (K / 4 tones per
@@ -434,9 +354,7 @@ size_t residue_lds_bytes(int k, int log2g, int qp)
 template <int K, int DC, bool NT>
 static const void *residue_dc_kernel()
 {
-    return reinterpret_cast<const void *>(
-        &residue_tile_kernel<K, 4, kWavesPerBlock, true, false, (K <= 8 ? 4 : 0), kResidueQP, false,
-                             true, false, DC, NT>);
+    return reinterpret_cast<const void *>(&residue_tile_kernel<K, 4, DC, NT>);
 }
 
 template <int K, bool NT>
@@ -454,9 +372,7 @@ static const void *residue_kernel_for_t(int log2g, int dcls)
         }
         return residue_dc_kernel<K, 0, NT>();
     }
-    return reinterpret_cast<const void *>(
-        &residue_tile_kernel<K, -1, kWavesPerBlock, true, false, (K <= 8 ? 4 : 0), kResidueQP, false,
-                             true, false, 0, NT>);
+    return reinterpret_cast<const void *>(&residue_tile_kernel<K, -1, 0, NT>);
 }
 
 // nt: hop = n (each byte read once); overlapping windows keep their lines in L2
@@ -468,15 +384,7 @@ static const void *residue_kernel_for(int log2g, int dcls, bool nt)
 
 const void *residue_kernel_ptr(int k, int log2g, int dcls, bool nt)
 {
-    switch (k) {
-#define FSKD_CASE(K) case K: return residue_kernel_for<K>(log2g, dcls, nt);
-        FSKD_CASE(1) FSKD_CASE(2) FSKD_CASE(3) FSKD_CASE(4)
-        FSKD_CASE(5) FSKD_CASE(6) FSKD_CASE(7) FSKD_CASE(8)
-        FSKD_CASE(9) FSKD_CASE(10) FSKD_CASE(11) FSKD_CASE(12)
-        FSKD_CASE(13) FSKD_CASE(14) FSKD_CASE(15) FSKD_CASE(16)
-#undef FSKD_CASE
-    default: return nullptr;
-    }
+    return for_tone_count(k, [&](auto kc) { return residue_kernel_for<decltype(kc)::value>(log2g, dcls, nt); });
 }
 
 }  // namespace fskd

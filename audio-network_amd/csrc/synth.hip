@@ -99,8 +99,6 @@ hipError_t launch_synth(const SynthParams &p, hipStream_t s)
 
 namespace fskd {
 
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-
 // Read-only reference stream for bench.py (demod_read_ceiling_async): each
 // wave reads one contiguous 8 KiB tile with 8 coalesced 16 B/lane
 // non-temporal buffer loads and discards it, i.e. the tile kernels' access
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(64 * kPlainWPB) void read_ceiling_kernel(const int1
     unsigned acc = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const u32x4s v = __builtin_amdgcn_raw_buffer_load_b128(rs, (64 * i + lane) * 16, 0, 2);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (64 * i + lane) * 16, 0, 2);
         acc ^= v.x ^ v.y ^ v.z ^ v.w;
     }
     if (acc == 0x9E3779B9u) g_ceiling_sink[lane & 15] = acc;  // keeps the loads; practically never stores

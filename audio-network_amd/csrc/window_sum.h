@@ -53,11 +53,6 @@ __device__ __forceinline__ void mag_store(float *mag, long long idx, float v)
 }
 
 template <int CTRL>
-__device__ __forceinline__ float ws_dpp(float v)
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
 __device__ __forceinline__ unsigned ws_dpp_u(unsigned v)
 {
     return (unsigned)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
@@ -98,7 +93,7 @@ __device__ __forceinline__ void ws_stage(float (&v)[V], int lane)
     constexpr int VS = V > 16 ? 16 : V;  // values a 16-lane group can scatter
     if constexpr ((1 << B) >= VS) {
 #pragma unroll
-        for (int e = 0; e < V; ++e) v[e] += ws_dpp<C>(v[e]);
+        for (int e = 0; e < V; ++e) v[e] += dpp_f<C>(v[e]);
     } else {
 #pragma unroll
         for (int e = 0; e < V; ++e) {
@@ -106,7 +101,7 @@ __device__ __forceinline__ void ws_stage(float (&v)[V], int lane)
             const int f = e | (1 << B);
             const float keep = ws_sel<B>(v[e], v[f]);
             const float send = ws_sel<B>(v[f], v[e]);
-            v[e] = keep + ws_dpp<C>(send);
+            v[e] = keep + dpp_f<C>(send);
         }
     }
 }
@@ -241,11 +236,11 @@ __device__ __forceinline__ bool window_sum_decide(const float (&re)[K], const fl
     // rounding does not depend on the compiler's contraction (the error
     // bound and tests/fp32emu.py follow this operation sequence)
     float sq = v[0] * v[0];
-    const float P0 = __builtin_fmaf(v[0], v[0], ws_dpp<0xB1>(sq));
+    const float P0 = __builtin_fmaf(v[0], v[0], dpp_f<0xB1>(sq));
     float P1 = 0.f;
     if constexpr (V > 16) {
         sq = v[16] * v[16];
-        P1 = __builtin_fmaf(v[16], v[16], ws_dpp<0xB1>(sq));
+        P1 = __builtin_fmaf(v[16], v[16], dpp_f<0xB1>(sq));
     }
     const bool ok0 = re_lane && t0 < K;
     const bool ok1 = V > 16 && re_lane && t0 + 8 < K;
@@ -293,7 +288,7 @@ __device__ __forceinline__ bool window_sum_decide_split8(const float (&re)[4], c
     const bool re_lane = (j & 1) == 0;
     const int t0 = j >> 1;
     const float sq = v[0] * v[0];
-    const float P0 = __builtin_fmaf(v[0], v[0], ws_dpp<0xB1>(sq));  // as window_sum_decide
+    const float P0 = __builtin_fmaf(v[0], v[0], dpp_f<0xB1>(sq));  // as window_sum_decide
     const int o0 = PERM ? (int)((perm >> (4 * t0)) & 15u) : t0;
     float mx;
     const unsigned arg = ws_argmax_m<false>(__float_as_uint(P0), re_lane, o0, 0u, false, 0, mx);

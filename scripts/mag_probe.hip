@@ -40,8 +40,7 @@ using namespace fskd;
 template <int MST, int LAUX = -1>
 static const void *f16k()
 {
-    return reinterpret_cast<const void *>(
-        &fold_tile_kernel<8, 4, true, kPlainWPB, false, false, true, false, true, true, MST, LAUX>);
+    return reinterpret_cast<const void *>(&fold_tile_kernel<8, 4, true, true, MST, LAUX>);
 }
 
 struct Var {

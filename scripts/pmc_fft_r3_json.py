@@ -23,7 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def per_launch(path, spec):
-    key = "fft1024_quad_kernel<4, 4, 0, true" if spec else "fft1024_quad_kernel<4, 4, 0, false"
+    # fft1024_quad_kernel<SPEC, AUX, SPL, OVL, PICK> (csrc/fft_quad.hip)
+    key = "fft1024_quad_kernel<true" if spec else "fft1024_quad_kernel<false"
     vals, name = {}, None
     with open(path) as fh:
         for r in csv.DictReader(fh):

@@ -18,7 +18,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "fft1024_quad_kernel<4, 4, 0, true"
+KERNEL = "fft1024_quad_kernel<true"  # <SPEC, AUX, SPL, OVL, PICK> (csrc/fft_quad.hip)
 
 
 def per_launch(d, counter):

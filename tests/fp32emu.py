@@ -288,7 +288,7 @@ def exact_dft_mag(x, n, hop, W, omegas):
 
 
 # ---------------------------------------------------------------------------
-# fft_quad.hip (the shipped FUSED 4 kernel), operation for operation: complex
+# fft_quad.hip (the kernel's fused asm blocks), operation for operation: complex
 # values as (re, im) pairs of float32 arrays.
 
 def _c(re, im):
