@@ -47,7 +47,7 @@ static hipError_t upload(DevBuf<T> &b, const std::vector<T> &v)
 
 // The direct Goertzel-family kernels at n = 1024 (plain bank, fold, residue;
 // any hop without segment sharing) re-decide their flagged windows inside the
-// detector kernel (rescue_rows, demod_internal.h) from the tile they hold in
+// detector kernel (rescue_rows, rescue_rows.h) from the tile they hold in
 // LDS: no rescue launch. Segment-shared windows (SLIDE, fold_slide_kernel)
 // and other window lengths keep rescue_kernel's launch; the FFT detector
 // always rescues in its own kernel (rescue_fft.h).
@@ -312,7 +312,7 @@ constexpr size_t kBurstMinBytes = 4u << 20;   // smaller outputs: no bursts
 // only pay the extra launches there (2-FSK hop 128: 0.466 -> 0.494 ms), so
 // they stay one launch, as does the VALU-bound FFT detector.
 // Round 3: such a batch runs as ONE launch that writes each XCD's L2 back in
-// bursts of ~kBurstBytes of output (wb_burst, demod_internal.h): no drain and
+// bursts of ~kBurstBytes of output (wb_burst, kernel_ops.h): no drain and
 // ramp per slice (8-FSK 315-316 us against 331 us for the 4 slices and 337 us
 // for one plain launch on one box, 309-310 / 324 / 316 us on another;
 // scripts/mag_probe.hip wb). Batches from kBurstMinBytes up

@@ -1,10 +1,10 @@
-// demod_internal.h — shared between the C-ABI host layer and the kernels.
+// demod_internal.h — the contract between the C-ABI host layer and the
+// kernels: constants, parameter structs and launch declarations. No device
+// code (kernel_ops.h, rescue_ops.h, rescue_rows.h, lane_ops.h hold it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-
-#include "lane_ops.h"
 
 struct demod_acquire_result;  // include/demod.h
 
@@ -22,10 +22,10 @@ constexpr int kLdsSegStride = 144;    // bytes: 128 B segment + 16 B pad (confli
 constexpr int kLdsWaveBytes = 64 * kLdsSegStride;
 constexpr int kMaxTones = 16;
 constexpr int kFoldSlideSegs = 80;    // fold.hip fold_slide_kernel: segments per tile (10 KiB)
-constexpr int kMaxDevices = 64;
+constexpr int kMaxDevices = 64;       // device ordinals the module tables cover
 // the rescue's pass 0 by the fold (plan.h fold64) for fold plans up to this K
 // (above, its code cost the fold kernels an occupancy step: K = 14, 4 -> 3)
-constexpr int kFold64MaxK = 12;       // device ordinals the module tables cover
+constexpr int kFold64MaxK = 12;
 
 // Uniform per-launch parameters (kernarg -> SGPRs).
 struct GoertzelParams {
@@ -112,404 +112,6 @@ struct GoertzelParams {
 // square waves on the fold-slide path). Digital silence (zero energy) is
 // decided as a tie (tone 0) without a rescue, as the oracle's exact zeros are.
 constexpr uint8_t kSymAmbiguous = 0x80;
-
-// stage 1: margin within tau sqrt(Q P_max) (amb_tq = tau sqrt(Q)), or
-// P_max == 0 (a candidate: stage 2 asks for energy)
-__device__ __forceinline__ bool amb_margin(float p1, float p2, float tq, float fl)
-{
-    return tq > 0.f && (p1 == 0.f || p1 - p2 < tq * __builtin_amdgcn_sqrtf(p1) || p1 < fl);
-}
-
-// stage 2: (p1 - p2)^2 < t2e E p1, or p1 below the floor t2e E / 16, or p1 ==
-// 0 with E > 0
-__device__ __forceinline__ bool amb_energy(float p1, float p2, float e, float t2e)
-{
-    const float c = t2e * e, d = p1 - p2;
-    return p1 > 0.f ? (d * d < c * p1 || 16.f * p1 < c) : c > 0.f;
-}
-
-// The two stages over a wave: `amb1` is this lane's stage-1 verdict (false for
-// lanes without a real window); efn() returns the lane's row energy E and is
-// called by every lane (it may shuffle), only when some lane of the wave has
-// amb1 set (a wave-uniform branch: nothing is spent on unflagged waves).
-template <typename EFn>
-__device__ __forceinline__ bool amb_two_stage(bool amb1, float p1, float p2, float t2e, EFn efn)
-{
-    if (__ballot(amb1) == 0) return false;
-    const float e = efn();
-    return amb1 && amb_energy(p1, p2, e, t2e);
-}
-
-// Sequential argmax (ties to the lowest k) that also keeps the runner-up, for
-// the detectors' K-tone chains where every lane holds every P_k.
-template <int K>
-__device__ __forceinline__ int chain_argmax(const float (&P)[K], float &p1, float &p2)
-{
-    float best = -1.f, second = -1.f;
-    int arg = 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (P[k] > best) {
-            second = best;
-            best = P[k];
-            arg = k;
-        } else if (P[k] > second) {
-            second = P[k];
-        }
-    }
-    p1 = best;
-    p2 = second;
-    return arg;
-}
-
-// A chain decision (K >= 2 flags ambiguous windows): the argmax, and the
-// two-stage ambiguity verdict (stage 2 via efn, see amb_two_stage; `live` =
-// the lane's window exists).
-template <int K, typename EFn>
-__device__ __forceinline__ int chain_decide(const float (&P)[K], bool live, float tq, float fl, float t2e,
-                                            EFn efn, bool &amb)
-{
-    float p1, p2;
-    const int arg = chain_argmax<K>(P, p1, p2);
-    amb = K >= 2 && amb_two_stage(live && amb_margin(p1, p2, tq, fl), p1, p2, t2e, efn);
-    return arg;
-}
-
-// Sum of squares of the 64 int16 samples of one lane segment, 16-byte chunks
-// read by `chunk(i)` (i < 8), as fp32 (each square and partial sum rounded:
-// relative error < 100 u, covered by error_model.cpp's safety factor in
-// amb_t2e).
-template <typename Chunk>
-__device__ __forceinline__ float seg_energy(Chunk chunk)
-{
-    f2 a = {0.f, 0.f}, b = {0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const u32x4 d = chunk(i);
-        const unsigned d4[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f2 x = {(float)(int)(short)(d4[q] & 0xFFFFu), (float)((int)d4[q] >> 16)};
-            if (q & 1) b = __builtin_elementwise_fma(x, x, b);
-            else a = __builtin_elementwise_fma(x, x, a);
-        }
-    }
-    return (a.x + a.y) + (b.x + b.y);
-}
-
-// seg_energy's arithmetic, bit for bit, U chunks in flight at a time
-template <int U, typename Chunk>
-__device__ __forceinline__ float seg_energy_lowreg(Chunk chunk)
-{
-    f2 a = {0.f, 0.f}, b = {0.f, 0.f};
-#pragma unroll U
-    for (int i = 0; i < 8; ++i) {
-        const u32x4 d = chunk(i);
-        const unsigned d4[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f2 x = {(float)(int)(short)(d4[q] & 0xFFFFu), (float)((int)d4[q] >> 16)};
-            if (q & 1) b = __builtin_elementwise_fma(x, x, b);
-            else a = __builtin_elementwise_fma(x, x, a);
-        }
-    }
-    return (a.x + a.y) + (b.x + b.y);
-}
-
-// A serial sum one chunk at a time (4 VGPRs of samples live instead of 32:
-// for rare paths inside kernels at their VGPR limit)
-template <typename Chunk>
-__device__ __forceinline__ float seg_energy_serial(Chunk chunk)
-{
-    float e = 0.f;
-#pragma unroll 1
-    for (int i = 0; i < 8; ++i) {
-        const u32x4 d = chunk(i);
-        const unsigned d4[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const float x = (float)(short)((d4[q >> 1] >> (16 * (q & 1))) & 0xFFFFu);
-            e = __builtin_fmaf(x, x, e);
-        }
-    }
-    return e;
-}
-
-// Sum over the 16 lanes of a row (n = 1024 windows), every lane the same total.
-__device__ __forceinline__ float row_sum16(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));
-    v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-
-// The same tree in double (the rescue's pass 0): each stage's partner by DPP
-// (two 32-bit moves) instead of __shfl_xor's ds_bpermute round trips through
-// the LDS crossbar. Bit-identical to the xor butterfly: after each stage the
-// lanes of a group hold one value (a + b == b + a), so any lane of the
-// partner group is the partner.
-template <int C>
-__device__ __forceinline__ double dpp_d(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)b, C, 0xF, 0xF, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(b >> 32), C, 0xF, 0xF, true);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-__device__ __forceinline__ double row_sum16d(double v)
-{
-    v += dpp_d<0xB1>(v);
-    v += dpp_d<0x4E>(v);
-    v += dpp_d<0x141>(v);
-    v += dpp_d<0x140>(v);
-    return v;
-}
-
-// Tile-group index of this block. Blocks are dealt round-robin to the 8 XCDs
-// (MI355X_MICROARCH.md §Workgroup dispatch), so with the swizzle each XCD
-// walks one contiguous 1/8 of the tiles and every output line is written by a
-// single XCD's L2. Placement only affects speed, never correctness.
-__device__ __forceinline__ long long tile_block(int swz)
-{
-    const long long b = blockIdx.x, nb = gridDim.x;
-    if (!swz) return b;
-    const long long per = nb / 8, full = per * 8;
-    if (b >= full) return b;
-    return (b % 8) * per + b / 8;
-}
-
-// Write-back bursts (round 3), at the end of a Goertzel-family
-// tile kernel. A batch whose outputs are more than the XCDs' L2s hold dirty
-// (8-FSK: 33 MiB) runs as one launch in which the last block of every
-// 1/wb_bursts of an XCD's swizzled blocks (its wave 0, after its stores)
-// writes that XCD's L2 back with an agent-scope release, so the output lines
-// leave in a few bursts instead of trickling out between the input's reads;
-// the launch slices this replaces paid a drain and a ramp per slice.
-// In-kernel decision rescue of a wave's flagged windows, each by its 16-lane
-// row (n = 1024; round 3 for the 2-FSK plain bank, round 4 every direct
-// Goertzel-family kernel at n = 1024). Two passes of one loop (one copy of
-// the code, so the detector's VGPR budget pays for one):
-//  pass 0 (round 4, when t2e64 > 0): the row's K powers in double, computed
-//    the way the fp32 plain bank computes them — lane seg runs every tone's
-//    recurrence over its own 64 samples, rotates its end state into the
-//    window's phase (rot64) and the row sums — K x 64 double steps per lane
-//    on all 16 lanes, instead of one 1024-step chain per tone on K lanes
-//    (~10x fewer wave instructions at K = 2). These powers are not the
-//    oracle's bits, but |sqrt P_0 - sigma P_ref| <= rho_first sqrt(E) (its own
-//    rounding and the oracle's, derived by error_model.cpp from both
-//    operation sequences; checked by tests/test_rescue_model64.py), so where
-//    their top-2 margin satisfies margin^2 >= t2e64 E P_max (t2e64 = 16
-//    rho_first^2) the argmax is the oracle's and the row is decided here (its
-//    magnitudes: these powers rounded to fp32, within the bound of the
-//    oracle's). Rows inside that band (exact ties; margins within ~1e-10 of
-//    P_max) go on to
-//  pass 1: lane seg < K runs tone seg's recurrence in double over the
-//    window's 1024 samples with exactly rescue_kernel's operations and order
-//    (so exactly oracle/fsk_oracle.c's: contraction off); the row's argmax
-//    (ties to the lowest tone) replaces the symbol, and the powers (rounded
-//    to fp32) the magnitudes, bit-identical to the oracle's.
-// chunk(q) returns the window's 16-byte chunk q (samples 8q .. 8q + 7) from
-// wherever the kernel holds the tile (its LDS slice: no global round trip).
-// Every lane of the wave calls it (the shuffles); rows with amb_row false
-// change nothing. The detector leaves the symbol and magnitudes of a flagged
-// row to this function (no second store).
-// Pass 0 by the fold (FOLD: fold detector plans, every tone on a multiple of
-// 8 bins; round 5): lane seg sums the window's samples
-// 128 m + 8 seg + i over m < 8 (exact integers: the folded samples 8 seg ..
-// 8 seg + 7 of the window folded to 128), then per tone an 8-step double
-// chain at the exact bin, the rotation (rot64: the fold tables, plan.h
-// fold64), the row sum and the power; the margin test as pass 0 above (t2e64
-// derived for this sequence, error_model.cpp first_pass_fold_rho). 8x fewer
-// double steps than 64 raw samples per lane per tone. Returns amb_row after
-// it (the rows left to the exact chains).
-// x_lo^2 + x_hi^2 of 4 dwords (8 int16 samples): exact per dword by
-// v_dot2_i32_i16 (clamped, only (-32768, -32768) saturates, to 2^31 - 1),
-// converted and summed in fp32 (pass 0's energy: error_model.cpp allows E
-// 100 u, this is < 36 u over a lane's 64 samples)
-typedef short i16x2_dot __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float dot_energy4(const unsigned (&d4)[4])
-{
-    float e = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const i16x2_dot s = __builtin_bit_cast(i16x2_dot, d4[c]);
-        e += (float)__builtin_amdgcn_sdot2(s, s, 0, true);
-    }
-    return e;
-}
-
-template <int K, typename Chunk>
-__device__ __forceinline__ bool rescue_rows_fold0(const GoertzelParams &p, long long w, int seg,
-                                                  bool amb_row, Chunk chunk)
-{
-#pragma clang fp contract(off)
-    // opaque here: no address built from seg is hoisted into the detector's
-    // loop (where it would hold VGPRs across every tile)
-    asm volatile("" : "+v"(seg));
-    int xf[8];
-    float e = 0.f;  // the lane's 64 raw samples' sum x^2 (any partition of the window)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) xf[i] = 0;
-#pragma unroll 1
-    for (int m = 0; m < 8; ++m) {
-        const u32x4 d = chunk(16 * m + seg);
-        const unsigned d4[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xf[i] += (int)(short)((d4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
-        e += dot_energy4(d4);
-    }
-    double best = -1.0, second = -1.0;
-    int arg = 0;
-#pragma unroll 1
-    for (int k = 0; k < K; ++k) {
-        int ci = 64 * K + k;
-        asm volatile("" : "+v"(ci));  // a vector load (as scalar, SGPR spills at large K)
-        const double c = p.rot64[ci];
-        double s1 = 0.0, s2 = 0.0;
-        // each sample converted at its step (scheduled together, the 8
-        // doubles raised the fold kernels' VGPR peak)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            double s = (double)xf[i] + c * s1;
-            s = s - s2;
-            s2 = s1;
-            s1 = s;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const double2 A = *reinterpret_cast<const double2 *>(p.rot64 + 4 * (k * 16 + seg));
-        const double2 B = *reinterpret_cast<const double2 *>(p.rot64 + 4 * (k * 16 + seg) + 2);
-        double re = A.x * s1, im = A.y * s1;
-        re = re - B.x * s2;
-        im = im - B.y * s2;
-        re = row_sum16d(re);
-        im = row_sum16d(im);
-        const double pk = re * re + im * im;
-        if (pk > best) {
-            second = best;
-            best = pk;
-            arg = k;
-        } else if (pk > second) {
-            second = pk;
-        }
-        if (k == seg && amb_row && p.mag) p.mag[w * K + seg] = (float)pk;
-    }
-    const double cth = p.t2e64 * (double)row_sum16(e), dm = best - second;
-    const bool still = !(best > 0.0) || dm * dm < cth * best || 16.0 * best < cth;
-    if (amb_row && !still && seg == 0) p.sym[w] = (uint8_t)arg;
-    return amb_row && still;
-}
-
-// FOLD: 0 = pass 0 by segments, 1 = by the fold (fold kernels), 2 = as the
-// plan says at run time (p.fold64: plain-bank plans on multiples of 8 bins)
-template <int K, int FOLD = 0, typename Chunk>
-__device__ __forceinline__ void rescue_rows(const GoertzelParams &p, long long w, int seg, int lane,
-                                            bool amb_row, Chunk chunk)
-{
-#pragma clang fp contract(off)
-    int first = p.t2e64 > 0.0 ? 0 : 1;
-    if constexpr (FOLD != 0) {
-        if (first == 0 && (FOLD == 1 || p.fold64)) {
-            amb_row = rescue_rows_fold0<K>(p, w, seg, amb_row, chunk);
-            if (__ballot(amb_row) == 0) return;
-            first = 1;
-        }
-    }
-#pragma unroll 1
-    for (int pass = first; pass < 2; ++pass) {
-        const bool exact = pass == 1;
-        const bool run = exact ? amb_row && seg < K : true;  // lanes that run chains
-        const int q0 = exact ? 0 : 8 * seg, q1 = exact ? 128 : 8 * seg + 8;
-        double best = -1.0, second = -1.0, mine = 0.0;
-        float e = 0.f;  // pass 0: the lane's sum x^2
-        int arg = 0;
-#pragma unroll 1
-        for (int t = 0; t < (exact ? 1 : K); ++t) {
-            const int k = exact ? seg : t;
-            // pass 0's coefficient, or the oracle's rcoef[k] (exact), per lane
-            const double c = p.rot64[(exact ? 65 : 64) * K + (k < K ? k : 0)];
-            double s1 = 0.0, s2 = 0.0;
-            if (run) {
-#pragma unroll 1
-                for (int q = q0; q < q1; ++q) {
-                    const u32x4 d = chunk(q);
-                    const unsigned d4[4] = {d.x, d.y, d.z, d.w};
-                    if (!exact && t == 0) e += dot_energy4(d4);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const double x = (double)(short)((d4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
-                        double s = x + c * s1;
-                        s = s - s2;
-                        s2 = s1;
-                        s1 = s;
-                    }
-                }
-            }
-            if (exact) {
-                const double a = s1 * s1 + s2 * s2;
-                const double b = c * s1;
-                mine = run ? a - b * s2 : 0.0;
-            } else {
-                // the rotation's loads after the chain (an offset that depends
-                // on its result): hoisted above it they hold 8 VGPRs through it
-                // (and B's after A's products: 4 VGPRs of table live at a time)
-                int ro = 4 * (k * 16 + seg);
-                asm volatile("" : "+v"(ro) : "v"(s1));
-                const double2 A = *reinterpret_cast<const double2 *>(p.rot64 + ro);
-                double re = A.x * s1, im = A.y * s1;
-                asm volatile("" : "+v"(ro) : "v"(re), "v"(im));
-                const double2 B = *reinterpret_cast<const double2 *>(p.rot64 + ro + 2);
-                re = re - B.x * s2;
-                im = im - B.y * s2;
-                re = row_sum16d(re);
-                im = row_sum16d(im);
-                const double pk = re * re + im * im;
-                if (pk > best) {
-                    second = best;
-                    best = pk;
-                    arg = k;
-                } else if (pk > second) {
-                    second = pk;
-                }
-                // the row's magnitudes now (pass 1 rewrites those of the rows
-                // it takes over): no register holds them across the loop
-                if (k == seg && amb_row && p.mag) p.mag[w * K + seg] = (float)pk;
-            }
-        }
-        bool still = false;
-        if (exact) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const double pk = __shfl(mine, (lane & 48) + k);
-                if (pk > best) {
-                    best = pk;
-                    arg = k;
-                }
-            }
-        } else {
-            // stage threshold^2 = t2e64 E P_max, E the row's sum x^2 (fp32,
-            // within 1e-5: the host's t2e64 carries (1 + 1e-3))
-            const double cth = p.t2e64 * (double)row_sum16(e), dm = best - second;
-            still = !(best > 0.0) || dm * dm < cth * best || 16.0 * best < cth;
-        }
-        if (amb_row && !still) {
-            if (seg == 0) p.sym[w] = (uint8_t)arg;
-            if (exact && p.mag && seg < K) p.mag[w * K + seg] = (float)mine;
-        }
-        amb_row = amb_row && still;
-        if (__ballot(amb_row) == 0) break;
-    }
-}
-
-__device__ __forceinline__ void wb_burst(int wb_bursts)
-{
-    if (wb_bursts <= 0 || threadIdx.x >= 64) return;
-    const long long b = blockIdx.x, per = gridDim.x / 8, seg = per / wb_bursts;
-    if (seg > 0 && b < per * 8 && (b / 8) % seg == seg - 1)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-}
 
 // Full-spectrum detector (fft.hip), n = 1024.
 struct FftParams {

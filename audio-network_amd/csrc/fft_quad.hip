@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "demod_internal.h"
+#include "kernel_ops.h"
 #include "rescue_fft.h"
 #include "window_sum.h"
 

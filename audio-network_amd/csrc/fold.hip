@@ -18,6 +18,8 @@
 // VALU per sample drops from ~(1 + 2K) to ~(1 + 2K/8 + epilogue), which makes
 // 8-FSK HBM-bound.
 #include "demod_internal.h"
+#include "kernel_ops.h"
+#include "rescue_rows.h"
 #include "window_sum.h"
 
 namespace fskd {
@@ -27,7 +29,7 @@ namespace fskd {
 // row is a candidate only if the window itself is not digital silence:
 // rawfn() (called by every lane, only when some live row of the wave has E_f
 // == 0) returns the raw window's sum x^2, which the P_max == 0 test of
-// demod_internal.h amb_energy then reads (> 0: ambiguous). A window with
+// kernel_ops.h amb_energy then reads (> 0: ambiguous). A window with
 // E_f > 0 has raw energy too, so only its threshold scale matters.
 // Round 5: the threshold carries the double oracle's own error too, which
 // scales with the raw window (error_model.cpp): E_eff = (sqrt(E_f) + d)^2,

@@ -23,6 +23,8 @@
 // 64-sample chains keep the fp32 error <= ~3e-6 of max_k P (a single
 // 1024-sample chain reaches ~2e-5, over the 1e-5 bar).
 #include "demod_internal.h"
+#include "kernel_ops.h"
+#include "rescue_rows.h"
 
 #ifndef FSKD_SLIDE_EU
 #define FSKD_SLIDE_EU 4
@@ -315,7 +317,7 @@ __global__ __launch_bounds__(64 * kPlainWPB) void goertzel_tile_kernel(GoertzelP
         }
         const long long w = tt * wins_per_tile + win_in_tile;
         const bool live = w < p.n_windows;
-        // stage 2 of the ambiguity test (demod_internal.h): this lane's 64
+        // stage 2 of the ambiguity test (kernel_ops.h): this lane's 64
         // samples again (the tile is still in the wave's LDS slice), summed
         // over the window's lanes
         auto efn = [&]() {
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(64 * kPlainWPB) void goertzel_tile_kernel(GoertzelP
             }
         }
         if constexpr (kInline) {
-            // decision rescue in the kernel (demod_internal.h rescue_rows); every
+            // decision rescue in the kernel (rescue_rows.h rescue_rows); every
             // lane of a row holds the same all-reduced powers, so the same verdict
             if (defer && __ballot(amb && live) != 0) rescue_rows<K, (K <= 2 ? 2 : 0)>(p, w, seg, lane, amb && live, chunk);
         }

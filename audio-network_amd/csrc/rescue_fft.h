@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "demod_internal.h"
+#include "rescue_ops.h"
 
 namespace fskd {
 
@@ -176,7 +177,7 @@ __device__ __attribute__((always_inline)) inline void rescue_fft_window(const in
 }
 
 // The FFT rescue's first pass (round 4, tones only): the
-// Goertzel family's pass 0 (demod_internal.h rescue_rows) for the four
+// Goertzel family's pass 0 (rescue_rows.h rescue_rows) for the four
 // windows of a flagged group, one per 16-lane row as the detector holds them:
 // lane seg runs each tone bin's recurrence in double over its own 64 samples
 // (read once from global memory / L2 into 32 VGPRs: the group loop's
@@ -206,18 +207,21 @@ __device__ __forceinline__ bool rescue_fft_seg(const int16_t *__restrict__ x, co
         int a = 0;
         if (fold) {
 #pragma unroll
-            for (int m = 0; m < 8; ++m) a += (int)(short)((v[4 * m + (i >> 1)] >> (16 * (i & 1))) & 0xFFFFu);
+            for (int m = 0; m < 8; ++m) a += (int)sample16(v[4 * m + (i >> 1)], i & 1);
         }
         xf[i] = a;
     }
     float e = 0.f;
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
-        const float xf = (float)(short)((v[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+        const float xf = (float)sample16(v[i >> 1], i & 1);
         e = __builtin_fmaf(xf, xf, e);
     }
     double best = -1.0, second = -1.0, mine = 0.0;
     int arg = 0;
+    // (the tone loop and the margin test restate rescue_ops.h chain_step_d,
+    // pass0_head, top2_update and pass0_still inline: through the helpers
+    // fft_quad.hip's machine code changes)
 #pragma unroll 1
     for (int t = 0; t < k; ++t) {
         const double c = rot64[64 * k + t];
@@ -233,7 +237,7 @@ __device__ __forceinline__ bool rescue_fft_seg(const int16_t *__restrict__ x, co
         } else {
 #pragma unroll
             for (int i = 0; i < 64; ++i) {
-                const double xd = (double)(short)((v[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+                const double xd = (double)sample16(v[i >> 1], i & 1);
                 double s = xd + c * s1;
                 s = s - s2;
                 s2 = s1;

@@ -36,6 +36,8 @@
 // folds them. VALU per sample ~ 2.3 for the butterflies + K/4 for the
 // recurrences (vs ~ 1 + K for the plain bank), so K = 8 stays HBM-bound.
 #include "demod_internal.h"
+#include "kernel_ops.h"
+#include "rescue_rows.h"
 #include "window_sum.h"
 
 namespace fskd {

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "demod_internal.h"
+#include "kernel_ops.h"
 
 namespace fskd {
 

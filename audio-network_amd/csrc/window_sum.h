@@ -25,6 +25,7 @@
 // higher one was strictly larger.)
 #pragma once
 #include "demod_internal.h"
+#include "kernel_ops.h"
 
 namespace fskd {
 
@@ -139,7 +140,7 @@ __device__ __forceinline__ unsigned ws_argmax(unsigned pb0, bool ok0, int o0, un
     return ws_argmax_m<TWO>(pb0, ok0, o0, pb1, ok1, o1, mx);
 }
 
-// Decision-rescue test over a row (demod_internal.h
+// Decision-rescue test over a row (kernel_ops.h
 // amb_margin): the window is ambiguous when a second tone's power lies within
 // the threshold of the row's max mx (the max's own lane counts once), or mx is
 // below the floor; mx == 0 is a stage-1 candidate and ambiguous in stage 2
@@ -176,7 +177,7 @@ __device__ __forceinline__ bool ws_ambiguous(float mx, float a0, bool ok0, float
     return ws_ambiguous_t(mx, a0, ok0, a1, ok1, tq * tq, fl);
 }
 
-// Both stages over the wave (demod_internal.h amb_two_stage): stage 1 with
+// Both stages over the wave (kernel_ops.h amb_two_stage): stage 1 with
 // the int16 worst case, stage 2 only if some live row of the wave is flagged
 // (efn: the row energy, called by every lane). Row-uniform result.
 template <typename EFn>

@@ -17,6 +17,11 @@ is normalised (comments stripped, every mangled symbol `_Z...` replaced by one
 placeholder, the function index removed from local labels) and hashed. The two
 multisets of hashes are compared per unit. Exit status 0: equal everywhere.
 
+For every function that is not identical and has a namesake on the other side,
+a second line says whether the normalised lines are equal as a multiset
+("reordered": the same instructions in another order), the line count before
+and after, and the kernel descriptor's register, LDS and scratch fields.
+
 A refactor that renames or drops template parameters changes every mangled
 name and nothing else; this tool proves the "nothing else". It hashes text and
 looks for no particular instruction.
@@ -31,7 +36,8 @@ import subprocess
 import sys
 import tempfile
 
-UNITS = ["goertzel", "fold", "residue", "fft_quad", "rescue", "synth"]
+UNITS = ["goertzel", "fold", "residue", "fft_quad", "rescue", "synth", "acquire", "acquire_segments",
+         "frame_gpu"]
 CSRC = os.path.join("audio-network_amd", "csrc")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,6 +46,7 @@ FUNC_START = re.compile(r"^\s*\.type\s+(\S+),@function")
 TAIL_START = re.compile(r"^\s*(\.type\s+\S+,@object|\.amdgpu_metadata|\.ident|\.amdgpu_lds)\b")
 MANGLED = re.compile(r"_Z[A-Za-z0-9_.$]+")
 LOCAL_LABEL = re.compile(r"\.L([A-Za-z_]+?)\d+(_\d+)?\b")
+DESCRIPTOR = ("next_free_vgpr", "next_free_sgpr", "group_segment_fixed_size", "private_segment_fixed_size")
 
 
 def compile_command(csrc):
@@ -65,7 +72,7 @@ def normalise(line):
 
 
 def functions(path):
-    """name -> hash of the normalised body (code + descriptor), one per function."""
+    """name -> (hash, lines) of the normalised body (code + descriptor), one per function."""
     bodies, name, cur = {}, None, []
     with open(path) as f:
         for raw in f:
@@ -80,7 +87,17 @@ def functions(path):
                     cur.append(line)
     if name:
         bodies[name] = cur
-    return {n: hashlib.sha256("\n".join(b).encode()).hexdigest() for n, b in bodies.items()}
+    return {n: (hashlib.sha256("\n".join(b).encode()).hexdigest(), b) for n, b in bodies.items()}
+
+
+def descriptor(lines):
+    """The DESCRIPTOR fields of a function's .amdhsa_ block, as 'v/s/lds/scratch'."""
+    got = {}
+    for line in lines:
+        for key in DESCRIPTOR:
+            if line.startswith(".amdhsa_" + key + " "):
+                got[key] = line.split()[1]
+    return "/".join(got.get(key, "-") for key in DESCRIPTOR)
 
 
 def materialise(arg, stack):
@@ -130,15 +147,22 @@ def main():
         for unit in args.units:
             fa = functions(os.path.join(asm["before"], unit + ".s"))
             fb = functions(os.path.join(asm["after"], unit + ".s"))
-            ca, cb = collections.Counter(fa.values()), collections.Counter(fb.values())
+            ca = collections.Counter(h for h, _ in fa.values())
+            cb = collections.Counter(h for h, _ in fb.values())
             same = ca == cb
             differ |= not same
             print(f"{unit}: {len(fa)} functions before ({len(ca)} distinct), {len(fb)} after "
                   f"({len(cb)} distinct): {'equal' if same else 'DIFFERENT'}")
             for side, names, only in (("before", fa, ca - cb), ("after", fb, cb - ca)):
-                for name, h in sorted(names.items()):
+                for name, (h, _) in sorted(names.items()):
                     if h in only:
                         print(f"  only {side}: {h[:12]} {name}")
+            for name in sorted(set(fa) & set(fb)):
+                (ha, la), (hb, lb) = fa[name], fb[name]
+                if ha != hb:
+                    kind = "reordered" if collections.Counter(la) == collections.Counter(lb) else "changed"
+                    print(f"  {kind}: {name}: lines {len(la)} -> {len(lb)}, "
+                          f"vgpr/sgpr/lds/scratch {descriptor(la)} -> {descriptor(lb)}")
         print("machine code: " + ("DIFFERENT" if differ else "identical"))
         return 1 if differ else 0
 

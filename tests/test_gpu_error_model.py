@@ -92,7 +92,7 @@ def test_rescue_launch_equals_in_kernel_rescue(A, O, torch, monkeypatch, plan, h
     """The rescue launch of segment-shared windows (rescue.hip
     rescue_seg_kernel: pass 0 by shared segment states in dense runs, per
     window otherwise, by the fold for fold plans; then the exact chain) runs
-    the in-kernel rescue's arithmetic (demod_internal.h rescue_rows), so on
+    the in-kernel rescue's arithmetic (rescue_rows.h rescue_rows), so on
     two tones at equal power (every window flagged and rescued) every
     segment-shared window that starts at a multiple of n carries the same
     symbol and magnitude bits as the direct kernel's window at hop = n, with

@@ -1,4 +1,4 @@
-"""The in-kernel rescue's first pass (demod_internal.h rescue_rows, pass 0),
+"""The in-kernel rescue's first pass (rescue_rows.h rescue_rows, pass 0),
 its derived error bound checked on the CPU.
 
 Pass 0 re-computes a flagged window's K tone powers in double the way the
@@ -158,7 +158,7 @@ def test_fft_pass0_error_model(A, O, plan):
 
 
 # fold detector plans (every tone on a multiple of 8 bins; plan.h fold64):
-# pass 0 by the fold (demod_internal.h rescue_rows_fold0, rescue.hip
+# pass 0 by the fold (rescue_rows.h rescue_rows_fold0, rescue.hip
 # rescue_seg_kernel), including the DC and Nyquist bins
 FOLD_PLANS = {
     "fsk8": (tuple(1500.0 + 375.0 * i for i in range(8)), "AUTO"),
