@@ -162,6 +162,34 @@ def acquire_result_dict(r: "DemodAcquireResult") -> dict:
     return out
 
 
+class DemodFrameHit(ctypes.Structure):
+    """demod_frame_hit_t (include/demod.h): one sync-word hit of a frame scan."""
+    _fields_ = [("window", ctypes.c_uint64), ("errors", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class DemodFramesResult(ctypes.Structure):
+    """demod_frames_result_t (include/demod.h): the phase decision as
+    DemodAcquireResult, the hit counts and the incomplete hit at the batch's end."""
+    _fields_ = [
+        ("metric", ctypes.c_double * DEMOD_MAX_PHASES),
+        ("phases", ctypes.c_uint32), ("phase", ctypes.c_uint32),
+        ("per_phase", ctypes.c_uint64),
+        ("n_hits", ctypes.c_uint64), ("n_written", ctypes.c_uint64),
+        ("tail_window", ctypes.c_int64),
+        ("tail_errors", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+
+FRAME_HIT_DTYPE = np.dtype([("window", "<u8"), ("errors", "<u4"), ("reserved", "<u4")])   # DemodFrameHit
+
+
+def frames_result_dict(r: "DemodFramesResult") -> dict:
+    """The fields of a DemodFramesResult; `metric` as float64 [phases]."""
+    out = {f: int(getattr(r, f)) for f, _ in DemodFramesResult._fields_ if f != "metric"}
+    out["metric"] = np.array(r.metric[:r.phases], np.float64)
+    return out
+
+
 class DemodError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -229,6 +257,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                   _P, _SZ, _P]),
         "demod_segments_layout": (ctypes.c_int, [ctypes.POINTER(DemodCfg), _SZ, _P, _P, _P,
                                                  ctypes.POINTER(_SZ)]),
+        "demod_frames_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), _SZ]),
+        "demod_frames_async": (ctypes.c_int, [_P, _P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _SZ, _P, _P,
+                                              _P, _SZ, _P, _P, _SZ, _P]),
+        "demod_frames": (ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _SZ, _P, _P, _P, _SZ,
+                                        ctypes.POINTER(DemodFramesResult)]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -392,6 +425,19 @@ def acquire_segments_workspace_size(cfg: DemodCfg, max_segments: int, max_window
                                                                    int(max_windows)))
     if size == 0:
         raise DemodError(DEMOD_BAD_ARG, "demod_acquire_segments_workspace_size")
+    return size
+
+
+def frames_workspace_size(cfg: DemodCfg, max_windows: int) -> int:
+    """demod_frames_workspace_size: bytes of d_work a frame scan of up to
+    max_windows windows needs (no GPU); monotone in max_windows. Raises
+    DemodError(DEMOD_BAD_ARG) where it is 0 (no acquisition for cfg,
+    max_windows >= 2^31)."""
+    if max_windows < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_frames_workspace_size")
+    size = int(load_library().demod_frames_workspace_size(ctypes.byref(cfg), int(max_windows)))
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_frames_workspace_size")
     return size
 
 
@@ -751,6 +797,90 @@ class Demodulator:
             stream or None)
         if rc < 0:
             raise DemodError(rc, "demod_acquire_segments_async")
+
+    def frames(self, pcm, sync, max_errors: int = 0, frame_symbols: int = 0,
+               max_frames: Optional[int] = None, n_windows: Optional[int] = None,
+               payload: bool = True, packed: bool = True):
+        """demod_frames: the detector over the sliding windows of pcm (a host
+        int16 array or a device tensor), then every sync-word hit on the
+        acquired phase with its frame_symbols payload symbols. Returns (hits: a
+        FRAME_HIT_DTYPE array [n_written], payload uint8 [n_written][N] or None,
+        packed uint8 [n_written][ceil(N bits / 8)] or None, result dict).
+        Overlapping hits are all listed (include/demod.h "frame scan")."""
+        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
+        if host:
+            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+            size = flat.size
+        else:
+            size = int(pcm.numel())
+        if n_windows is None:
+            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
+        n_windows = int(n_windows)
+        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
+        if host:
+            if need > size:
+                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
+            buf = flat
+            if flat.ctypes.data % 16:
+                buf = np.empty(flat.size + 8, dtype=np.int16)
+                off = (-buf.ctypes.data % 16) // 2
+                buf = buf[off:off + flat.size]
+                buf[:] = flat
+        else:
+            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
+            buf = pcm
+        sync = _sync_bytes(sync)
+        N = int(frame_symbols)
+        if N < 0 or (max_frames is not None and max_frames < 0):
+            raise DemodError(DEMOD_BAD_ARG, "frame_symbols or max_frames < 0")
+        if max_frames is None:
+            max_frames = n_windows // max(self.n // self.hop, 1) + 1
+        cap = int(max_frames)
+        B = (N * bits_per_symbol(self.k) + 7) // 8
+        hits = np.zeros(max(cap, 1), dtype=FRAME_HIT_DTYPE)
+        pay = np.empty((max(cap, 1), N), dtype=np.uint8) if payload and N else None
+        pak = np.empty((max(cap, 1), B), dtype=np.uint8) if packed and N else None
+        res = DemodFramesResult()
+        rc = self._lib.demod_frames(self._h, _ptr(buf), n_windows, _ptr(sync) if sync.size else None,
+                                    sync.size, int(max_errors), N, _ptr(hits) if cap else None,
+                                    _ptr(pay) if pay is not None else None,
+                                    _ptr(pak) if pak is not None else None, cap, ctypes.byref(res))
+        if rc < 0:
+            raise DemodError(rc, "demod_frames")
+        return (hits[:rc], pay[:rc] if pay is not None else None,
+                pak[:rc] if pak is not None else None, frames_result_dict(res))
+
+    def frames_async(self, d_sym, d_mag, n_windows: int, sync, max_errors: int, frame_symbols: int,
+                     d_hits, d_payload, d_packed, max_frames: int, d_result, d_work,
+                     stream: int = 0) -> None:
+        """demod_frames_async on a batch's device outputs. d_hits (uint8,
+        max_frames * sizeof(DemodFrameHit) bytes; None with max_frames 0),
+        d_payload (uint8, max_frames * frame_symbols bytes, or None), d_packed
+        (uint8, max_frames * ceil(frame_symbols * bits / 8) bytes, or None),
+        d_result (uint8, sizeof(DemodFramesResult) bytes) and d_work (uint8, at
+        least frames_workspace_size(cfg, n_windows) bytes) are device tensors,
+        checked like the batch calls' (dtype, contiguity, device, size)."""
+        n_windows, N, cap = int(n_windows), int(frame_symbols), int(max_frames)
+        if n_windows < 0 or N < 0 or cap < 0:
+            raise DemodError(DEMOD_BAD_ARG, "n_windows, frame_symbols or max_frames < 0")
+        dev = int(self.cfg.device)
+        B = (N * bits_per_symbol(self.k) + 7) // 8
+        _check_dev(d_sym, "d_sym", "uint8", max(n_windows, 1), dev)
+        _check_dev(d_mag, "d_mag", "float32", max(n_windows, 1) * self.k, dev)
+        _check_dev(d_hits, "d_hits", "uint8", cap * ctypes.sizeof(DemodFrameHit), dev)
+        _check_dev(d_payload, "d_payload", "uint8", cap * N, dev, nullable=True)
+        _check_dev(d_packed, "d_packed", "uint8", cap * B, dev, nullable=True)
+        _check_dev(d_result, "d_result", "uint8", ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_work, "d_work", "uint8", frames_workspace_size(self.cfg, n_windows), dev)
+        sync = _sync_bytes(sync)
+        rc = self._lib.demod_frames_async(
+            self._h, _ptr(d_sym), _ptr(d_mag), n_windows, _ptr(sync) if sync.size else None, sync.size,
+            int(max_errors), N, _ptr(d_hits) if d_hits is not None else None,
+            _ptr(d_payload) if d_payload is not None else None,
+            _ptr(d_packed) if d_packed is not None else None, cap, _ptr(d_result), _ptr(d_work),
+            int(d_work.numel()), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_async")
 
 
 class Streams:

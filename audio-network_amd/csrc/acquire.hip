@@ -4,7 +4,8 @@
 // Inputs: sym[W] and P[W][K] of W sliding windows (window w at sample w hop),
 // R = n / hop phases. Three launches on the caller's stream:
 //
-//  scan      a fixed-size grid walks tiles of kAcqTile windows (block b takes
+//  scan      (its body is acquire_scan.h's, which acquire_frames.hip runs too)
+//            a fixed-size grid walks tiles of kAcqTile windows (block b takes
 //            tiles b, b + grid, ..). Thread t owns the tile's windows t + 256 i:
 //            256 and the tile are multiples of R (a power of two, as n and hop
 //            are), so every window a thread ever sees is on phase t mod R and
@@ -26,81 +27,31 @@
 //            the blocks, and every byte of *d_result.
 //  gather    out[j] = sym[first_window + j R], j < n_written, both read from
 //            *d_result (skipped when cap == 0).
-#include "../../include/demod.h"
-#include "demod_internal.h"
+#include "acquire_scan.h"
 
 namespace fskd {
 
-constexpr int kAcqThreads = 256;
-constexpr int kAcqPerThread = kAcqTile / kAcqThreads;
-constexpr int kAcqHalo = (DEMOD_MAX_SYNC - 1) * DEMOD_MAX_PHASES;
-constexpr unsigned long long kAcqNone = ~0ull;
+static __device__ __forceinline__ AcqScanArgs scan_args(const AcquireParams &p)
+{
+    return {p.sym, p.mag, p.n_windows, p.per_phase, p.phases, p.k, p.sync_len, p.max_errors, p.part};
+}
 
-static_assert(kAcqTile % kAcqThreads == 0 && kAcqThreads % DEMOD_MAX_PHASES == 0,
-              "a thread's windows must stay on one phase");
-
+// the scan itself is acquire_scan.h's (shared with acquire_frames.hip); here a
+// match lowers its phase's first-match word
 __global__ __launch_bounds__(kAcqThreads) void acquire_scan_kernel(AcquireParams p)
 {
-    __shared__ uint8_t s_sym[kAcqTile + kAcqHalo];
-    __shared__ uint8_t s_sync[DEMOD_MAX_SYNC];
+    __shared__ AcqScanLds s;
     __shared__ unsigned long long s_first[DEMOD_MAX_PHASES];
-    __shared__ double s_acc[kAcqThreads];
-    const int t = threadIdx.x, R = p.phases, L = p.sync_len;
-    const long long W = p.n_windows, Wm = p.per_phase * R;
-    const int halo = L > 0 ? (L - 1) * R : 0;
+    const int t = threadIdx.x, R = p.phases;
     if (t < DEMOD_MAX_PHASES) s_first[t] = kAcqNone;
-    if (t < DEMOD_MAX_SYNC) s_sync[t] = p.sync[t];
-    double acc = 0.0;
-    const long long tiles = (W + kAcqTile - 1) / kAcqTile;
-    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long long base = tile * kAcqTile;
-        __syncthreads();  // the previous tile's compares have read s_sym
-        uint8_t sv[kAcqPerThread];
-#pragma unroll
-        for (int i = 0; i < kAcqPerThread; ++i) {
-            const long long w = base + t + kAcqThreads * i;
-            sv[i] = w < W ? p.sym[w] : (uint8_t)0xFF;
-            s_sym[t + kAcqThreads * i] = sv[i];
-        }
-        for (int h = t; h < halo; h += kAcqThreads) {
-            const long long w = base + kAcqTile + h;
-            s_sym[kAcqTile + h] = w < W ? p.sym[w] : (uint8_t)0xFF;
-        }
-        // the decided tone's power; a byte >= K reads nothing and adds nothing
-        float pw[kAcqPerThread];
-#pragma unroll
-        for (int i = 0; i < kAcqPerThread; ++i) {
-            const long long w = base + t + kAcqThreads * i;
-            pw[i] = (w < Wm && sv[i] < p.k) ? p.mag[w * p.k + sv[i]] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < kAcqPerThread; ++i) acc += (double)pw[i];
-        __syncthreads();
-        if (L > 0) {
-#pragma unroll 1
-            for (int i = 0; i < kAcqPerThread; ++i) {
-                const int local = t + kAcqThreads * i;
-                const long long w = base + local;
-                if (w + halo >= W) continue;  // the word would run past the batch
-                unsigned err = 0;
-                for (int j = 0; j < L; ++j) {
-                    err += s_sym[local + j * R] != s_sync[j];
-                    if (err > p.max_errors) break;
-                }
-                if (err <= p.max_errors)
-                    atomicMin(&s_first[local & (R - 1)], ((unsigned long long)w << 8) | err);
-            }
-        }
-    }
-    s_acc[t] = acc;
-    __syncthreads();
-    if (t < R) {
-        double m = 0.0;
-#pragma unroll 8
-        for (int g = t; g < kAcqThreads; g += R) m += s_acc[g];
-        p.part[(long long)blockIdx.x * R + t] = m;
-        p.first[(long long)blockIdx.x * R + t] = s_first[t];
-    }
+    acquire_scan_body(
+        scan_args(p), p.sync, s,
+        [&](int local, long long w, unsigned err) {
+            atomicMin(&s_first[local & (R - 1)], ((unsigned long long)w << 8) | err);
+        },
+        [](long long) {});
+    // (the body's last barrier stands between the atomics and this read)
+    if (t < R) p.first[(long long)blockIdx.x * R + t] = s_first[t];
 }
 
 __global__ __launch_bounds__(kAcqThreads) void acquire_final_kernel(AcquireParams p)
@@ -111,35 +62,8 @@ __global__ __launch_bounds__(kAcqThreads) void acquire_final_kernel(AcquireParam
     __shared__ int s_phase;
     const int t = threadIdx.x, R = p.phases;
     demod_acquire_result_t *res = p.res;
-    // the partials [grid][R] as one array: entry i is on phase i mod R and 256
-    // is a multiple of R, so thread t adds entries t, t + 256, .. (coalesced,
-    // in block order), then thread r adds the threads' sums of its phase in
-    // thread order: the scan's own scheme, short chains of adds in a fixed order
-    const long long total = (long long)p.grid * R;
-    double m = 0.0;
-#pragma unroll 4
-    for (long long i = t; i < total; i += kAcqThreads) m += p.part[i];
-    s_acc[t] = m;
-    __syncthreads();
-    if (t < DEMOD_MAX_PHASES) {
-        double v = 0.0;
-        if (t < R) {
-#pragma unroll 8
-            for (int g = t; g < kAcqThreads; g += R) v += s_acc[g];
-        }
-        s_m[t] = v;          // 0 for t >= R
-        res->metric[t] = v;
-    }
     if (t == 0) s_best = kAcqNone;
-    __syncthreads();
-    if (t == 0) {
-        int best = 0;
-        for (int r = 1; r < R; ++r)
-            if (s_m[r] > s_m[best]) best = r;
-        s_phase = best;
-    }
-    __syncthreads();
-    const int phase = s_phase;
+    const int phase = acquire_final_phase(p.part, p.grid, R, res->metric, s_acc, s_m, &s_phase);
     if (p.sync_len > 0) {
         unsigned long long v = kAcqNone;
         for (int b = t; b < p.grid; b += kAcqThreads) {

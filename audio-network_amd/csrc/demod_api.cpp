@@ -861,6 +861,120 @@ int demod_acquire_segments(demod_t *st, const int16_t *pcm, size_t n_windows,
     return (int)total;
 }
 
+// ---- frame scan (acquire_frames.hip) ---------------------------------------
+
+size_t demod_frames_workspace_size(const demod_cfg_t *cfg, size_t max_windows)
+{
+    if (validate_cfg(cfg) != DEMOD_OK) return 0;
+    const uint32_t R = acquire_phases(*cfg);
+    if (R == 0 || max_windows > 0x7FFFFFFF) return 0;
+    return frames_work_bytes((max_windows + kAcqTile - 1) / kAcqTile, R);
+}
+
+// The handle's R when a frame scan of these arguments is acceptable, else 0:
+// what acquire_check refuses, no word, or a frame of 2^31 windows or more.
+static uint32_t frames_check(const demod_t *st, size_t n_windows, const uint8_t *sync,
+                             size_t sync_len, uint32_t max_errors, size_t frame_symbols,
+                             size_t max_frames)
+{
+    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
+    if (R == 0 || sync_len == 0 || max_frames > 0x7FFFFFFF) return 0;
+    if (frame_symbols > 0x7FFFFFFF || (sync_len + frame_symbols) * R > 0x7FFFFFFF) return 0;
+    return R;
+}
+
+int demod_frames_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                       size_t n_windows, const uint8_t *sync, size_t sync_len,
+                       uint32_t max_errors, size_t frame_symbols, demod_frame_hit_t *d_hits,
+                       uint8_t *d_payload, uint8_t *d_packed, size_t max_frames,
+                       demod_frames_result_t *d_result, void *d_work, size_t work_bytes,
+                       void *stream)
+{
+    if (!d_symbols || !d_mags || !d_result || !d_work) return DEMOD_BAD_ARG;
+    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
+    if (R == 0) return DEMOD_BAD_ARG;
+    if ((max_frames && !d_hits) || ((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_result & 7) != 0 ||
+        ((uintptr_t)d_work & 7) != 0)
+        return DEMOD_BAD_ARG;
+    const size_t need = demod_frames_workspace_size(&st->cfg, n_windows);
+    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
+    const size_t tiles = (n_windows + kAcqTile - 1) / kAcqTile;
+    FramesParams p;
+    std::memset(&p, 0, sizeof(p));
+    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
+    p.sym = d_symbols;
+    p.mag = d_mags;
+    p.n_windows = (long long)n_windows;
+    p.per_phase = (long long)(n_windows / R);
+    p.frame_symbols = (long long)frame_symbols;
+    p.phases = (int)R;
+    p.k = (int)st->cfg.k;
+    p.bits = demod_bits_per_symbol(st->cfg.k);
+    p.sync_len = (int)sync_len;
+    p.max_errors = max_errors;
+    p.max_frames = max_frames;
+    p.hits = d_hits;
+    p.payload = d_payload;
+    p.packed = d_packed;
+    p.res = d_result;
+    p.part = static_cast<double *>(d_work);
+    p.tail = reinterpret_cast<unsigned long long *>(p.part + (size_t)kAcqMaxBlocks * R);
+    p.offs = reinterpret_cast<unsigned *>(p.tail + (size_t)kAcqMaxBlocks * R);
+    p.count = p.offs + (tiles + 1) / 2 * 2;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_frames(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+int demod_frames(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                 size_t sync_len, uint32_t max_errors, size_t frame_symbols,
+                 demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed, size_t max_frames,
+                 demod_frames_result_t *result)
+{
+    if (!pcm || !result || (max_frames && !hits) || ((uintptr_t)pcm & 15) != 0) return DEMOD_BAD_ARG;
+    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
+    if (R == 0) return DEMOD_BAD_ARG;   // before the detector runs
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
+    const bool din = is_device_ptr(pcm);
+    const size_t N = frame_symbols;
+    const size_t B = (N * (size_t)demod_bits_per_symbol(st->cfg.k) + 7) / 8;
+    int rc;
+    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
+    const size_t work = demod_frames_workspace_size(&st->cfg, n_windows);
+    HIP_TRY(st->d_frm_work.reserve(work));  // bytes
+    HIP_TRY(st->d_frm_res.reserve(1));
+    // complete hits are starts on one phase whose frame fits: W / R + 1 bounds them
+    const size_t dcap = std::min(max_frames, n_windows / R + 1);
+    const bool want_payload = payload && N && dcap, want_packed = packed && N && dcap;
+    HIP_TRY(st->d_frm_hits.reserve(dcap));
+    if (want_payload) HIP_TRY(st->d_frm_payload.reserve(dcap * N));
+    if (want_packed) HIP_TRY(st->d_frm_packed.reserve(dcap * B));
+    if (!din)
+        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
+                               st->stream));
+    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
+    if (rc < 0) return rc;
+    rc = demod_frames_async(st, st->d_sym.p, st->d_mag.p, n_windows, sync, sync_len, max_errors, N,
+                            dcap ? st->d_frm_hits.p : nullptr,
+                            want_payload ? st->d_frm_payload.p : nullptr,
+                            want_packed ? st->d_frm_packed.p : nullptr, dcap, st->d_frm_res.p,
+                            st->d_frm_work.p, work, st->stream);
+    if (rc < 0) return rc;
+    HIP_TRY(hipMemcpyAsync(result, st->d_frm_res.p, sizeof(*result), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    // the device list was cut at dcap >= every possible n_hits or at max_frames
+    const size_t nw = (size_t)result->n_written;
+    if (nw) {
+        HIP_TRY(hipMemcpy(hits, st->d_frm_hits.p, nw * sizeof(*hits), hipMemcpyDeviceToHost));
+        if (want_payload) HIP_TRY(hipMemcpy(payload, st->d_frm_payload.p, nw * N, hipMemcpyDeviceToHost));
+        if (want_packed) HIP_TRY(hipMemcpy(packed, st->d_frm_packed.p, nw * B, hipMemcpyDeviceToHost));
+    }
+    return (int)nw;
+}
+
 int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,
                           uint64_t *first, uint32_t *count, size_t *n_windows)
 {

@@ -149,6 +149,12 @@ struct demod {
     fskd::DevBuf<demod_acquire_result_t> d_seg_res;
     fskd::DevBuf<uint8_t> d_seg_out;
     fskd::PinnedBuf<uint8_t> h_seg_out; // the rows on their way to the caller's [S][cap]
+    // demod_frames: workspace, result, hits and payload rows (first use)
+    fskd::DevBuf<unsigned char> d_frm_work;
+    fskd::DevBuf<demod_frames_result_t> d_frm_res;
+    fskd::DevBuf<demod_frame_hit_t> d_frm_hits;
+    fskd::DevBuf<uint8_t> d_frm_payload;
+    fskd::DevBuf<uint8_t> d_frm_packed;
     fskd::PinnedBuf<int16_t> h_in;      // pinned staging for small host calls
     fskd::PinnedBuf<uint8_t> h_sym;
     fskd::PinnedBuf<float> h_mag;       // [h_sym.cap][k]

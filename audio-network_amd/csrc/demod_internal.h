@@ -7,6 +7,8 @@
 #include <stdint.h>
 
 struct demod_acquire_result;  // include/demod.h
+struct demod_frames_result;
+struct demod_frame_hit;
 
 namespace fskd {
 
@@ -260,5 +262,39 @@ struct AcquireSegParams {
 constexpr size_t acquire_seg_header_bytes(size_t S) { return (20 * S + 4 + 7) / 8 * 8; }
 constexpr size_t acquire_seg_tile_bytes(size_t R) { return 16 * R; }
 hipError_t launch_acquire_segments(const AcquireSegParams &p, hipStream_t s);
+
+// acquire_frames.hip: every sync-word hit on the acquired phase, in window
+// order, with fixed-length payloads. d_work, for T = ceil(n_windows / kAcqTile)
+// tiles: part and tail [kAcqMaxBlocks][R] (8 bytes each), then the chosen
+// phase's exclusive prefix of hits [T] (4 bytes each, padded to 8), then the
+// complete hits per tile and phase [T][R] (4 bytes each, padded to 8).
+struct FramesParams {
+    const uint8_t *sym;      // [n_windows]
+    const float *mag;        // [n_windows][k]
+    long long n_windows;
+    long long per_phase;     // J = n_windows / phases
+    long long frame_symbols; // N
+    int phases;              // R
+    int k;
+    int bits;                // demod_bits_per_symbol(k)
+    int sync_len;            // L >= 1
+    unsigned max_errors;
+    unsigned long long max_frames;
+    ::demod_frame_hit *hits;     // [max_frames] or nullptr (max_frames == 0)
+    uint8_t *payload;            // [max_frames][N] or nullptr
+    uint8_t *packed;             // [max_frames][ceil(N bits / 8)] or nullptr
+    ::demod_frames_result *res;
+    double *part;                // d_work: [grid][phases] per-block phase sums
+    unsigned long long *tail;    // d_work: [grid][phases] lowest incomplete hit (w << 8 | errors), ~0: none
+    unsigned *offs;              // d_work: [tiles] hits of the chosen phase in the tiles before
+    unsigned *count;             // d_work: [tiles][phases] complete hits
+    int grid;                    // set by launch_frames
+    uint8_t sync[64];
+};
+constexpr size_t frames_work_bytes(size_t tiles, size_t R)
+{
+    return (size_t)16 * kAcqMaxBlocks * R + (tiles + 1) / 2 * 8 + (tiles * R + 1) / 2 * 8;
+}
+hipError_t launch_frames(FramesParams p, hipStream_t s);
 
 }  // namespace fskd

@@ -502,6 +502,111 @@ int demod_acquire_segments(demod_t *st, const int16_t *pcm, size_t n_windows,
 int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,
                           uint64_t *first, uint32_t *count, size_t *n_windows);
 
+/* ---- frame scan: every sync-word hit of a batch, with payloads ---------- */
+/*
+ * The acquisition above stops at the lowest window where the sync word
+ * matches. A recording holds many frames; the frame scan makes the same phase
+ * decision (R, J, M[r], phase and errors(w) exactly as "acquisition" defines
+ * them; metric, phases, phase and per_phase come out byte-identical to
+ * demod_acquire_async's on the same inputs) and then lists ALL hits on that
+ * phase, each with a fixed-length payload.
+ *
+ *   L = sync_len, 1 <= L <= DEMOD_MAX_SYNC (the word a HOST pointer, copied
+ *   into the launch arguments); max_errors < L; N = frame_symbols >= 0 payload
+ *   symbols after the word, (L + N) R < 2^31; bits = demod_bits_per_symbol(K).
+ *
+ *   hit          a start w = phase (mod R) with w + (L - 1) R < W and
+ *                errors(w) <= max_errors.
+ *   complete     a hit with w + (L + N - 1) R < W: word and payload lie inside
+ *                the batch (N = 0: the word itself is the frame).
+ *   hits         the complete hits in ascending w; n_hits their number;
+ *                n_written = min(n_hits, max_frames).
+ *   tail_window  the lowest hit that is NOT complete (its frame runs past the
+ *                batch's end), -1 if there is none; tail_errors its error
+ *                count (0 if none).
+ *
+ * For i < n_written only:
+ *   d_hits[i]    = {window_i, errors(window_i), 0}
+ *   d_payload[i N + j] = sym[window_i + (L + j) R], j < N (raw bytes, a byte
+ *                >= K included); may be NULL.
+ *   d_packed[i B .. (i + 1) B), B = ceil(N bits / 8): what
+ *                demod_pack_symbols(payload_i, N, bits, ..) writes (MSB first,
+ *                each symbol masked to `bits` bits, pad bits 0); may be NULL.
+ * Rows >= n_written and bytes outside these arrays are not written.
+ *
+ * Overlaps are reported, not resolved: a hit inside another frame's payload is
+ * listed like any other, so `hits` is NOT a list of disjoint frames. Random
+ * symbols hold the word at a rate of about C(L, <= max_errors) / K^L per
+ * start, and a greedy hold-off is serial in the worst case; callers settle it
+ * with the frame's own header or CRC.
+ *
+ * Streaming: a caller that keeps its samples from tail_window on (or, with
+ * tail_window == -1, from the first start on the phase whose word no longer
+ * fits, w + (L - 1) R >= W) and puts them in front of the next batch loses no
+ * frame.
+ *
+ * All output bytes are a function of the inputs alone (no floating-point
+ * atomics, no atomics that decide a position): bit-identical from run to run
+ * and stream to stream.
+ */
+typedef struct demod_frame_hit {
+    uint64_t window;                    /* the word's first window */
+    uint32_t errors, reserved;          /* errors(window); 0 */
+} demod_frame_hit_t;
+
+typedef struct demod_frames_result {
+    double   metric[DEMOD_MAX_PHASES];  /* as demod_acquire_result_t */
+    uint32_t phases, phase;
+    uint64_t per_phase;
+    uint64_t n_hits, n_written;
+    int64_t  tail_window;               /* -1: none */
+    uint32_t tail_errors, reserved;
+} demod_frames_result_t;
+
+/* Bytes of d_work a frame scan of up to max_windows windows needs; monotone in
+ * max_windows. With T = ceil(max_windows / DEMOD_ACQUIRE_TILE) tiles: two
+ * 8-byte words per phase for each of 1024 workgroups (16 * 1024 * R), one
+ * 4-byte prefix per tile (4 T) and one 4-byte hit count per tile and phase
+ * (4 T R), each rounded up to 8. 0 when the configuration is invalid, n % hop != 0,
+ * R > DEMOD_MAX_PHASES or max_windows >= 2^31. No device needed. */
+size_t demod_frames_workspace_size(const demod_cfg_t *cfg, size_t max_windows);
+
+/*
+ * The frame scan over a batch's device outputs, enqueued on `stream`: four
+ * launches whatever the hit count is (scan, finalise, emit, gather; three when
+ * d_payload and d_packed are both NULL or N == 0; two when max_frames == 0,
+ * which is legal and counts only). All d_* arguments are device pointers
+ * (d_hits, d_result and d_work 8-byte aligned; d_payload and d_packed at any
+ * alignment). Nothing is allocated or synchronised and the handle keeps no
+ * state of the call; d_work may hold anything on entry (every word a launch
+ * reads is stored by an earlier launch of the same call), so the call can be
+ * captured into a HIP graph behind demod_batch_async. Every byte of *d_result
+ * is written. Returns DEMOD_OK once enqueued; DEMOD_BAD_ARG, before any
+ * launch, for everything demod_acquire_async refuses (W < R included),
+ * sync_len == 0, (L + N) R >= 2^31, a NULL d_hits with max_frames > 0,
+ * max_frames >= 2^31, work_bytes below demod_frames_workspace_size(cfg,
+ * n_windows), or a misaligned d_hits, d_result or d_work.
+ */
+int demod_frames_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                       size_t n_windows, const uint8_t *sync, size_t sync_len,
+                       uint32_t max_errors, size_t frame_symbols, demod_frame_hit_t *d_hits,
+                       uint8_t *d_payload, uint8_t *d_packed, size_t max_frames,
+                       demod_frames_result_t *d_result, void *d_work, size_t work_bytes,
+                       void *stream);
+
+/*
+ * The handle's detector over the n_windows sliding windows of pcm (a host or
+ * device pointer, as demod_acquire), then the frame scan of its outputs.
+ * hits[max_frames], payload[max_frames][N] and packed[max_frames][B] (either
+ * may be NULL) and *result are HOST memory; rows past n_written are left
+ * alone. Synchronous; handle-owned buffers grow on first use. Returns
+ * n_written or a negative code.
+ */
+int demod_frames(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                 size_t sync_len, uint32_t max_errors, size_t frame_symbols,
+                 demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed, size_t max_frames,
+                 demod_frames_result_t *result);
+
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
  * n_streams independent streams that share one configuration, each behaving
