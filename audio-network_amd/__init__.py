@@ -262,6 +262,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                               _P, _SZ, _P, _P, _SZ, _P]),
         "demod_frames": (ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _SZ, _P, _P, _P, _SZ,
                                         ctypes.POINTER(DemodFramesResult)]),
+        "demod_frames_segments_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), _SZ, _SZ]),
+        "demod_frames_segments_async": (ctypes.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _P, _SZ,
+                                                       ctypes.c_uint32, _SZ, _P, _P, _P, _SZ, _P, _P, _SZ,
+                                                       _P]),
+        "demod_frames_segments": (ctypes.c_int, [_P, _P, _SZ, _P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _SZ,
+                                                 _P, _P, _P, _SZ, _P]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -438,6 +444,21 @@ def frames_workspace_size(cfg: DemodCfg, max_windows: int) -> int:
     size = int(load_library().demod_frames_workspace_size(ctypes.byref(cfg), int(max_windows)))
     if size == 0:
         raise DemodError(DEMOD_BAD_ARG, "demod_frames_workspace_size")
+    return size
+
+
+def frames_segments_workspace_size(cfg: DemodCfg, max_segments: int, max_windows: int) -> int:
+    """demod_frames_segments_workspace_size: bytes of d_work a segmented frame
+    scan of up to max_segments segments over a batch of up to max_windows
+    windows needs (no GPU); monotone in both. Raises DemodError(DEMOD_BAD_ARG)
+    where it is 0 (no acquisition for cfg, max_segments not in 1 ..
+    DEMOD_MAX_SEGMENTS, max_windows >= 2^31)."""
+    if max_segments < 0 or max_windows < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_frames_segments_workspace_size")
+    size = int(load_library().demod_frames_segments_workspace_size(ctypes.byref(cfg), int(max_segments),
+                                                                  int(max_windows)))
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_frames_segments_workspace_size")
     return size
 
 
@@ -881,6 +902,110 @@ class Demodulator:
             int(d_work.numel()), stream or None)
         if rc < 0:
             raise DemodError(rc, "demod_frames_async")
+
+    def frames_segments(self, pcm, first, count, sync, max_errors: int = 0, frame_symbols: int = 0,
+                        max_frames: Optional[int] = None, n_windows: Optional[int] = None,
+                        payload: bool = True, packed: bool = True):
+        """demod_frames_segments: the detector over the sliding windows of pcm
+        (a host int16 array or a device tensor), then the frame scan of each
+        segment first[s] .. first[s] + count[s] - 1 as a batch of its own.
+        Returns one (hits FRAME_HIT_DTYPE [n_written], payload uint8
+        [n_written][N] or None, packed uint8 [n_written][ceil(N bits / 8)] or
+        None, result dict) per segment; a hit's window is relative to its
+        segment's first window."""
+        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
+        if host:
+            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+            size = flat.size
+        else:
+            size = int(pcm.numel())
+        if n_windows is None:
+            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
+        n_windows = int(n_windows)
+        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
+        if host:
+            if need > size:
+                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
+            buf = flat
+            if flat.ctypes.data % 16:
+                buf = np.empty(flat.size + 8, dtype=np.int16)
+                off = (-buf.ctypes.data % 16) // 2
+                buf = buf[off:off + flat.size]
+                buf[:] = flat
+        else:
+            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
+            buf = pcm
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+        if first.size != count.size or first.size == 0:
+            raise DemodError(DEMOD_BAD_ARG, "first and count: one entry per segment, at least one")
+        S = first.size
+        sync = _sync_bytes(sync)
+        N = int(frame_symbols)
+        if N < 0 or (max_frames is not None and max_frames < 0):
+            raise DemodError(DEMOD_BAD_ARG, "frame_symbols or max_frames < 0")
+        if max_frames is None:
+            max_frames = int(count.max()) // max(self.n // self.hop, 1) + 1
+        cap = int(max_frames)
+        B = (N * bits_per_symbol(self.k) + 7) // 8
+        hits = np.zeros((S, max(cap, 1)), dtype=FRAME_HIT_DTYPE)
+        pay = np.empty((S, max(cap, 1), N), dtype=np.uint8) if payload and N else None
+        pak = np.empty((S, max(cap, 1), B), dtype=np.uint8) if packed and N else None
+        results = (DemodFramesResult * S)()
+        rc = self._lib.demod_frames_segments(
+            self._h, _ptr(buf), n_windows, _ptr(first), _ptr(count), S, _ptr(sync) if sync.size else None,
+            sync.size, int(max_errors), N, _ptr(hits) if cap else None,
+            _ptr(pay) if pay is not None else None, _ptr(pak) if pak is not None else None, cap,
+            ctypes.cast(results, _P))
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_segments")
+        out = []
+        for s, r in enumerate(results):
+            nw = int(r.n_written)
+            out.append((hits[s, :nw].copy(), pay[s, :nw].copy() if pay is not None else None,
+                        pak[s, :nw].copy() if pak is not None else None, frames_result_dict(r)))
+        return out
+
+    def frames_segments_async(self, d_sym, d_mag, n_windows: int, d_first, d_count, n_segments: int,
+                              sync, max_errors: int, frame_symbols: int, d_hits, d_payload, d_packed,
+                              max_frames: int, d_results, d_work, stream: int = 0) -> None:
+        """demod_frames_segments_async on a batch's device outputs. d_first
+        (int64 tensor holding the uint64 table) and d_count (int32 tensor
+        holding the uint32 table) have n_segments entries; d_hits (uint8,
+        n_segments * max_frames * sizeof(DemodFrameHit) bytes; None with
+        max_frames 0), d_payload (uint8, n_segments * max_frames *
+        frame_symbols bytes, or None), d_packed (uint8, n_segments * max_frames
+        * ceil(frame_symbols * bits / 8) bytes, or None), d_results (uint8,
+        n_segments * sizeof(DemodFramesResult) bytes) and d_work (uint8, at
+        least frames_segments_workspace_size(cfg, n_segments, n_windows) bytes;
+        all of it is handed over, a larger one raises the tile budget) are
+        device tensors, checked like the batch calls' (dtype, contiguity,
+        device, size)."""
+        n_windows, S, N, cap = int(n_windows), int(n_segments), int(frame_symbols), int(max_frames)
+        if n_windows < 0 or N < 0 or cap < 0 or S < 1 or S > DEMOD_MAX_SEGMENTS:
+            raise DemodError(DEMOD_BAD_ARG, "n_windows, frame_symbols or max_frames < 0, or n_segments "
+                                            "not in 1 .. DEMOD_MAX_SEGMENTS")
+        dev = int(self.cfg.device)
+        B = (N * bits_per_symbol(self.k) + 7) // 8
+        _check_dev(d_sym, "d_sym", "uint8", max(n_windows, 1), dev)
+        _check_dev(d_mag, "d_mag", "float32", max(n_windows, 1) * self.k, dev)
+        _check_dev(d_first, "d_first", "int64", S, dev)
+        _check_dev(d_count, "d_count", "int32", S, dev)
+        _check_dev(d_hits, "d_hits", "uint8", S * cap * ctypes.sizeof(DemodFrameHit), dev)
+        _check_dev(d_payload, "d_payload", "uint8", S * cap * N, dev, nullable=True)
+        _check_dev(d_packed, "d_packed", "uint8", S * cap * B, dev, nullable=True)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_work, "d_work", "uint8", frames_segments_workspace_size(self.cfg, S, n_windows), dev)
+        sync = _sync_bytes(sync)
+        rc = self._lib.demod_frames_segments_async(
+            self._h, _ptr(d_sym), _ptr(d_mag), n_windows, _ptr(d_first), _ptr(d_count), S,
+            _ptr(sync) if sync.size else None, sync.size, int(max_errors), N,
+            _ptr(d_hits) if d_hits is not None else None,
+            _ptr(d_payload) if d_payload is not None else None,
+            _ptr(d_packed) if d_packed is not None else None, cap, _ptr(d_results), _ptr(d_work),
+            int(d_work.numel()), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_segments_async")
 
 
 class Streams:

@@ -38,27 +38,17 @@
 //            first-match word, every byte of result[s].
 //  gather    out[s cap + j] = sym[first' + first_window + j R], j < n_written.
 //
+// The scan's tile body and the finaliser's phase decision are in
+// acquire_seg_scan.h, shared with acquire_frames_segments.hip.
+//
 // Every sum's order depends on the segment's (count, R) alone: not on first[s],
 // the slot s, S or the grid. No floating-point atomics. Every word of d_work a
 // launch reads was stored by an earlier launch of the same call.
-#include "../../include/demod.h"
-#include "demod_internal.h"
+#include "acquire_seg_scan.h"
 
 namespace fskd {
 
-constexpr int kSegThreads = 256;
-constexpr int kSegLanes = 64;
-constexpr int kSegWaves = kSegThreads / kSegLanes;
-constexpr int kSegPerLane = kAcqTile / kSegLanes;
-constexpr int kSegHalo = (DEMOD_MAX_SYNC - 1) * DEMOD_MAX_PHASES;
-constexpr int kSegMaxBlocks = 2048;      // the scan's grid: min(ceil(budget / 4), this)
-constexpr unsigned kSegWaveTiles = 64;   // finalise: up to this many tiles by one wave
 constexpr int kSegPlanThreads = 1024;
-constexpr unsigned long long kSegNone = ~0ull;
-
-static_assert(kSegLanes % DEMOD_MAX_PHASES == 0 && kAcqTile % kSegLanes == 0,
-              "a lane's windows must stay on one phase");
-static_assert(kSegThreads % DEMOD_MAX_PHASES == 0, "finalise: a thread's entries stay on one phase");
 
 __global__ __launch_bounds__(kSegPlanThreads) void acquire_seg_plan_kernel(AcquireSegParams p)
 {
@@ -113,175 +103,31 @@ __global__ __launch_bounds__(kSegThreads) void acquire_seg_scan_kernel(AcquireSe
     __shared__ uint8_t s_sym[kSegWaves][kAcqTile + kSegHalo];
     __shared__ uint8_t s_sync[DEMOD_MAX_SYNC];
     const int t = threadIdx.x, wave = t / kSegLanes, lane = t % kSegLanes;
-    const int R = p.phases, L = p.sync_len;
-    const int halo = L > 0 ? (L - 1) * R : 0;
+    const int R = p.phases;
     if (t < DEMOD_MAX_SYNC) s_sync[t] = p.sync[t];
     const unsigned total = *p.w_total;
     for (unsigned g0 = blockIdx.x * kSegWaves; g0 < total; g0 += gridDim.x * kSegWaves) {
         const unsigned g = g0 + wave;
-        const bool live = g < total;
-        // the last segment whose first tile is <= g: zero-tile segments share a
-        // successor's first tile and lie before it, dropped ones start at total
-        unsigned s = 0;
-        if (live) {
-            unsigned lo = 0, hi = p.n_segments;
-            while (hi - lo > 1) {
-                const unsigned mid = lo + (hi - lo) / 2;
-                if (p.w_tile0[mid] <= g) lo = mid; else hi = mid;
-            }
-            s = lo;
-        }
-        const long long cnt = live ? (long long)p.w_count[s] : 0;
-        const unsigned long long f = live ? p.w_first[s] : 0;
-        const long long base = live ? (long long)(g - p.w_tile0[s]) * kAcqTile : 0;
-        const long long Wm = cnt / R * R;
-        if (L > 0) __syncthreads();  // the previous tile's compares have read s_sym
-        uint8_t sv[kSegPerLane];
-#pragma unroll
-        for (int i = 0; i < kSegPerLane; ++i) {
-            const long long w = base + lane + kSegLanes * i;
-            sv[i] = w < cnt ? p.sym[f + w] : (uint8_t)0xFF;
-            if (L > 0) s_sym[wave][lane + kSegLanes * i] = sv[i];
-        }
-        for (int h = lane; h < halo; h += kSegLanes) {
-            const long long w = base + kAcqTile + h;
-            s_sym[wave][kAcqTile + h] = w < cnt ? p.sym[f + w] : (uint8_t)0xFF;
-        }
-        // the decided tone's power; a byte >= K reads nothing and adds nothing
-        float pw[kSegPerLane];
-#pragma unroll
-        for (int i = 0; i < kSegPerLane; ++i) {
-            const long long w = base + lane + kSegLanes * i;
-            pw[i] = (w < Wm && sv[i] < p.k) ? p.mag[(f + w) * p.k + sv[i]] : 0.f;
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < kSegPerLane; ++i) acc += (double)pw[i];
-        unsigned long long best = kSegNone;
-        if (L > 0) {
-            __syncthreads();
-#pragma unroll 1
-            for (int i = 0; i < kSegPerLane; ++i) {
-                const int local = lane + kSegLanes * i;
-                const long long w = base + local;
-                if (w + halo >= cnt) break;  // the word would run past the segment
-                unsigned err = 0;
-                for (int j = 0; j < L; ++j) {
-                    err += s_sym[wave][local + j * R] != s_sync[j];
-                    if (err > p.max_errors) break;
-                }
-                if (err <= p.max_errors) {   // the lane's windows ascend: its first match is its lowest
-                    best = ((unsigned long long)w << 8) | err;
-                    break;
-                }
-            }
-        }
-        // the lanes of a phase: a fixed tree, the same value in every lane of it
-        for (int off = kSegLanes / 2; off >= R; off >>= 1) {
-            acc += __shfl_xor(acc, off);
-            const unsigned long long o = __shfl_xor(best, off);
-            best = o < best ? o : best;
-        }
-        if (live && lane < R) {
-            p.part[(size_t)g * R + lane] = acc;
-            p.first[(size_t)g * R + lane] = best;
+        const SegTile tl = seg_tile_of(p, g, total);
+        const SegScan r = seg_scan_tile<false>(p, tl, s_sym[wave], s_sync, lane, 0);
+        if (tl.live && lane < R) {
+            p.part[(size_t)g * R + lane] = r.acc;
+            p.first[(size_t)g * R + lane] = r.word;
         }
     }
 }
 
 __global__ __launch_bounds__(kSegThreads) void acquire_seg_final_kernel(AcquireSegParams p)
 {
-    __shared__ double s_acc[kSegThreads];
-    __shared__ double s_big[kSegWaves][DEMOD_MAX_PHASES];
-    __shared__ unsigned s_nt[kSegWaves], s_t0[kSegWaves];
-    __shared__ unsigned long long s_best[kSegWaves];
-    __shared__ int s_phase[kSegWaves];
-    const int t = threadIdx.x, wave = t / kSegLanes, lane = t % kSegLanes, R = p.phases;
-    const unsigned s = blockIdx.x * kSegWaves + wave;
-    const bool valid = s < p.n_segments;
-    const unsigned nt = valid ? p.w_tiles[s] : 0u;
-    const unsigned t0 = valid ? p.w_tile0[s] : 0u;
-    const unsigned long long cnt = valid ? p.w_count[s] : 0u;
-    if (lane == 0) {
-        s_nt[wave] = nt;
-        s_t0[wave] = t0;
-        s_best[wave] = kSegNone;
-    }
-    __syncthreads();
-    double m = 0.0;   // lane l: the metric of phase l mod R
-    if (nt <= kSegWaveTiles) {
-        const double *q = p.part + (size_t)t0 * R;
-        const unsigned total = nt * (unsigned)R;
-#pragma unroll 4
-        for (unsigned i = lane; i < total; i += kSegLanes) m += q[i];
-        for (int off = kSegLanes / 2; off >= R; off >>= 1) m += __shfl_xor(m, off);
-    }
-    // long segments: the whole workgroup, one after the other (uniform branches)
-    for (int w = 0; w < kSegWaves; ++w) {
-        const unsigned ntw = s_nt[w];
-        if (ntw <= kSegWaveTiles) continue;
-        const double *q = p.part + (size_t)s_t0[w] * R;
-        const unsigned long long total = (unsigned long long)ntw * R;
-        double a = 0.0;
-#pragma unroll 8
-        for (unsigned long long i = t; i < total; i += kSegThreads) a += q[i];
-        s_acc[t] = a;
-        __syncthreads();
-        if (t < R) {
-            double v = 0.0;
-#pragma unroll 8
-            for (int g = t; g < kSegThreads; g += R) v += s_acc[g];
-            s_big[w][t] = v;
-        }
-        __syncthreads();
-        // its phase and that phase's lowest first-match word, by the workgroup too:
-        // one wave would wait for tiles / 64 loads one after the other
-        if (t == 0) {
-            int best = 0;
-            for (int r = 1; r < R; ++r)
-                if (s_big[w][r] > s_big[w][best]) best = r;
-            s_phase[w] = best;
-        }
-        __syncthreads();
-        if (p.sync_len > 0) {
-            const unsigned long long *f = p.first + (size_t)s_t0[w] * R + s_phase[w];
-            unsigned long long v = kSegNone;
-#pragma unroll 4
-            for (unsigned b = t; b < ntw; b += kSegThreads) {
-                const unsigned long long o = f[(size_t)b * R];
-                v = o < v ? o : v;
-            }
-            if (v != kSegNone) atomicMin(&s_best[w], v);   // integer, LDS
-        }
-        __syncthreads();
-    }
-    if (nt > kSegWaveTiles) m = s_big[wave][lane & (R - 1)];
-    // argmax over the phases, ties to the lowest
-    double bm = m;
-    int br = lane & (R - 1);
-    for (int off = R >> 1; off >= 1; off >>= 1) {
-        const double om = __shfl_xor(bm, off);
-        const int orr = __shfl_xor(br, off);
-        if (om > bm || (om == bm && orr < br)) {
-            bm = om;
-            br = orr;
-        }
-    }
-    const int phase = nt > kSegWaveTiles ? s_phase[wave] : __shfl(br, 0);
-    unsigned long long best = nt > kSegWaveTiles ? s_best[wave] : kSegNone;
-    if (p.sync_len > 0 && nt <= kSegWaveTiles) {
-        for (unsigned b = lane; b < nt; b += kSegLanes) {
-            const unsigned long long v = p.first[((size_t)t0 + b) * R + phase];
-            best = v < best ? v : best;
-        }
-        for (int off = kSegLanes / 2; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(best, off);
-            best = o < best ? o : best;
-        }
-    }
-    if (!valid) return;
-    demod_acquire_result_t *res = p.res + s;
-    res->metric[lane] = (lane < R && nt > 0) ? m : 0.0;
+    __shared__ SegFinalLds lds;
+    const int lane = threadIdx.x % kSegLanes, R = p.phases;
+    const SegFinal fin = seg_final_phase(p, lds);
+    if (!fin.valid) return;
+    const unsigned nt = fin.nt;
+    const unsigned long long cnt = fin.cnt, best = fin.best;
+    const int phase = fin.phase;
+    demod_acquire_result_t *res = p.res + fin.s;
+    res->metric[lane] = (lane < R && nt > 0) ? fin.m : 0.0;
     if (lane == 0) {
         const bool is_short = nt == 0;   // fewer than R windows, or past the tile budget
         const bool found = !is_short && p.sync_len > 0 && best != kSegNone;
@@ -314,13 +160,16 @@ __global__ __launch_bounds__(kSegThreads) void acquire_seg_gather_kernel(Acquire
         row[j] = p.sym[fw + j * p.phases];
 }
 
+void launch_acquire_seg_plan(const AcquireSegParams &p, hipStream_t s)
+{
+    hipLaunchKernelGGL(acquire_seg_plan_kernel, dim3(1), dim3(kSegPlanThreads), 0, s, p);
+}
+
 hipError_t launch_acquire_segments(const AcquireSegParams &p, hipStream_t s)
 {
     const unsigned S = p.n_segments;
-    hipLaunchKernelGGL(acquire_seg_plan_kernel, dim3(1), dim3(kSegPlanThreads), 0, s, p);
-    const unsigned long long blocks = ((unsigned long long)p.budget + kSegWaves - 1) / kSegWaves;
-    const unsigned grid = (unsigned)(blocks < kSegMaxBlocks ? (blocks ? blocks : 1) : kSegMaxBlocks);
-    hipLaunchKernelGGL(acquire_seg_scan_kernel, dim3(grid), dim3(kSegThreads), 0, s, p);
+    launch_acquire_seg_plan(p, s);
+    hipLaunchKernelGGL(acquire_seg_scan_kernel, dim3(seg_tile_grid(p.budget)), dim3(kSegThreads), 0, s, p);
     hipLaunchKernelGGL(acquire_seg_final_kernel, dim3((S + kSegWaves - 1) / kSegWaves),
                        dim3(kSegThreads), 0, s, p);
     if (p.cap > 0) {

@@ -875,9 +875,9 @@ size_t demod_frames_workspace_size(const demod_cfg_t *cfg, size_t max_windows)
 // what acquire_check refuses, no word, or a frame of 2^31 windows or more.
 static uint32_t frames_check(const demod_t *st, size_t n_windows, const uint8_t *sync,
                              size_t sync_len, uint32_t max_errors, size_t frame_symbols,
-                             size_t max_frames)
+                             size_t max_frames, bool whole = true)
 {
-    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
+    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors, whole);
     if (R == 0 || sync_len == 0 || max_frames > 0x7FFFFFFF) return 0;
     if (frame_symbols > 0x7FFFFFFF || (sync_len + frame_symbols) * R > 0x7FFFFFFF) return 0;
     return R;
@@ -973,6 +973,178 @@ int demod_frames(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_
         if (want_packed) HIP_TRY(hipMemcpy(packed, st->d_frm_packed.p, nw * B, hipMemcpyDeviceToHost));
     }
     return (int)nw;
+}
+
+// ---- segmented frame scan (acquire_frames_segments.hip) ---------------------
+
+size_t demod_frames_segments_workspace_size(const demod_cfg_t *cfg, size_t max_segments,
+                                            size_t max_windows)
+{
+    if (validate_cfg(cfg) != DEMOD_OK) return 0;
+    const uint32_t R = acquire_phases(*cfg);
+    if (R == 0 || max_segments == 0 || max_segments > DEMOD_MAX_SEGMENTS || max_windows > 0x7FFFFFFF)
+        return 0;
+    const size_t tiles = (max_windows + kAcqTile - 1) / kAcqTile + max_segments;
+    return acquire_seg_header_bytes(max_segments) + frames_seg_tiles_bytes(tiles, R);
+}
+
+int demod_frames_segments_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                                size_t n_windows, const uint64_t *d_first, const uint32_t *d_count,
+                                size_t n_segments, const uint8_t *sync, size_t sync_len,
+                                uint32_t max_errors, size_t frame_symbols, demod_frame_hit_t *d_hits,
+                                uint8_t *d_payload, uint8_t *d_packed, size_t max_frames,
+                                demod_frames_result_t *d_results, void *d_work, size_t work_bytes,
+                                void *stream)
+{
+    if (!d_symbols || !d_mags || !d_results || !d_work || !d_first || !d_count) return DEMOD_BAD_ARG;
+    const uint32_t R =
+        frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames, false);
+    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
+    if ((unsigned long long)n_segments * max_frames > 0x7FFFFFFFull) return DEMOD_BAD_ARG;
+    if ((max_frames && !d_hits) || ((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 ||
+        ((uintptr_t)d_work & 7) != 0 || ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_count & 3) != 0)
+        return DEMOD_BAD_ARG;
+    const size_t need = demod_frames_segments_workspace_size(&st->cfg, n_segments, n_windows);
+    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
+    const size_t head = acquire_seg_header_bytes(n_segments);
+    const size_t budget = std::min<size_t>(frames_seg_budget(work_bytes - head, R), 0xFFFFFFFFu);
+    FrameSegParams q;
+    std::memset(&q, 0, sizeof(q));
+    AcquireSegParams &p = q.seg;
+    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
+    p.sym = d_symbols;
+    p.mag = d_mags;
+    p.seg_first = reinterpret_cast<const unsigned long long *>(d_first);
+    p.seg_count = d_count;
+    p.n_windows = (long long)n_windows;
+    p.n_segments = (unsigned)n_segments;
+    p.budget = (unsigned)budget;
+    p.phases = (int)R;
+    p.k = (int)st->cfg.k;
+    p.sync_len = (int)sync_len;
+    p.max_errors = max_errors;
+    // the header as demod_acquire_segments_async lays it out, then the tiles'
+    // words: part and tail [B][R], count [B][R], offs [B]
+    unsigned char *w = static_cast<unsigned char *>(d_work);
+    p.w_first = reinterpret_cast<unsigned long long *>(w);
+    p.w_count = reinterpret_cast<unsigned *>(w + 8 * n_segments);
+    p.w_tile0 = p.w_count + n_segments;
+    p.w_tiles = p.w_tile0 + n_segments;
+    p.w_total = p.w_tiles + n_segments;
+    p.part = reinterpret_cast<double *>(w + head);
+    p.first = reinterpret_cast<unsigned long long *>(p.part + budget * R);
+    q.count = reinterpret_cast<unsigned *>(p.first + budget * R);
+    q.offs = q.count + (budget * R + 1) / 2 * 2;
+    q.frame_symbols = (long long)frame_symbols;
+    q.bits = demod_bits_per_symbol(st->cfg.k);
+    q.max_frames = max_frames;
+    q.hits = d_hits;
+    q.payload = d_payload;
+    q.packed = d_packed;
+    q.res = d_results;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_frames_segments(q, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, const uint64_t *first,
+                          const uint32_t *count, size_t n_segments, const uint8_t *sync,
+                          size_t sync_len, uint32_t max_errors, size_t frame_symbols,
+                          demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed,
+                          size_t max_frames, demod_frames_result_t *results)
+{
+    if (!pcm || !results || !first || !count || (max_frames && !hits) || ((uintptr_t)pcm & 15) != 0)
+        return DEMOD_BAD_ARG;
+    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
+    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
+    // the tables are host memory here: refuse what the kernels would clamp
+    size_t longest = 0;
+    unsigned long long tiles = 0, rows = 0;
+    for (size_t s = 0; s < n_segments; ++s) {
+        if (count[s] < R || first[s] > n_windows || count[s] > n_windows - first[s])
+            return DEMOD_BAD_ARG;
+        longest = std::max<size_t>(longest, count[s]);
+        tiles += (count[s] + (size_t)kAcqTile - 1) / kAcqTile;
+        rows += std::min<unsigned long long>(max_frames, count[s] / R + 1);
+    }
+    if (rows > 0x7FFFFFFF) return DEMOD_BAD_ARG;   // the return value is their sum at most
+    // complete hits are starts on one phase whose frame fits: count / R + 1 bounds them
+    const size_t dcap = std::min(max_frames, longest / R + 1);
+    if ((unsigned long long)n_segments * dcap > 0x7FFFFFFFull) return DEMOD_BAD_ARG;
+    // a workspace for every tile (overlapping segments may hold more than the batch)
+    const unsigned long long cover = std::max<unsigned long long>(
+        n_windows, tiles > n_segments ? (tiles - n_segments) * kAcqTile : 0);
+    if (cover > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const size_t work = demod_frames_segments_workspace_size(&st->cfg, n_segments, (size_t)cover);
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
+    const bool din = is_device_ptr(pcm);
+    const size_t N = frame_symbols;
+    const size_t B = (N * (size_t)demod_bits_per_symbol(st->cfg.k) + 7) / 8;
+    const size_t n_rows = dcap * n_segments;
+    const bool want_payload = payload && N && dcap, want_packed = packed && N && dcap;
+    int rc;
+    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
+    HIP_TRY(st->d_seg_work.reserve(work));  // bytes
+    HIP_TRY(st->d_seg_first.reserve(n_segments));
+    HIP_TRY(st->d_seg_count.reserve(n_segments));
+    HIP_TRY(st->d_fsg_res.reserve(n_segments));
+    HIP_TRY(st->d_fsg_hits.reserve(n_rows));
+    HIP_TRY(st->h_fsg_hits.reserve(n_rows));
+    if (want_payload) {
+        HIP_TRY(st->d_fsg_payload.reserve(n_rows * N));
+        HIP_TRY(st->h_fsg_payload.reserve(n_rows * N));
+    }
+    if (want_packed) {
+        HIP_TRY(st->d_fsg_packed.reserve(n_rows * B));
+        HIP_TRY(st->h_fsg_packed.reserve(n_rows * B));
+    }
+    HIP_TRY(hipMemcpyAsync(st->d_seg_first.p, first, n_segments * sizeof(uint64_t),
+                           hipMemcpyHostToDevice, st->stream));
+    HIP_TRY(hipMemcpyAsync(st->d_seg_count.p, count, n_segments * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, st->stream));
+    if (!din)
+        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
+                               st->stream));
+    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
+    if (rc < 0) return rc;
+    rc = demod_frames_segments_async(st, st->d_sym.p, st->d_mag.p, n_windows, st->d_seg_first.p,
+                                     st->d_seg_count.p, n_segments, sync, sync_len, max_errors, N,
+                                     dcap ? st->d_fsg_hits.p : nullptr,
+                                     want_payload ? st->d_fsg_payload.p : nullptr,
+                                     want_packed ? st->d_fsg_packed.p : nullptr, dcap, st->d_fsg_res.p,
+                                     st->d_seg_work.p, work, st->stream);
+    if (rc < 0) return rc;
+    HIP_TRY(hipMemcpyAsync(results, st->d_fsg_res.p, n_segments * sizeof(*results),
+                           hipMemcpyDeviceToHost, st->stream));
+    // the rows through pinned staging in the same pass, then each segment's
+    // written rows to the caller's [S][max_frames]
+    if (dcap) {
+        HIP_TRY(hipMemcpyAsync(st->h_fsg_hits.p, st->d_fsg_hits.p, n_rows * sizeof(*hits),
+                               hipMemcpyDeviceToHost, st->stream));
+        if (want_payload)
+            HIP_TRY(hipMemcpyAsync(st->h_fsg_payload.p, st->d_fsg_payload.p, n_rows * N,
+                                   hipMemcpyDeviceToHost, st->stream));
+        if (want_packed)
+            HIP_TRY(hipMemcpyAsync(st->h_fsg_packed.p, st->d_fsg_packed.p, n_rows * B,
+                                   hipMemcpyDeviceToHost, st->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    unsigned long long total = 0;
+    for (size_t s = 0; s < n_segments; ++s) {
+        const size_t nw = (size_t)results[s].n_written;
+        if (nw) {
+            std::memcpy(hits + s * max_frames, st->h_fsg_hits.p + s * dcap, nw * sizeof(*hits));
+            if (want_payload)
+                std::memcpy(payload + s * max_frames * N, st->h_fsg_payload.p + s * dcap * N, nw * N);
+            if (want_packed)
+                std::memcpy(packed + s * max_frames * B, st->h_fsg_packed.p + s * dcap * B, nw * B);
+        }
+        total += nw;
+    }
+    return (int)total;
 }
 
 int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,

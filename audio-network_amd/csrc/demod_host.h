@@ -155,6 +155,15 @@ struct demod {
     fskd::DevBuf<demod_frame_hit_t> d_frm_hits;
     fskd::DevBuf<uint8_t> d_frm_payload;
     fskd::DevBuf<uint8_t> d_frm_packed;
+    // demod_frames_segments: results and rows (first use); the tables and the
+    // workspace are demod_acquire_segments' (d_seg_first, d_seg_count, d_seg_work)
+    fskd::DevBuf<demod_frames_result_t> d_fsg_res;
+    fskd::DevBuf<demod_frame_hit_t> d_fsg_hits;
+    fskd::DevBuf<uint8_t> d_fsg_payload;
+    fskd::DevBuf<uint8_t> d_fsg_packed;
+    fskd::PinnedBuf<demod_frame_hit_t> h_fsg_hits;   // the rows on their way to the caller's [S][max_frames]
+    fskd::PinnedBuf<uint8_t> h_fsg_payload;
+    fskd::PinnedBuf<uint8_t> h_fsg_packed;
     fskd::PinnedBuf<int16_t> h_in;      // pinned staging for small host calls
     fskd::PinnedBuf<uint8_t> h_sym;
     fskd::PinnedBuf<float> h_mag;       // [h_sym.cap][k]

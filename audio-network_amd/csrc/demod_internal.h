@@ -297,4 +297,37 @@ constexpr size_t frames_work_bytes(size_t tiles, size_t R)
 }
 hipError_t launch_frames(FramesParams p, hipStream_t s);
 
+// acquire_frames_segments.hip: the frame scan over S segments of a batch, each
+// treated as a batch of its own. d_work is acquire_segments.hip's header
+// (written by its plan launch, launch_acquire_seg_plan) followed, for the
+// budget's B tiles, by part [B][R] (8 bytes each), tail [B][R] (8 bytes: a
+// tile's lowest incomplete hit per phase, in seg.first), count [B][R] (4 bytes:
+// complete hits) and offs [B] (4 bytes: the chosen phase's hits in the
+// segment's tiles before), each array padded to 8 bytes.
+struct FrameSegParams {
+    AcquireSegParams seg;        // tables, header, part, first (= tail), sync; cap, out and res unused
+    long long frame_symbols;     // N
+    int bits;                    // demod_bits_per_symbol(k)
+    unsigned long long max_frames;
+    ::demod_frame_hit *hits;     // [n_segments][max_frames] or nullptr (max_frames == 0)
+    uint8_t *payload;            // [n_segments][max_frames][N] or nullptr
+    uint8_t *packed;             // [n_segments][max_frames][ceil(N bits / 8)] or nullptr
+    ::demod_frames_result *res;  // [n_segments]
+    unsigned *count;             // d_work: [budget][phases]
+    unsigned *offs;              // d_work: [budget]
+};
+// Bytes of the words of B tiles, and the largest B that `bytes` hold.
+constexpr size_t frames_seg_tiles_bytes(size_t B, size_t R)
+{
+    return 16 * B * R + (B * R + 1) / 2 * 8 + (B + 1) / 2 * 8;
+}
+constexpr size_t frames_seg_budget(size_t bytes, size_t R)
+{
+    size_t B = bytes / (20 * R + 4);   // no padding: an upper bound
+    while (B > 0 && frames_seg_tiles_bytes(B, R) > bytes) --B;
+    return B;
+}
+void launch_acquire_seg_plan(const AcquireSegParams &p, hipStream_t s);
+hipError_t launch_frames_segments(const FrameSegParams &q, hipStream_t s);
+
 }  // namespace fskd

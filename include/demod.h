@@ -607,6 +607,102 @@ int demod_frames(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_
                  demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed, size_t max_frames,
                  demod_frames_result_t *result);
 
+/* ---- segmented frame scan: every frame of every segment, one call ------- */
+/*
+ * The frame scan above picks ONE phase for the batch and lists the hits on it:
+ * many streams in one batch, or a stream whose timing slips, lose frames. Here
+ * the batch holds S segments, segment s being batch windows first[s] ..
+ * first[s] + count[s] - 1 (the tables of "segmented acquisition": device
+ * arrays read when the launches run, clamped first' = min(first, n_windows),
+ * count' = min(count, n_windows - first'); segments may touch, leave gaps,
+ * come in any order and overlap), and each is scanned exactly as a batch of
+ * its own: with W = count'[s] and window indices relative to first'[s], the
+ * "frame scan" definitions on (sym + first', P + first' K, count') give
+ * results[s] and, for i < results[s].n_written,
+ *
+ *   d_hits[s max_frames + i]            (window segment-relative, as sync_window)
+ *   d_payload[(s max_frames + i) N + j] (j < N)
+ *   d_packed[(s max_frames + i) B ..)   (B = ceil(N bits / 8))
+ *
+ * A word or a payload never reads past its segment: a hit whose payload would
+ * leave the segment is not complete and is that segment's tail_window. Rows
+ * >= n_written of a segment are not written; every byte of d_results[0 .. S)
+ * is. No table content makes the kernels read outside the inputs or write
+ * outside the outputs and d_work.
+ *
+ * Short segments: a segment with count' < R, or one past the tile budget,
+ * reports phases = R, phase = 0, per_phase = 0, metric all 0, n_hits =
+ * n_written = 0, tail_window = -1, tail_errors = 0.
+ *
+ * Tile budget: the rule of "segmented acquisition" (B = ceil(Wmax /
+ * DEMOD_ACQUIRE_TILE) + S tiles; a call's budget is the largest B its
+ * work_bytes hold; segment s is scanned when the tiles of segments 0 .. s
+ * together are within it).
+ *
+ * metric, phases, phase and per_phase of results[s] are byte-identical to the
+ * same fields of demod_acquire_segments_async for the same tables. Every
+ * output byte of a segment depends on its own contents and (count', R) alone:
+ * not on first[s], the slot s, S, the grid or the neighbours. No
+ * floating-point atomics, no atomic decides a position.
+ */
+
+/* Bytes of d_work for up to max_segments segments of a batch of up to
+ * max_windows windows; monotone in both. With S = max_segments, B =
+ * ceil(max_windows / DEMOD_ACQUIRE_TILE) + S tiles and R phases: the header of
+ * the segmented acquisition, 20 S + 4 rounded up to 8, then per tile one
+ * 8-byte partial and one 8-byte tail word per phase (16 B R), one 4-byte hit
+ * count per phase (4 B R, rounded up to 8) and one 4-byte prefix (4 B, rounded
+ * up to 8). 0 when the configuration is invalid (as
+ * demod_frames_workspace_size), max_segments is 0 or above DEMOD_MAX_SEGMENTS,
+ * or max_windows >= 2^31. No device needed. */
+size_t demod_frames_segments_workspace_size(const demod_cfg_t *cfg, size_t max_segments,
+                                            size_t max_windows);
+
+/*
+ * Enqueued on `stream`: five launches whatever n_segments and the hit counts
+ * are (plan, scan, finalise, emit, gather; four when d_payload and d_packed
+ * are both NULL or N == 0; three when max_frames == 0, which counts only).
+ * Nothing is allocated or synchronised and the handle holds no state of the
+ * call; d_work may hold anything on entry (every word a launch reads is
+ * stored by an earlier launch of the same call; no atomics on d_work), so the
+ * call can be captured behind demod_batch_async and replayed after the tables
+ * are rewritten in place. d_hits is [n_segments][max_frames], d_payload
+ * [n_segments][max_frames][N], d_packed [n_segments][max_frames][B] (either
+ * may be NULL), d_results [n_segments]. Returns DEMOD_OK once enqueued;
+ * DEMOD_BAD_ARG, before any launch, for what demod_frames_async refuses except
+ * n_windows < R (a per-segment outcome here), n_segments == 0 or >
+ * DEMOD_MAX_SEGMENTS, a NULL d_first or d_count, n_segments * max_frames >=
+ * 2^31, work_bytes below demod_frames_segments_workspace_size(cfg, n_segments,
+ * n_windows), or a misaligned d_hits, d_results, d_work, d_first (8 bytes) or
+ * d_count (4 bytes).
+ */
+int demod_frames_segments_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
+                                size_t n_windows, const uint64_t *d_first, const uint32_t *d_count,
+                                size_t n_segments, const uint8_t *sync, size_t sync_len,
+                                uint32_t max_errors, size_t frame_symbols, demod_frame_hit_t *d_hits,
+                                uint8_t *d_payload, uint8_t *d_packed, size_t max_frames,
+                                demod_frames_result_t *d_results, void *d_work, size_t work_bytes,
+                                void *stream);
+
+/*
+ * The handle's detector over the n_windows sliding windows of pcm (a host or
+ * device pointer, as demod_acquire), then the segmented frame scan of its
+ * outputs. first, count, hits ([n_segments][max_frames]), payload
+ * ([n_segments][max_frames][N]) and packed ([n_segments][max_frames][B];
+ * either may be NULL) and results are HOST memory; rows past a segment's
+ * n_written are left alone. The tables are checked here, as
+ * demod_acquire_segments checks them: a segment that leaves the batch or
+ * holds fewer than R windows is refused with DEMOD_BAD_ARG before the
+ * detector runs. The device keeps min(max_frames, longest / R + 1) rows per
+ * segment. Synchronous; handle-owned buffers grow on first use. Returns the
+ * sum of n_written or a negative code.
+ */
+int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, const uint64_t *first,
+                          const uint32_t *count, size_t n_segments, const uint8_t *sync,
+                          size_t sync_len, uint32_t max_errors, size_t frame_symbols,
+                          demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed,
+                          size_t max_frames, demod_frames_result_t *results);
+
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
  * n_streams independent streams that share one configuration, each behaving
