@@ -190,6 +190,33 @@ def frames_result_dict(r: "DemodFramesResult") -> dict:
     return out
 
 
+DEMOD_CRC16_CCITT_FALSE = 1
+DEMOD_CRC32_MPEG2 = 2
+DEMOD_CHECK_OK = 0
+DEMOD_CHECK_BAD_LENGTH = 1   # len > max_len; crc reported as 0
+DEMOD_CHECK_BAD_CRC = 2
+CRC_BYTES = {DEMOD_CRC16_CCITT_FALSE: 2, DEMOD_CRC32_MPEG2: 4}
+
+
+class DemodFrameCheck(ctypes.Structure):
+    """demod_frame_check_t (include/demod.h "checked frames"): one row's header
+    value, computed CRC, status and covered flag."""
+    _fields_ = [("length", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("status", ctypes.c_uint32),
+                ("covered", ctypes.c_uint32)]
+
+
+class DemodFramesCheckResult(ctypes.Structure):
+    """demod_frames_check_result_t: a group's rows checked, valid and kept."""
+    _fields_ = [("n_checked", ctypes.c_uint64), ("n_valid", ctypes.c_uint64), ("n_kept", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64)]
+
+
+FRAME_CHECK_DTYPE = np.dtype([("length", "<u4"), ("crc", "<u4"), ("status", "<u4"),
+                              ("covered", "<u4")])                                        # DemodFrameCheck
+FRAMES_CHECK_RESULT_DTYPE = np.dtype([("n_checked", "<u8"), ("n_valid", "<u8"), ("n_kept", "<u8"),
+                                      ("reserved", "<u8")])                     # DemodFramesCheckResult
+
+
 class DemodError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -268,6 +295,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                        _P]),
         "demod_frames_segments": (ctypes.c_int, [_P, _P, _SZ, _P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _SZ,
                                                  _P, _P, _P, _SZ, _P]),
+        "demod_crc": (ctypes.c_uint32, [ctypes.c_int, _P, _SZ]),
+        "demod_checked_frame_size": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int]),
+        "demod_checked_frame_encode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, _P, _SZ]),
+        "demod_frames_check_async": (ctypes.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, ctypes.c_int,
+                                                    ctypes.c_int, _P, _P, _P, _P, _P]),
+        "demod_frames_checked": (ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _SZ, ctypes.c_int,
+                                                ctypes.c_int, _P, _P, _P, _SZ,
+                                                ctypes.POINTER(DemodFramesResult),
+                                                ctypes.POINTER(DemodFramesCheckResult)]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -1007,6 +1043,102 @@ class Demodulator:
         if rc < 0:
             raise DemodError(rc, "demod_frames_segments_async")
 
+    def _checked_shape(self, frame_symbols: int, len_bytes: int, crc: int) -> Tuple[int, int]:
+        """(B, max_len) of a checked frame on rows of frame_symbols symbols."""
+        if len_bytes not in (1, 2) or crc not in CRC_BYTES:
+            raise DemodError(DEMOD_BAD_ARG, "len_bytes not 1 or 2, or an unknown crc kind")
+        B = (int(frame_symbols) * bits_per_symbol(self.k) + 7) // 8
+        max_len = B - len_bytes - CRC_BYTES[crc]
+        if max_len < 0 or max_len > DEMOD_MAX_FRAME_PAYLOAD:
+            raise DemodError(DEMOD_BAD_ARG, "rows too short for header and CRC, or max_len above "
+                                            "DEMOD_MAX_FRAME_PAYLOAD")
+        return B, max_len
+
+    def frames_check_async(self, d_hits, d_packed, d_results, n_groups: int, max_frames: int,
+                           sync_len: int, frame_symbols: int, len_bytes: int, crc: int, d_check, d_kept,
+                           d_body, d_summary, stream: int = 0) -> None:
+        """demod_frames_check_async on a frame scan's device outputs (n_groups =
+        1 after frames_async, = n_segments after frames_segments_async). d_hits
+        (uint8, n_groups * max_frames * sizeof(DemodFrameHit) bytes), d_packed
+        (uint8, n_groups * max_frames * B bytes) and d_results (uint8, n_groups
+        * sizeof(DemodFramesResult) bytes) are the scan's; d_check (uint8, 16
+        bytes a row), d_kept (int32, one a row), d_body (uint8, n_groups *
+        max_frames * max_len bytes, or None) and d_summary (uint8, n_groups *
+        sizeof(DemodFramesCheckResult) bytes) are written. Device tensors,
+        checked like the batch calls' (dtype, contiguity, device, size)."""
+        S, cap, L, N = int(n_groups), int(max_frames), int(sync_len), int(frame_symbols)
+        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31:
+            raise DemodError(DEMOD_BAD_ARG, "n_groups not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
+                                            "frame_symbols < 0 or n_groups * max_frames >= 2^31")
+        B, max_len = self._checked_shape(N, len_bytes, crc)
+        dev = int(self.cfg.device)
+        rows = S * cap
+        _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
+        _check_dev(d_packed, "d_packed", "uint8", rows * B, dev)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_check, "d_check", "uint8", rows * ctypes.sizeof(DemodFrameCheck), dev)
+        _check_dev(d_kept, "d_kept", "int32", rows, dev)
+        _check_dev(d_body, "d_body", "uint8", rows * max_len, dev, nullable=True)
+        _check_dev(d_summary, "d_summary", "uint8", S * ctypes.sizeof(DemodFramesCheckResult), dev)
+        rc = self._lib.demod_frames_check_async(
+            self._h, _ptr(d_hits), _ptr(d_packed), _ptr(d_results), S, cap, L, N, int(len_bytes), int(crc),
+            _ptr(d_check), _ptr(d_kept), _ptr(d_body) if d_body is not None else None, _ptr(d_summary),
+            stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_check_async")
+
+    def frames_checked(self, pcm, sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
+                       crc: int = DEMOD_CRC16_CCITT_FALSE, max_frames: Optional[int] = None,
+                       n_windows: Optional[int] = None, body: bool = True):
+        """demod_frames_checked: the detector over the sliding windows of pcm (a
+        host int16 array or a device tensor), the frame scan and the check of
+        its rows. Returns (hits: a FRAME_HIT_DTYPE array [n_kept], lengths
+        uint32 [n_kept], bodies: a list of n_kept bytes objects or None, the
+        scan's result dict, the check's summary dict): the kept frames alone."""
+        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
+        if host:
+            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+            size = flat.size
+        else:
+            size = int(pcm.numel())
+        if n_windows is None:
+            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
+        n_windows = int(n_windows)
+        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
+        if host:
+            if need > size:
+                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
+            buf = flat
+            if flat.ctypes.data % 16:
+                buf = np.empty(flat.size + 8, dtype=np.int16)
+                off = (-buf.ctypes.data % 16) // 2
+                buf = buf[off:off + flat.size]
+                buf[:] = flat
+        else:
+            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
+            buf = pcm
+        sync = _sync_bytes(sync)
+        N = int(frame_symbols)
+        if N < 0 or (max_frames is not None and max_frames < 1):
+            raise DemodError(DEMOD_BAD_ARG, "frame_symbols < 0 or max_frames < 1")
+        _, max_len = self._checked_shape(N, len_bytes, crc)
+        if max_frames is None:
+            max_frames = n_windows // max(self.n // self.hop, 1) + 1
+        cap = int(max_frames)
+        hits = np.zeros(cap, dtype=FRAME_HIT_DTYPE)
+        lengths = np.zeros(cap, dtype=np.uint32)
+        bod = np.zeros((cap, max(max_len, 1)), dtype=np.uint8) if body else None
+        res, summ = DemodFramesResult(), DemodFramesCheckResult()
+        rc = self._lib.demod_frames_checked(
+            self._h, _ptr(buf), n_windows, _ptr(sync) if sync.size else None, sync.size, int(max_errors), N,
+            int(len_bytes), int(crc), _ptr(hits), _ptr(lengths),
+            _ptr(bod) if bod is not None and max_len else None, cap, ctypes.byref(res), ctypes.byref(summ))
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_checked")
+        bodies = [bytes(bod[r, :int(lengths[r])]) for r in range(rc)] if bod is not None else None
+        summary = {f: int(getattr(summ, f)) for f, _ in DemodFramesCheckResult._fields_}
+        return hits[:rc], lengths[:rc], bodies, frames_result_dict(res), summary
+
 
 class Streams:
     """demod_streams_t: n_streams independent streams behind one detector,
@@ -1178,6 +1310,40 @@ def frame_encode(payload: bytes) -> bytes:
     rc = lib.demod_frame_encode(src, len(payload), out, cap)
     if rc < 0:
         raise DemodError(rc, "demod_frame_encode")
+    return bytes(out[:rc])
+
+
+def crc(kind: int, data: bytes) -> int:
+    """demod_crc: DEMOD_CRC16_CCITT_FALSE or DEMOD_CRC32_MPEG2 of data."""
+    if kind not in CRC_BYTES:
+        raise DemodError(DEMOD_BAD_ARG, "crc: unknown kind")
+    data = bytes(data)
+    src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    return int(load_library().demod_crc(kind, src, len(data)))
+
+
+def checked_frame_size(length: int, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE) -> int:
+    """demod_checked_frame_size: len_bytes + length + the CRC's bytes."""
+    rc = int(load_library().demod_checked_frame_size(int(length), int(len_bytes), int(crc)))
+    if rc < 0:
+        raise DemodError(rc, "demod_checked_frame_size")
+    return rc
+
+
+def checked_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE,
+                         cap: Optional[int] = None) -> bytes:
+    """demod_checked_frame_encode: len || data || CRC (include/demod.h "checked
+    frames"); unpack_symbols turns the bytes into symbols. cap: the output
+    room handed to the library (default: what the frame needs)."""
+    lib = load_library()
+    data = bytes(data)
+    if cap is None:
+        cap = len(data) + 8
+    src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    out = (ctypes.c_uint8 * max(int(cap), 1))()
+    rc = lib.demod_checked_frame_encode(src, len(data), int(len_bytes), int(crc), out, int(cap))
+    if rc < 0:
+        raise DemodError(rc, "demod_checked_frame_encode")
     return bytes(out[:rc])
 
 

@@ -1147,6 +1147,143 @@ int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, con
     return (int)total;
 }
 
+// ---- checked frames (frames_check.hip) ---------------------------------------
+
+// Fills what the shape decides (row width, max_len, the CRC's constants, R,
+// bits, L); false for what demod_frames_check_async refuses about it.
+static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_frames, size_t sync_len,
+                               size_t frame_symbols, int len_bytes, int crc, FramesCheckParams &p)
+{
+    if (!st) return false;
+    const uint32_t R = acquire_phases(st->cfg);
+    if (R == 0 || n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames == 0) return false;
+    if (max_frames > 0x7FFFFFFF || (unsigned long long)n_groups * max_frames > 0x7FFFFFFFull) return false;
+    if (sync_len == 0 || sync_len > DEMOD_MAX_SYNC || (len_bytes != 1 && len_bytes != 2)) return false;
+    if (crc != DEMOD_CRC16_CCITT_FALSE && crc != DEMOD_CRC32_MPEG2) return false;
+    const size_t bits = (size_t)demod_bits_per_symbol(st->cfg.k);
+    const size_t c = crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4, h = (size_t)len_bytes;
+    if (frame_symbols > 0x7FFFFFFF) return false;
+    const size_t B = (frame_symbols * bits + 7) / 8;
+    if (B < h + c || B - h - c > DEMOD_MAX_FRAME_PAYLOAD) return false;
+    p.n_groups = (unsigned)n_groups;
+    p.max_frames = (unsigned)max_frames;
+    p.row_bytes = (unsigned)B;
+    p.max_len = (unsigned)(B - h - c);
+    p.len_bytes = len_bytes;
+    p.crc_bytes = (int)c;
+    p.poly = c == 2 ? 0x1021u << 16 : 0x04C11DB7u;
+    p.init = c == 2 ? 0xFFFFu << 16 : 0xFFFFFFFFu;
+    // x^8, then its squares mod P (Horner over the square's own coefficients, highest first)
+    static_assert(DEMOD_MAX_FRAME_PAYLOAD + 2 < (1 << kCrcPowBits), "bytes after a lane's chunk");
+    const int width = 8 * (int)c;
+    p.xpow8[0] = 1u << (32 - width + 8);
+    for (int j = 1; j < kCrcPowBits; ++j) {
+        const uint32_t a = p.xpow8[j - 1];
+        uint32_t r = 0, b = a;
+        for (int i = 0; i < width; ++i, b <<= 1)
+            r = (r << 1) ^ ((r >> 31) ? p.poly : 0u) ^ ((b >> 31) ? a : 0u);
+        p.xpow8[j] = r;
+    }
+    p.bits = (int)bits;
+    p.phases = (int)R;
+    p.sync_len = (int)sync_len;
+    return true;
+}
+
+int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_packed,
+                             const demod_frames_result_t *d_results, size_t n_groups,
+                             size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                             int crc, demod_frame_check_t *d_check, uint32_t *d_kept, uint8_t *d_body,
+                             demod_frames_check_result_t *d_summary, void *stream)
+{
+    if (!st || !d_hits || !d_packed || !d_results || !d_check || !d_kept || !d_summary) return DEMOD_BAD_ARG;
+    if (((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_summary & 7) != 0 ||
+        ((uintptr_t)d_check & 3) != 0 || ((uintptr_t)d_kept & 3) != 0)
+        return DEMOD_BAD_ARG;
+    FramesCheckParams p;
+    std::memset(&p, 0, sizeof(p));
+    if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, p))
+        return DEMOD_BAD_ARG;
+    p.hits = d_hits;
+    p.packed = d_packed;
+    p.res = d_results;
+    p.check = d_check;
+    p.kept = d_kept;
+    p.body = d_body;
+    p.summary = d_summary;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_frames_check(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                         size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
+                         int crc, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
+                         size_t max_frames, demod_frames_result_t *result,
+                         demod_frames_check_result_t *summary)
+{
+    if (!pcm || !result || !summary || !hits || !lengths || ((uintptr_t)pcm & 15) != 0) return DEMOD_BAD_ARG;
+    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
+    if (R == 0) return DEMOD_BAD_ARG;   // before the detector runs
+    // complete hits are starts on one phase whose frame fits: W / R + 1 bounds them
+    const size_t dcap = std::min(max_frames, n_windows / R + 1);
+    FramesCheckParams p;
+    std::memset(&p, 0, sizeof(p));
+    if (!frames_check_shape(st, 1, dcap, sync_len, frame_symbols, len_bytes, crc, p)) return DEMOD_BAD_ARG;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
+    const bool din = is_device_ptr(pcm);
+    const size_t N = frame_symbols, B = p.row_bytes, M = p.max_len;
+    const bool want_body = body && M;
+    int rc;
+    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
+    const size_t work = demod_frames_workspace_size(&st->cfg, n_windows);
+    HIP_TRY(st->d_frm_work.reserve(work));  // bytes
+    HIP_TRY(st->d_frm_res.reserve(1));
+    HIP_TRY(st->d_frm_hits.reserve(dcap));
+    HIP_TRY(st->d_frm_packed.reserve(dcap * B));
+    HIP_TRY(st->d_chk_check.reserve(dcap));
+    HIP_TRY(st->d_chk_kept.reserve(dcap));
+    HIP_TRY(st->d_chk_sum.reserve(1));
+    HIP_TRY(st->d_chk_hits.reserve(dcap));
+    HIP_TRY(st->d_chk_len.reserve(dcap));
+    if (want_body) HIP_TRY(st->d_chk_body.reserve(dcap * M));
+    if (!din)
+        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
+                               st->stream));
+    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
+    if (rc < 0) return rc;
+    rc = demod_frames_async(st, st->d_sym.p, st->d_mag.p, n_windows, sync, sync_len, max_errors, N,
+                            st->d_frm_hits.p, nullptr, st->d_frm_packed.p, dcap, st->d_frm_res.p,
+                            st->d_frm_work.p, work, st->stream);
+    if (rc < 0) return rc;
+    rc = demod_frames_check_async(st, st->d_frm_hits.p, st->d_frm_packed.p, st->d_frm_res.p, 1, dcap,
+                                  sync_len, N, len_bytes, crc, st->d_chk_check.p, st->d_chk_kept.p,
+                                  want_body ? st->d_chk_body.p : nullptr, st->d_chk_sum.p, st->stream);
+    if (rc < 0) return rc;
+    // the kept rows' hits and lengths side by side, so that only they cross to the host
+    HIP_TRY(launch_frames_kept_rows(st->d_frm_hits.p, st->d_chk_check.p, st->d_chk_kept.p, st->d_chk_sum.p,
+                                    (unsigned)dcap, st->d_chk_hits.p, st->d_chk_len.p, st->stream));
+    HIP_TRY(hipMemcpyAsync(result, st->d_frm_res.p, sizeof(*result), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipMemcpyAsync(summary, st->d_chk_sum.p, sizeof(*summary), hipMemcpyDeviceToHost, st->stream));
+    HIP_TRY(hipStreamSynchronize(st->stream));
+    const size_t nk = (size_t)summary->n_kept;
+    if (nk) {
+        HIP_TRY(hipMemcpy(hits, st->d_chk_hits.p, nk * sizeof(*hits), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(lengths, st->d_chk_len.p, nk * sizeof(*lengths), hipMemcpyDeviceToHost));
+        if (want_body) {
+            // a body row holds its frame's bytes alone: the rest of the caller's row is left as it is
+            st->h_chk_body.resize(nk * M);
+            HIP_TRY(hipMemcpy(st->h_chk_body.data(), st->d_chk_body.p, nk * M, hipMemcpyDeviceToHost));
+            for (size_t r = 0; r < nk; ++r)
+                std::memcpy(body + r * M, st->h_chk_body.data() + r * M, lengths[r]);
+        }
+    }
+    return (int)nk;
+}
+
 int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,
                           uint64_t *first, uint32_t *count, size_t *n_windows)
 {

@@ -164,6 +164,15 @@ struct demod {
     fskd::PinnedBuf<demod_frame_hit_t> h_fsg_hits;   // the rows on their way to the caller's [S][max_frames]
     fskd::PinnedBuf<uint8_t> h_fsg_payload;
     fskd::PinnedBuf<uint8_t> h_fsg_packed;
+    // demod_frames_checked: the check's outputs over demod_frames' rows (d_frm_*), then
+    // the kept rows' hits and lengths side by side (first use)
+    fskd::DevBuf<demod_frame_check_t> d_chk_check;
+    fskd::DevBuf<uint32_t> d_chk_kept;
+    fskd::DevBuf<uint8_t> d_chk_body;
+    fskd::DevBuf<demod_frames_check_result_t> d_chk_sum;
+    fskd::DevBuf<demod_frame_hit_t> d_chk_hits;
+    fskd::DevBuf<uint32_t> d_chk_len;
+    std::vector<uint8_t> h_chk_body;    // the body rows on their way to the caller's bytes
     fskd::PinnedBuf<int16_t> h_in;      // pinned staging for small host calls
     fskd::PinnedBuf<uint8_t> h_sym;
     fskd::PinnedBuf<float> h_mag;       // [h_sym.cap][k]

@@ -9,6 +9,8 @@
 struct demod_acquire_result;  // include/demod.h
 struct demod_frames_result;
 struct demod_frame_hit;
+struct demod_frame_check;
+struct demod_frames_check_result;
 
 namespace fskd {
 
@@ -329,5 +331,38 @@ constexpr size_t frames_seg_budget(size_t bytes, size_t R)
 }
 void launch_acquire_seg_plan(const AcquireSegParams &p, hipStream_t s);
 hipError_t launch_frames_segments(const FrameSegParams &q, hipStream_t s);
+
+// frames_check.hip: length, CRC and overlap of the rows a frame scan wrote
+// (group g owns rows g max_frames + i, i < min(res[g].n_written, max_frames)).
+// No workspace: select reads what check stored in `check`, body what select
+// stored in `kept` and `summary`.
+constexpr int kCrcPowBits = 13;           // a row's header and data are below 2^13 bytes
+struct FramesCheckParams {
+    const ::demod_frame_hit *hits;        // [n_groups][max_frames]
+    const uint8_t *packed;                // [n_groups][max_frames][row_bytes]
+    const ::demod_frames_result *res;     // [n_groups]
+    unsigned n_groups;
+    unsigned max_frames;                  // n_groups * max_frames < 2^31
+    unsigned row_bytes;                   // B = ceil(N bits / 8)
+    unsigned max_len;                     // B - len_bytes - crc_bytes <= DEMOD_MAX_FRAME_PAYLOAD
+    int len_bytes;                        // h: 1 or 2
+    int crc_bytes;                        // c: 2 or 4
+    unsigned poly, init;                  // in the top 8 c bits of the word
+    unsigned xpow8[kCrcPowBits];          // x^(8 2^j) mod P, as the register
+    int bits;                             // demod_bits_per_symbol(k)
+    int phases;                           // R
+    int sync_len;                         // L
+    ::demod_frame_check *check;           // [n_groups][max_frames]
+    uint32_t *kept;                       // [n_groups][max_frames]
+    uint8_t *body;                        // [n_groups][max_frames][max_len] or nullptr
+    ::demod_frames_check_result *summary; // [n_groups]
+};
+hipError_t launch_frames_check(const FramesCheckParams &p, hipStream_t s);
+// One group's kept rows side by side, for the synchronous wrapper: out_hits[r] =
+// hits[kept[r]], out_len[r] = check[kept[r]].length, r < min(summary->n_kept, max_frames).
+hipError_t launch_frames_kept_rows(const ::demod_frame_hit *hits, const ::demod_frame_check *check,
+                                   const uint32_t *kept, const ::demod_frames_check_result *summary,
+                                   unsigned max_frames, ::demod_frame_hit *out_hits, uint32_t *out_len,
+                                   hipStream_t s);
 
 }  // namespace fskd

@@ -538,7 +538,8 @@ int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_
  * listed like any other, so `hits` is NOT a list of disjoint frames. Random
  * symbols hold the word at a rate of about C(L, <= max_errors) / K^L per
  * start, and a greedy hold-off is serial in the worst case; callers settle it
- * with the frame's own header or CRC.
+ * with the frame's own header or CRC ("checked frames" below does it on the
+ * device for one frame format).
  *
  * Streaming: a caller that keeps its samples from tail_window on (or, with
  * tail_window == -1, from the first start on the phase whose word no longer
@@ -702,6 +703,130 @@ int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, con
                           size_t sync_len, uint32_t max_errors, size_t frame_symbols,
                           demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed,
                           size_t max_frames, demod_frames_result_t *results);
+
+/* ---- checked frames: length, CRC and overlap after a frame scan --------- */
+/*
+ * The frame scans above list every sync-word hit with a fixed-length row, false
+ * hits and hits inside other frames included. This stage reads the rows they
+ * wrote, on the device, and keeps the frames that check out. The frame is
+ * defined on the packed row (B = ceil(N bits / 8) bytes, MSB first, as
+ * demod_pack_symbols), with h = len_bytes in {1, 2} and c = 2 or 4 by CRC kind:
+ *
+ *   byte 0 .. h-1          len, big-endian
+ *   byte h .. h+len-1      data
+ *   byte h+len .. +c-1     CRC, big-endian, over bytes 0 .. h+len-1 (the length
+ *                          field included)
+ *   the rest of the row    ignored
+ *
+ *   max_len = B - h - c (a call with B < h + c is refused). A frame occupies
+ *   L + S symbols: the word, then S = ceil((h + len + c) 8 / bits).
+ *
+ * Both CRC kinds are non-reflected with xorout 0:
+ *
+ *   DEMOD_CRC16_CCITT_FALSE  width 16, poly 0x1021, init 0xFFFF
+ *                            (CRC of "123456789": 0x29B1)
+ *   DEMOD_CRC32_MPEG2        width 32, poly 0x04C11DB7, init 0xFFFFFFFF
+ *                            (CRC of "123456789": 0x0376E6E7)
+ *
+ * Groups and rows: group g < n_groups owns rows g max_frames + i, i < nw_g =
+ * min(d_results[g].n_written, max_frames): what demod_frames_async (n_groups =
+ * 1) or demod_frames_segments_async (n_groups = S) wrote for that batch or
+ * segment, in ascending window order. The counts are read on the device and
+ * clamped there; no content of d_results, d_hits or d_packed makes a kernel
+ * read outside the rows or write outside the outputs. For each row i < nw_g:
+ *
+ *   length   the header value.
+ *   status   DEMOD_CHECK_BAD_LENGTH when length > max_len (nothing past the
+ *            header is read; crc is reported as 0); else crc = the CRC computed
+ *            over bytes 0 .. h+len-1, and DEMOD_CHECK_BAD_CRC when the stored
+ *            one differs, DEMOD_CHECK_OK otherwise.
+ *   covered  with end_j = window_j + (L + S_j) R (64-bit, wrapping): 1 when
+ *            row i is OK and some OK row j < i of the group has end_j >
+ *            window_i, else 0. An exclusive prefix maximum over the OK rows:
+ *            parallel and the same on every run. It is NOT the serial greedy
+ *            hold-off (which lets a frame covered only by a covered frame
+ *            through): the prefix maximum drops a superset of what greedy
+ *            drops, and the two differ only when frames that pass their CRC
+ *            overlap each other.
+ *   kept     OK and not covered. d_kept[g max_frames + r] is the row index i
+ *            of the group's r-th kept row, ascending; d_body[(g max_frames +
+ *            r) max_len + b] is data byte b of that row, b < length (d_body
+ *            may be NULL).
+ *
+ * d_summary[g] = {nw_g, rows OK, rows kept, 0}. Written: every byte of d_check
+ * rows i < nw_g and of d_summary[0 .. n_groups); kept entries r < n_kept; body
+ * bytes b < length of body rows r < n_kept. Nothing else.
+ */
+#define DEMOD_CRC16_CCITT_FALSE 1
+#define DEMOD_CRC32_MPEG2       2
+
+#define DEMOD_CHECK_OK          0
+#define DEMOD_CHECK_BAD_LENGTH  1   /* len > max_len; crc reported as 0 */
+#define DEMOD_CHECK_BAD_CRC     2
+
+typedef struct demod_frame_check {
+    uint32_t length, crc /* computed */, status, covered;
+} demod_frame_check_t;
+
+typedef struct demod_frames_check_result {
+    uint64_t n_checked, n_valid, n_kept, reserved;
+} demod_frames_check_result_t;
+
+/* The CRC of data[0 .. len) by kind (0 for an unknown kind). No device needed. */
+uint32_t demod_crc(int crc, const uint8_t *data, size_t len);
+
+/* Bytes of a checked frame of len data bytes, h + len + c; DEMOD_BAD_ARG for a
+ * bad kind or len_bytes, DEMOD_FRAME_TOO_LARGE for len above 256^h - 1 or
+ * DEMOD_MAX_FRAME_PAYLOAD. */
+long long demod_checked_frame_size(size_t len, int len_bytes, int crc);
+
+/* The transmit side: len || data || CRC into out[0 .. cap); demod_unpack_symbols
+ * turns the bytes into symbols (with a 0 byte behind them where bits does not
+ * divide 8 (h + len + c): the last symbol's missing bits). Returns the bytes written, what
+ * demod_checked_frame_size refuses, or DEMOD_BUFFER_TOO_SMALL. */
+int demod_checked_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc,
+                               uint8_t *out, size_t cap);
+
+/*
+ * Enqueued on `stream`: three launches whatever the counts are (check, select,
+ * body; two when d_body is NULL or max_len == 0). No workspace; nothing is
+ * allocated or synchronised and the handle keeps no state of the call, so it
+ * can be captured behind demod_frames[_segments]_async and replayed. No atomic
+ * decides a position; every output byte is a function of the inputs alone. R
+ * and bits come from the handle's configuration; sync_len and frame_symbols are
+ * the frame scan's. d_hits, d_packed and d_results are the frame scan's outputs
+ * ([n_groups][max_frames] rows, [n_groups] results); d_check and d_kept are
+ * [n_groups][max_frames], d_body [n_groups][max_frames][max_len], d_summary
+ * [n_groups]. Returns DEMOD_OK once enqueued; DEMOD_BAD_ARG, before any launch,
+ * for a NULL handle or pointer (d_body excepted), a misaligned d_hits,
+ * d_results or d_summary (8 bytes), d_check or d_kept (4 bytes), n_groups == 0
+ * or above DEMOD_MAX_SEGMENTS, max_frames == 0, n_groups * max_frames >= 2^31,
+ * sync_len outside 1 .. DEMOD_MAX_SYNC, a bad len_bytes or crc, n % hop != 0 or
+ * R > DEMOD_MAX_PHASES, B < h + c, or max_len > DEMOD_MAX_FRAME_PAYLOAD.
+ */
+int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_packed,
+                             const demod_frames_result_t *d_results, size_t n_groups,
+                             size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                             int crc, demod_frame_check_t *d_check, uint32_t *d_kept, uint8_t *d_body,
+                             demod_frames_check_result_t *d_summary, void *stream);
+
+/*
+ * The handle's detector over the n_windows sliding windows of pcm (a host or
+ * device pointer, as demod_acquire), the frame scan of its outputs and the
+ * check of the scan's rows. Only the kept frames come back: hits[r], lengths[r]
+ * and body[r max_len .. r max_len + lengths[r]) for r < n_kept (body may be
+ * NULL; bytes past a frame's length are left alone), HOST memory of max_frames
+ * rows, with *result the scan's and *summary the check's. result->n_hits >
+ * result->n_written says that max_frames cut the scan. Synchronous;
+ * handle-owned buffers grow on first use. Returns n_kept or a negative code
+ * (DEMOD_BAD_ARG for what demod_frames and demod_frames_check_async refuse,
+ * before the detector runs).
+ */
+int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                         size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
+                         int crc, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
+                         size_t max_frames, demod_frames_result_t *result,
+                         demod_frames_check_result_t *summary);
 
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
