@@ -101,6 +101,95 @@ def family(name, freqs, n, blocks, seed):
     return np.clip(np.round(v), -32768, 32767).astype(np.int16).reshape(-1)
 
 
+def tie_run(freqs, n, length, rng):
+    """`length` samples of which EVERY n-sample window, wherever it starts, is
+    a near tie of plan tones (the blocks of `two_tone_equal` carry a new pair
+    and new phases each, so only windows that start on a block do tie).
+    Every tone on an integer bin: two plan tones at amplitude 12000 each,
+    phase-continuous over the run; any n consecutive samples hold whole
+    periods of both, so both powers are (6000 n)^2 exactly and the rounding to
+    int16 sets the margin, the same in every window of the run (the rounded
+    samples have period n too): parts in 10^5 at n = 64, more than the fold
+    detector's threshold there, so of 64 draws of the two phases the one with
+    the smallest margin over a period is kept. Other plans (leakage between the
+    tones would decide): an impulse every n samples, so each window holds
+    exactly one and |X_k| is its amplitude at every frequency. Both over a
+    dither of +-1 on one sample in 64 (n < 1024: in 65536 / n, a sample's
+    share of |X_k| grows as n falls), which moves each window's margin by
+    parts in 10^6 of P_max, far above the first pass's band and far below the
+    flag threshold.
+
+    The limit of the impulse windows: only the segment that holds the impulse
+    has a state that is not dither, and |X_k| does not depend on the phase it
+    is rotated by, so on the off-bin plans a rotation row of the wrong phase
+    (or a run's state rotated into its neighbour's phase) leaves a rescued
+    power unchanged to fp32; those windows see a row whose modulus is off, a
+    wrong segment state and a stale or missing store. The rotation's phase
+    is held by the integer-bin plans' two-tone windows, where all 16 segments
+    carry the tones. (No off-bin signal ties in every sliding window with
+    energy in more than one segment: a second impulse at distance d adds 2 a b
+    cos(w_k d) to |X_k|^2, equal for two tones only where (f_1 +- f_2) d / fs
+    is an integer.)"""
+    f = np.asarray(freqs, np.float64)
+    bins = f * n / FS
+    t = np.arange(length)
+    if np.abs(bins - np.round(bins)).max() < 1e-9:
+        a, b = rng.choice(len(freqs), 2, replace=False)
+        ka, kb = (int(k) for k in np.round(bins[[a, b]]))
+        best, tn = None, np.arange(n)
+        for ph in rng.uniform(0, 2 * np.pi, (64, 2)):
+            u = 12000 * (np.sin(2 * np.pi * f[a] / FS * tn + ph[0]) + np.sin(2 * np.pi * f[b] / FS * tn + ph[1]))
+            P = np.abs(np.fft.rfft(np.round(u))[[ka, kb]]) ** 2
+            m = abs(P[0] - P[1]) / P.max()
+            if best is None or m < best[0]:
+                best = (m, ph)
+        ph = best[1]
+        v = 12000 * (np.sin(2 * np.pi * f[a] / FS * t + ph[0]) + np.sin(2 * np.pi * f[b] / FS * t + ph[1]))
+    else:
+        v = np.zeros(length)
+        at = np.arange(int(rng.integers(0, n)), length, n)
+        v[at] = rng.integers(12000, 30000, at.size) * rng.choice([-1, 1], at.size)
+    v = v + np.where(rng.random(length) < min(1.0 / 64, n / 65536.0), rng.choice([-1.0, 1.0], length), 0.0)
+    return np.clip(np.round(v), -32768, 32767).astype(np.int16)
+
+
+def mixed_stream(freqs, blocks, seed):
+    """Runs of 1..40 1024-sample blocks alternating between two tones at equal
+    power (near ties) and clean FSK at sigma 400."""
+    n = 1024
+    rng = np.random.default_rng(seed)
+    tie = family("two_tone_equal", freqs, n, blocks, seed)
+    fsk = family("fsk_s400", freqs, n, blocks, seed + 1)
+    out = np.empty(blocks * n, np.int16)
+    b, use_tie = 0, bool(rng.integers(0, 2))
+    while b < blocks:
+        r = int(rng.integers(1, 41))
+        e = min(blocks, b + r)
+        src = tie if use_tie else fsk
+        out[b * n:e * n] = src[b * n:e * n]
+        b, use_tie = e, not use_tie
+    return out
+
+
+def mixed_stream_windows(freqs, blocks, seed, hop):
+    """mixed_stream for the rescued-magnitude tests: `blocks` 1024-sample
+    blocks of clean FSK at sigma 400 in which runs of near ties are laid, the
+    runs counted in windows at `hop`, 1..40 windows wholly inside each, and
+    the near ties tie_run's. So the windows off a multiple of n tie as well,
+    and a run of r windows is r consecutive flagged windows at every hop."""
+    n = 1024
+    rng = np.random.default_rng(seed)
+    out = family("fsk_s400", freqs, n, blocks, seed + 1).copy()
+    pos, use_tie = 0, bool(rng.integers(0, 2))
+    while pos < out.size:
+        r = int(rng.integers(1, 41))
+        e = min(out.size, pos + -(-((r - 1) * hop + n) // hop) * hop)
+        if use_tie:
+            out[pos:e] = tie_run(freqs, n, e - pos, rng)
+        pos, use_tie = e, not use_tie
+    return out
+
+
 def window_energies(x, n, hop, W):
     """(raw sum x^2, folded sum xf^2) per window, exact."""
     idx = np.arange(W)[:, None] * hop + np.arange(n)[None, :]

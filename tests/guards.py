@@ -38,6 +38,11 @@ flagged, so that the rescue is reached at the edges where they are placed
 (`edge_stream`). A flagged window's symbol and magnitudes are stored by the
 rescue, not by the detector's epilogue, so each shape also runs with clean FSK
 windows at the same edges: those leave by the epilogue's own stores.
+
+`clear_mask` is sure_mask's counterpart (windows no detector flags) and
+`rescue_fixture` the window classes and fixture conditions of the
+rescued-magnitude tests (tests/test_gpu_rescue_mags.py); neither needs a
+device.
 """
 import contextlib
 import math
@@ -184,6 +189,53 @@ def sure_mask(model, n, xw, ref_P):
         NE = float(n) * (xw * xw).sum(axis=1)
     Ps = np.sort(np.asarray(ref_P, np.float64), axis=1)
     return (Ps[:, -1] - Ps[:, -2]) < 0.5 * model["tau"] * np.sqrt(NE * Ps[:, -1])
+
+
+def clear_mask(model, n, xw, ref_P):
+    """Windows no detector flags, by the oracle and the error model alone: the
+    oracle's top-2 margin above 4 tau sqrt(NE P_max), eight times sure_mask's
+    line. With a = sqrt P_1, b = sqrt P_2 of the oracle and d = tau sqrt(NE) /
+    4 the two derived bounds' sum, the margin (a - b)(a + b) > 16 d a gives
+    a - b > 8 d; the fp32 roots a', b' are within d of them, so the fp32
+    margin is at least 6 d (a' + b') >= 6 d a', above the flag line tau
+    sqrt(NE_eff) a' = 4 d a' (and above the FFT's, whose Parseval energy is at
+    most twice n sum x^2: 5.7 d a')."""
+    W = xw.shape[0]
+    if model["energy"] == 1:   # ENERGY_FOLDED
+        xf = xw.reshape(W, 8, n // 8).sum(axis=1)
+        NE = (n / 8.0) * (xf * xf).sum(axis=1)
+    else:
+        NE = float(n) * (xw * xw).sum(axis=1)
+    Ps = np.sort(np.asarray(ref_P, np.float64), axis=1)
+    return (Ps[:, -1] - Ps[:, -2]) > 4.0 * model["tau"] * np.sqrt(NE * Ps[:, -1])
+
+
+def longest_run(mask):
+    """Length of the longest run of consecutive True."""
+    m = np.concatenate([[0], np.asarray(mask, np.int8), [0]])
+    edges = np.flatnonzero(np.diff(m))
+    return int((edges[1::2] - edges[::2]).max()) if edges.size else 0
+
+
+def rescue_fixture(model, x, n, hop, W, ref_P):
+    """The window classes of a stream of near-tie runs beside clean FSK
+    (error_model.mixed_stream_windows; near_tie_windows with a tie_run) that
+    the rescued-magnitude tests stand on, from the oracle's powers and the error
+    model alone (no device): `sure` (flagged whatever the fp32 rounding does),
+    `clear` (never flagged), `off` (start off a multiple of n: another tile
+    position, carried sums). Asserts the fixture conditions: at least 32 sure
+    windows, 8 of them off a multiple of n where hop < n, one run of 8 or
+    more consecutive sure windows (a dense run of the rescue launch), and 32
+    clear windows beside them."""
+    xw = windows_of(x, n, hop, W)
+    sure = sure_mask(model, n, xw, ref_P)
+    clear = clear_mask(model, n, xw, ref_P)
+    off = (np.arange(W) * hop) % n != 0
+    assert sure.sum() >= 32, int(sure.sum())
+    assert hop == n or (sure & off).sum() >= 8, int((sure & off).sum())
+    assert clear.sum() >= 32, int(clear.sum())
+    assert longest_run(sure) >= 8, longest_run(sure)
+    return {"xw": xw, "sure": sure, "clear": clear, "off": off}
 
 
 def edge_windows(W, T):

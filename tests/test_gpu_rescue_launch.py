@@ -18,6 +18,8 @@ import numpy as np
 import pytest
 
 import error_model as EM
+from decision import check_decisions
+from error_model import mixed_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -34,23 +36,6 @@ def torch():
     return t
 
 
-def mixed_stream(freqs, blocks, seed):
-    """Runs of 1..40 n-sample blocks alternating between two tones at equal
-    power (near ties) and clean FSK at sigma 400."""
-    rng = np.random.default_rng(seed)
-    tie = EM.family("two_tone_equal", freqs, N, blocks, seed)
-    fsk = EM.family("fsk_s400", freqs, N, blocks, seed + 1)
-    out = np.empty(blocks * N, np.int16)
-    b, use_tie = 0, bool(rng.integers(0, 2))
-    while b < blocks:
-        r = int(rng.integers(1, 41))
-        e = min(blocks, b + r)
-        src = tie if use_tie else fsk
-        out[b * N:e * N] = src[b * N:e * N]
-        b, use_tie = e, not use_tie
-    return out
-
-
 def run(A, O, freqs, hop, W, seed, expect_slide=True):
     blocks = -(-((W - 1) * hop + N) // N)
     x = mixed_stream(freqs, blocks, seed)[:(W - 1) * hop + N]
@@ -59,10 +44,14 @@ def run(A, O, freqs, hop, W, seed, expect_slide=True):
             assert d.slide_windows > 0
         assert d.rescue_tau64 > 0
         sym = d.batch(x, n_windows=W)
-    rs, _ = O.goertzel(x, freqs, N, hop=hop, fs=EM.FS, threads=16)
+        sym_m, mag = d.batch(x, n_windows=W, mags=True)
+    rs, rP = O.goertzel(x, freqs, N, hop=hop, fs=EM.FS, threads=16)
     assert not (sym & 0x80).any()
     bad = np.flatnonzero(sym != rs[:W])
     assert bad.size == 0, bad[:8].tolist()
+    # with magnitudes: the same symbols, each the argmax of the stored powers
+    assert np.array_equal(sym_m, sym)
+    check_decisions(sym_m, mag, rs[:W], rP[:W])
 
 
 @pytest.mark.parametrize("H", list(range(1, 16)))
