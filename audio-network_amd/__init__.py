@@ -217,6 +217,23 @@ FRAMES_CHECK_RESULT_DTYPE = np.dtype([("n_checked", "<u8"), ("n_valid", "<u8"), 
                                       ("reserved", "<u8")])                     # DemodFramesCheckResult
 
 
+DEMOD_FEC_CONV_K7 = 1
+DEMOD_FEC_DEPTH = 64
+DEMOD_DECODE_OK = 0
+DEMOD_DECODE_BAD_LENGTH = 1   # len > max_len; metric and steps 0
+
+
+class DemodFrameDecode(ctypes.Structure):
+    """demod_frame_decode_t (include/demod.h "coded frames"): one row's decoded
+    length, path metric, status and trellis steps."""
+    _fields_ = [("length", ctypes.c_uint32), ("metric", ctypes.c_int32), ("status", ctypes.c_uint32),
+                ("steps", ctypes.c_uint32)]
+
+
+FRAME_DECODE_DTYPE = np.dtype([("length", "<u4"), ("metric", "<i4"), ("status", "<u4"),
+                               ("steps", "<u4")])                                         # DemodFrameDecode
+
+
 class DemodError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -304,6 +321,23 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                 ctypes.c_int, _P, _P, _P, _SZ,
                                                 ctypes.POINTER(DemodFramesResult),
                                                 ctypes.POINTER(DemodFramesCheckResult)]),
+        "demod_coded_frame_steps": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int]),
+        "demod_coded_frame_symbols": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+        "demod_coded_frame_encode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, _P, _SZ]),
+        "demod_coded_row_bytes": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int]),
+        "demod_soft_bits": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
+        "demod_coded_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, _P, _SZ,
+                                                    ctypes.POINTER(DemodFrameDecode)]),
+        "demod_frames_decode_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), _SZ, _SZ, _SZ]),
+        "demod_frames_decode_async": (ctypes.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, _SZ,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P,
+                                                     _SZ, _P]),
+        "demod_frames_check_coded_async": (ctypes.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, _P]),
+        "demod_frames_coded": (ctypes.c_int, [_P, _P, _SZ, _P, _SZ, ctypes.c_uint32, _SZ, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, _P, _P, _P, _SZ,
+                                              ctypes.POINTER(DemodFramesResult),
+                                              ctypes.POINTER(DemodFramesCheckResult)]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -516,6 +550,19 @@ def segments_layout(cfg: DemodCfg, n_samples):
 
 def _sync_bytes(sync) -> np.ndarray:
     return np.zeros(0, np.uint8) if sync is None else np.ascontiguousarray(sync, dtype=np.uint8).reshape(-1)
+
+
+def frames_decode_workspace_size(cfg: DemodCfg, n_groups: int, max_frames: int, frame_symbols: int) -> int:
+    """demod_frames_decode_workspace_size: bytes of d_work a decode of n_groups
+    x max_frames rows of frame_symbols symbols needs (no GPU). Raises
+    DemodError(DEMOD_BAD_ARG) where it is 0."""
+    if n_groups < 0 or max_frames < 0 or frame_symbols < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_frames_decode_workspace_size")
+    size = int(load_library().demod_frames_decode_workspace_size(ctypes.byref(cfg), int(n_groups),
+                                                                int(max_frames), int(frame_symbols)))
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_frames_decode_workspace_size")
+    return size
 
 
 def _ptr(a) -> int:
@@ -1087,6 +1134,86 @@ class Demodulator:
         if rc < 0:
             raise DemodError(rc, "demod_frames_check_async")
 
+    def _coded_shape(self, frame_symbols: int, len_bytes: int, crc: int) -> Tuple[int, int, int]:
+        """(St, Bd, max_len) of coded rows of frame_symbols symbols."""
+        if len_bytes not in (1, 2) or crc not in CRC_BYTES:
+            raise DemodError(DEMOD_BAD_ARG, "len_bytes not 1 or 2, or an unknown crc kind")
+        bits = bits_per_symbol(self.k)
+        if self.k != 1 << bits:
+            raise DemodError(DEMOD_BAD_ARG, "coded frames need K = 2^bits tones")
+        St = int(frame_symbols) * bits // 2
+        if St < 8 * len_bytes + DEMOD_FEC_DEPTH:
+            raise DemodError(DEMOD_BAD_ARG, "rows shorter than the header look-ahead")
+        Bd = (St - 6) // 8
+        max_len = Bd - len_bytes - CRC_BYTES[crc]
+        if max_len < 0 or max_len > DEMOD_MAX_FRAME_PAYLOAD:
+            raise DemodError(DEMOD_BAD_ARG, "max_len above DEMOD_MAX_FRAME_PAYLOAD")
+        return St, Bd, max_len
+
+    def frames_decode_async(self, d_hits, d_mag, n_windows: int, d_first, d_results, n_groups: int,
+                            max_frames: int, sync_len: int, frame_symbols: int, len_bytes: int, crc: int,
+                            d_rows, d_decode, d_work, fec: int = DEMOD_FEC_CONV_K7, stream: int = 0) -> None:
+        """demod_frames_decode_async on a frame scan's device outputs (n_groups =
+        1 and d_first None after frames_async; n_groups = n_segments and the
+        scan's d_first, an int64 tensor holding the uint64 table, after
+        frames_segments_async). d_hits and d_results are the scan's, d_mag
+        (float32, n_windows * k) the detector's; d_rows (uint8, n_groups *
+        max_frames * Bd bytes) and d_decode (uint8, 16 bytes a row) are
+        written; d_work (uint8, at least frames_decode_workspace_size bytes)
+        may hold anything. Device tensors, checked like the batch calls'."""
+        W, S, cap, L, N = int(n_windows), int(n_groups), int(max_frames), int(sync_len), int(frame_symbols)
+        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31 or W < 0 or W >= 2 ** 31:
+            raise DemodError(DEMOD_BAD_ARG, "n_groups not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
+                                            "frame_symbols < 0, n_groups * max_frames >= 2^31 or "
+                                            "n_windows not in 0 .. 2^31 - 1")
+        if fec != DEMOD_FEC_CONV_K7:
+            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        _, Bd, _ = self._coded_shape(N, len_bytes, crc)
+        dev = int(self.cfg.device)
+        rows = S * cap
+        _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
+        _check_dev(d_mag, "d_mag", "float32", max(W, 1) * self.k, dev)
+        _check_dev(d_first, "d_first", "int64", S, dev, nullable=True)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_rows, "d_rows", "uint8", rows * Bd, dev)
+        _check_dev(d_decode, "d_decode", "uint8", rows * ctypes.sizeof(DemodFrameDecode), dev)
+        _check_dev(d_work, "d_work", "uint8", frames_decode_workspace_size(self.cfg, S, cap, N), dev)
+        rc = self._lib.demod_frames_decode_async(
+            self._h, _ptr(d_hits), _ptr(d_mag), W, _ptr(d_first) if d_first is not None else None,
+            _ptr(d_results), S, cap, L, N, int(len_bytes), int(crc), int(fec), _ptr(d_rows), _ptr(d_decode),
+            _ptr(d_work), int(d_work.numel()), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_decode_async")
+
+    def frames_check_coded_async(self, d_hits, d_rows, d_results, n_groups: int, max_frames: int,
+                                 sync_len: int, frame_symbols: int, len_bytes: int, crc: int, d_check, d_kept,
+                                 d_body, d_summary, fec: int = DEMOD_FEC_CONV_K7, stream: int = 0) -> None:
+        """demod_frames_check_coded_async: frames_check_async over the rows
+        frames_decode_async wrote (uint8, n_groups * max_frames * Bd bytes),
+        with max_len = Bd - len_bytes - the CRC's bytes and the coded span."""
+        S, cap, L, N = int(n_groups), int(max_frames), int(sync_len), int(frame_symbols)
+        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31:
+            raise DemodError(DEMOD_BAD_ARG, "n_groups not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
+                                            "frame_symbols < 0 or n_groups * max_frames >= 2^31")
+        if fec != DEMOD_FEC_CONV_K7:
+            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        _, Bd, max_len = self._coded_shape(N, len_bytes, crc)
+        dev = int(self.cfg.device)
+        rows = S * cap
+        _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
+        _check_dev(d_rows, "d_rows", "uint8", rows * Bd, dev)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_check, "d_check", "uint8", rows * ctypes.sizeof(DemodFrameCheck), dev)
+        _check_dev(d_kept, "d_kept", "int32", rows, dev)
+        _check_dev(d_body, "d_body", "uint8", rows * max_len, dev, nullable=True)
+        _check_dev(d_summary, "d_summary", "uint8", S * ctypes.sizeof(DemodFramesCheckResult), dev)
+        rc = self._lib.demod_frames_check_coded_async(
+            self._h, _ptr(d_hits), _ptr(d_rows), _ptr(d_results), S, cap, L, N, int(len_bytes), int(crc),
+            int(fec), _ptr(d_check), _ptr(d_kept), _ptr(d_body) if d_body is not None else None,
+            _ptr(d_summary), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_check_coded_async")
+
     def frames_checked(self, pcm, sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
                        crc: int = DEMOD_CRC16_CCITT_FALSE, max_frames: Optional[int] = None,
                        n_windows: Optional[int] = None, body: bool = True):
@@ -1095,6 +1222,23 @@ class Demodulator:
         its rows. Returns (hits: a FRAME_HIT_DTYPE array [n_kept], lengths
         uint32 [n_kept], bodies: a list of n_kept bytes objects or None, the
         scan's result dict, the check's summary dict): the kept frames alone."""
+        return self._frames_checked(pcm, sync, max_errors, frame_symbols, len_bytes, crc, 0, max_frames,
+                                    n_windows, body)
+
+    def frames_coded(self, pcm, sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
+                     crc: int = DEMOD_CRC16_CCITT_FALSE, fec: int = DEMOD_FEC_CONV_K7,
+                     max_frames: Optional[int] = None, n_windows: Optional[int] = None, body: bool = True):
+        """demod_frames_coded: frames_checked for coded frames (include/demod.h
+        "coded frames"): detector, frame scan, soft-decision decode of its rows
+        and the coded check. Returns what frames_checked returns."""
+        if fec != DEMOD_FEC_CONV_K7:
+            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        return self._frames_checked(pcm, sync, max_errors, frame_symbols, len_bytes, crc, int(fec), max_frames,
+                                    n_windows, body)
+
+    def _frames_checked(self, pcm, sync, max_errors, frame_symbols, len_bytes, crc, fec, max_frames,
+                        n_windows, body):
+        """frames_checked (fec 0) and frames_coded."""
         host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
         if host:
             flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
@@ -1121,7 +1265,7 @@ class Demodulator:
         N = int(frame_symbols)
         if N < 0 or (max_frames is not None and max_frames < 1):
             raise DemodError(DEMOD_BAD_ARG, "frame_symbols < 0 or max_frames < 1")
-        _, max_len = self._checked_shape(N, len_bytes, crc)
+        _, max_len = self._coded_shape(N, len_bytes, crc)[1:] if fec else self._checked_shape(N, len_bytes, crc)
         if max_frames is None:
             max_frames = n_windows // max(self.n // self.hop, 1) + 1
         cap = int(max_frames)
@@ -1129,12 +1273,16 @@ class Demodulator:
         lengths = np.zeros(cap, dtype=np.uint32)
         bod = np.zeros((cap, max(max_len, 1)), dtype=np.uint8) if body else None
         res, summ = DemodFramesResult(), DemodFramesCheckResult()
-        rc = self._lib.demod_frames_checked(
-            self._h, _ptr(buf), n_windows, _ptr(sync) if sync.size else None, sync.size, int(max_errors), N,
-            int(len_bytes), int(crc), _ptr(hits), _ptr(lengths),
-            _ptr(bod) if bod is not None and max_len else None, cap, ctypes.byref(res), ctypes.byref(summ))
+        head = (self._h, _ptr(buf), n_windows, _ptr(sync) if sync.size else None, sync.size, int(max_errors), N,
+                int(len_bytes), int(crc))
+        tail = (_ptr(hits), _ptr(lengths), _ptr(bod) if bod is not None and max_len else None, cap,
+                ctypes.byref(res), ctypes.byref(summ))
+        if fec:
+            rc = self._lib.demod_frames_coded(*head, fec, *tail)
+        else:
+            rc = self._lib.demod_frames_checked(*head, *tail)
         if rc < 0:
-            raise DemodError(rc, "demod_frames_checked")
+            raise DemodError(rc, "demod_frames_coded" if fec else "demod_frames_checked")
         bodies = [bytes(bod[r, :int(lengths[r])]) for r in range(rc)] if bod is not None else None
         summary = {f: int(getattr(summ, f)) for f, _ in DemodFramesCheckResult._fields_}
         return hits[:rc], lengths[:rc], bodies, frames_result_dict(res), summary
@@ -1345,6 +1493,76 @@ def checked_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16
     if rc < 0:
         raise DemodError(rc, "demod_checked_frame_encode")
     return bytes(out[:rc])
+
+
+def coded_frame_steps(length: int, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE) -> int:
+    """demod_coded_frame_steps: T(len), the trellis steps of a coded frame."""
+    rc = int(load_library().demod_coded_frame_steps(int(length), int(len_bytes), int(crc)))
+    if rc < 0:
+        raise DemodError(rc, "demod_coded_frame_steps")
+    return rc
+
+
+def coded_frame_symbols(length: int, len_bytes: int, crc: int, bits: int) -> int:
+    """demod_coded_frame_symbols: Sc = ceil(2 T(len) / bits)."""
+    rc = int(load_library().demod_coded_frame_symbols(int(length), int(len_bytes), int(crc), int(bits)))
+    if rc < 0:
+        raise DemodError(rc, "demod_coded_frame_symbols")
+    return rc
+
+
+def coded_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE,
+                       cap: Optional[int] = None) -> bytes:
+    """demod_coded_frame_encode: the coded bits of len || data || CRC (include/
+    demod.h "coded frames"); unpack_symbols turns the bytes into symbols. cap:
+    the output room handed to the library (default: what the frame needs)."""
+    lib = load_library()
+    data = bytes(data)
+    if cap is None:
+        cap = 2 * len(data) + 32
+    src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    out = (ctypes.c_uint8 * max(int(cap), 1))()
+    rc = lib.demod_coded_frame_encode(src, len(data), int(len_bytes), int(crc), out, int(cap))
+    if rc < 0:
+        raise DemodError(rc, "demod_coded_frame_encode")
+    return bytes(out[:rc])
+
+
+def coded_row_bytes(frame_symbols: int, bits: int, len_bytes: int = 2) -> int:
+    """demod_coded_row_bytes: Bd, the decoded bytes of rows of frame_symbols symbols."""
+    if frame_symbols < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_coded_row_bytes")
+    rc = int(load_library().demod_coded_row_bytes(int(frame_symbols), int(bits), int(len_bytes)))
+    if rc < 0:
+        raise DemodError(rc, "demod_coded_row_bytes")
+    return rc
+
+
+def soft_bits(powers) -> np.ndarray:
+    """demod_soft_bits: the int8 soft values [bits] of one window's K powers."""
+    p = np.ascontiguousarray(powers, dtype=np.float32).reshape(-1)
+    out = np.zeros(8, dtype=np.int8)
+    rc = load_library().demod_soft_bits(_ptr(p) if p.size else None, p.size, _ptr(out))
+    if rc < 0:
+        raise DemodError(rc, "demod_soft_bits")
+    return out[:rc].copy()
+
+
+def coded_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE,
+                       cap: Optional[int] = None) -> Tuple[bytes, dict]:
+    """demod_coded_frame_decode: the host decoder on int8 soft values. Returns
+    (the row bytes written, the decode record as a dict). cap: the row room
+    handed to the library (default: Bd)."""
+    q = np.ascontiguousarray(soft, dtype=np.int8).reshape(-1)
+    if cap is None:
+        cap = max((q.size // 2 - 6) // 8, 0)
+    row = np.zeros(max(int(cap), 1), dtype=np.uint8)
+    dec = DemodFrameDecode()
+    rc = load_library().demod_coded_frame_decode(_ptr(q) if q.size else None, q.size, int(len_bytes),
+                                                 int(crc), _ptr(row), int(cap), ctypes.byref(dec))
+    if rc < 0:
+        raise DemodError(rc, "demod_coded_frame_decode")
+    return row[:rc].tobytes(), {f: int(getattr(dec, f)) for f, _ in DemodFrameDecode._fields_}
 
 
 def frame_decode(buf: bytes) -> Tuple[bytes, int]:

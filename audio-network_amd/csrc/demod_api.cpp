@@ -1152,7 +1152,8 @@ int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, con
 // Fills what the shape decides (row width, max_len, the CRC's constants, R,
 // bits, L); false for what demod_frames_check_async refuses about it.
 static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_frames, size_t sync_len,
-                               size_t frame_symbols, int len_bytes, int crc, FramesCheckParams &p)
+                               size_t frame_symbols, int len_bytes, int crc, FramesCheckParams &p,
+                               int fec = 0)
 {
     if (!st) return false;
     const uint32_t R = acquire_phases(st->cfg);
@@ -1163,7 +1164,15 @@ static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_fr
     const size_t bits = (size_t)demod_bits_per_symbol(st->cfg.k);
     const size_t c = crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4, h = (size_t)len_bytes;
     if (frame_symbols > 0x7FFFFFFF) return false;
-    const size_t B = (frame_symbols * bits + 7) / 8;
+    size_t B = (frame_symbols * bits + 7) / 8;
+    if (fec) {
+        // coded rows: St = floor(N bits / 2) steps decode to Bd = (St - 6) / 8 bytes
+        const size_t St = frame_symbols * bits / 2;
+        if (fec != DEMOD_FEC_CONV_K7 || st->cfg.k != (1u << bits)) return false;
+        if (St < 8 * h + DEMOD_FEC_DEPTH) return false;
+        B = (St - 6) / 8;
+        p.fec_depth = DEMOD_FEC_DEPTH;
+    }
     if (B < h + c || B - h - c > DEMOD_MAX_FRAME_PAYLOAD) return false;
     p.n_groups = (unsigned)n_groups;
     p.max_frames = (unsigned)max_frames;
@@ -1190,11 +1199,12 @@ static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_fr
     return true;
 }
 
-int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_packed,
-                             const demod_frames_result_t *d_results, size_t n_groups,
-                             size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
-                             int crc, demod_frame_check_t *d_check, uint32_t *d_kept, uint8_t *d_body,
-                             demod_frames_check_result_t *d_summary, void *stream)
+// fec 0: the scan's packed rows; else decoded rows (the coded entry has refused fec 0)
+static int frames_check_enqueue(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_packed,
+                                const demod_frames_result_t *d_results, size_t n_groups,
+                                size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                                int crc, int fec, demod_frame_check_t *d_check, uint32_t *d_kept,
+                                uint8_t *d_body, demod_frames_check_result_t *d_summary, void *stream)
 {
     if (!st || !d_hits || !d_packed || !d_results || !d_check || !d_kept || !d_summary) return DEMOD_BAD_ARG;
     if (((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_summary & 7) != 0 ||
@@ -1202,7 +1212,7 @@ int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const
         return DEMOD_BAD_ARG;
     FramesCheckParams p;
     std::memset(&p, 0, sizeof(p));
-    if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, p))
+    if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, p, fec))
         return DEMOD_BAD_ARG;
     p.hits = d_hits;
     p.packed = d_packed;
@@ -1217,11 +1227,94 @@ int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const
     return DEMOD_OK;
 }
 
-int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
-                         size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
-                         int crc, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
-                         size_t max_frames, demod_frames_result_t *result,
-                         demod_frames_check_result_t *summary)
+int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_packed,
+                             const demod_frames_result_t *d_results, size_t n_groups,
+                             size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                             int crc, demod_frame_check_t *d_check, uint32_t *d_kept, uint8_t *d_body,
+                             demod_frames_check_result_t *d_summary, void *stream)
+{
+    return frames_check_enqueue(st, d_hits, d_packed, d_results, n_groups, max_frames, sync_len,
+                                frame_symbols, len_bytes, crc, 0, d_check, d_kept, d_body, d_summary, stream);
+}
+
+// ---- coded frames (frames_fec.hip) -------------------------------------------
+
+size_t demod_frames_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
+                                          size_t frame_symbols)
+{
+    if (validate_cfg(cfg) != DEMOD_OK || cfg->k < 2 || (cfg->k & (cfg->k - 1)) != 0) return 0;
+    if (n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames == 0 || max_frames > 0x7FFFFFFF) return 0;
+    if ((unsigned long long)n_groups * max_frames > 0x7FFFFFFFull) return 0;
+    if (frame_symbols == 0 || frame_symbols > 0x7FFFFFFF) return 0;
+    const size_t St = frame_symbols * (size_t)demod_bits_per_symbol(cfg->k) / 2;
+    return n_groups * (size_t)fec_waves_per_group((unsigned)n_groups, (unsigned)max_frames) * St * 8;
+}
+
+int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, const float *d_mags,
+                              size_t n_windows, const uint64_t *d_first,
+                              const demod_frames_result_t *d_results, size_t n_groups,
+                              size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                              int crc, int fec, uint8_t *d_rows, demod_frame_decode_t *d_decode,
+                              void *d_work, size_t work_bytes, void *stream)
+{
+    if (!st || !d_hits || !d_mags || !d_results || !d_rows || !d_decode || !d_work) return DEMOD_BAD_ARG;
+    if (((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_work & 7) != 0 ||
+        ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_decode & 3) != 0)
+        return DEMOD_BAD_ARG;
+    if (fec != DEMOD_FEC_CONV_K7 || n_windows > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    FramesCheckParams q;   // the shape the coded check will see: the same refusals
+    std::memset(&q, 0, sizeof(q));
+    if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, q, fec))
+        return DEMOD_BAD_ARG;
+    if ((sync_len + frame_symbols) * (size_t)q.phases > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const size_t need = demod_frames_decode_workspace_size(&st->cfg, n_groups, max_frames, frame_symbols);
+    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
+    FramesFecParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.hits = d_hits;
+    p.mag = d_mags;
+    p.first = reinterpret_cast<const unsigned long long *>(d_first);
+    p.res = d_results;
+    p.n_windows = (unsigned)n_windows;
+    p.n_groups = q.n_groups;
+    p.max_frames = q.max_frames;
+    p.frame_symbols = (unsigned)frame_symbols;
+    p.steps = (unsigned)(frame_symbols * (size_t)q.bits / 2);
+    p.row_bytes = q.row_bytes;
+    p.max_len = q.max_len;
+    p.len_bytes = q.len_bytes;
+    p.crc_bytes = q.crc_bytes;
+    p.k = (int)st->cfg.k;
+    p.bits = q.bits;
+    p.phases = q.phases;
+    p.sync_len = q.sync_len;
+    p.rows = d_rows;
+    p.decode = d_decode;
+    p.work = static_cast<unsigned long long *>(d_work);
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_frames_decode(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+int demod_frames_check_coded_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_rows,
+                                   const demod_frames_result_t *d_results, size_t n_groups,
+                                   size_t max_frames, size_t sync_len, size_t frame_symbols,
+                                   int len_bytes, int crc, int fec, demod_frame_check_t *d_check,
+                                   uint32_t *d_kept, uint8_t *d_body,
+                                   demod_frames_check_result_t *d_summary, void *stream)
+{
+    if (fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    return frames_check_enqueue(st, d_hits, d_rows, d_results, n_groups, max_frames, sync_len,
+                                frame_symbols, len_bytes, crc, fec, d_check, d_kept, d_body, d_summary, stream);
+}
+
+// demod_frames_checked (fec 0: the scan's packed rows) and demod_frames_coded
+static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                              size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
+                              int crc, int fec, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
+                              size_t max_frames, demod_frames_result_t *result,
+                              demod_frames_check_result_t *summary)
 {
     if (!pcm || !result || !summary || !hits || !lengths || ((uintptr_t)pcm & 15) != 0) return DEMOD_BAD_ARG;
     const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
@@ -1230,7 +1323,8 @@ int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, cons
     const size_t dcap = std::min(max_frames, n_windows / R + 1);
     FramesCheckParams p;
     std::memset(&p, 0, sizeof(p));
-    if (!frames_check_shape(st, 1, dcap, sync_len, frame_symbols, len_bytes, crc, p)) return DEMOD_BAD_ARG;
+    if (!frames_check_shape(st, 1, dcap, sync_len, frame_symbols, len_bytes, crc, p, fec)) return DEMOD_BAD_ARG;
+    const size_t fec_work = fec ? demod_frames_decode_workspace_size(&st->cfg, 1, dcap, frame_symbols) : 0;
     DeviceGuard guard(st->device);
     HIP_TRY(guard.err);
     const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
@@ -1243,7 +1337,13 @@ int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, cons
     HIP_TRY(st->d_frm_work.reserve(work));  // bytes
     HIP_TRY(st->d_frm_res.reserve(1));
     HIP_TRY(st->d_frm_hits.reserve(dcap));
-    HIP_TRY(st->d_frm_packed.reserve(dcap * B));
+    if (fec) {
+        HIP_TRY(st->d_fec_rows.reserve(dcap * B));
+        HIP_TRY(st->d_fec_decode.reserve(dcap));
+        HIP_TRY(st->d_fec_work.reserve(fec_work));  // bytes
+    } else {
+        HIP_TRY(st->d_frm_packed.reserve(dcap * B));
+    }
     HIP_TRY(st->d_chk_check.reserve(dcap));
     HIP_TRY(st->d_chk_kept.reserve(dcap));
     HIP_TRY(st->d_chk_sum.reserve(1));
@@ -1256,12 +1356,19 @@ int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, cons
     rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
     if (rc < 0) return rc;
     rc = demod_frames_async(st, st->d_sym.p, st->d_mag.p, n_windows, sync, sync_len, max_errors, N,
-                            st->d_frm_hits.p, nullptr, st->d_frm_packed.p, dcap, st->d_frm_res.p,
-                            st->d_frm_work.p, work, st->stream);
+                            st->d_frm_hits.p, nullptr, fec ? nullptr : st->d_frm_packed.p, dcap,
+                            st->d_frm_res.p, st->d_frm_work.p, work, st->stream);
     if (rc < 0) return rc;
-    rc = demod_frames_check_async(st, st->d_frm_hits.p, st->d_frm_packed.p, st->d_frm_res.p, 1, dcap,
-                                  sync_len, N, len_bytes, crc, st->d_chk_check.p, st->d_chk_kept.p,
-                                  want_body ? st->d_chk_body.p : nullptr, st->d_chk_sum.p, st->stream);
+    if (fec) {
+        rc = demod_frames_decode_async(st, st->d_frm_hits.p, st->d_mag.p, n_windows, nullptr, st->d_frm_res.p,
+                                       1, dcap, sync_len, N, len_bytes, crc, fec, st->d_fec_rows.p,
+                                       st->d_fec_decode.p, st->d_fec_work.p, fec_work, st->stream);
+        if (rc < 0) return rc;
+    }
+    rc = frames_check_enqueue(st, st->d_frm_hits.p, fec ? st->d_fec_rows.p : st->d_frm_packed.p,
+                              st->d_frm_res.p, 1, dcap, sync_len, N, len_bytes, crc, fec, st->d_chk_check.p,
+                              st->d_chk_kept.p, want_body ? st->d_chk_body.p : nullptr, st->d_chk_sum.p,
+                              st->stream);
     if (rc < 0) return rc;
     // the kept rows' hits and lengths side by side, so that only they cross to the host
     HIP_TRY(launch_frames_kept_rows(st->d_frm_hits.p, st->d_chk_check.p, st->d_chk_kept.p, st->d_chk_sum.p,
@@ -1282,6 +1389,27 @@ int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, cons
         }
     }
     return (int)nk;
+}
+
+int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                         size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
+                         int crc, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
+                         size_t max_frames, demod_frames_result_t *result,
+                         demod_frames_check_result_t *summary)
+{
+    return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
+                              0, hits, lengths, body, max_frames, result, summary);
+}
+
+int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                       size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
+                       int crc, int fec, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
+                       size_t max_frames, demod_frames_result_t *result,
+                       demod_frames_check_result_t *summary)
+{
+    if (fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
+                              fec, hits, lengths, body, max_frames, result, summary);
 }
 
 int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,

@@ -1,0 +1,192 @@
+/*
+ * demod_fec.c — the host side of the coded frame (include/demod.h "coded
+ * frames", DESIGN.md §4.9 "Coded frames"): the constraint-length-7, rate-1/2
+ * convolutional encoder (0171/0133) over a checked frame's bytes, the soft
+ * values of one window's tone powers, and the soft-decision Viterbi decoder
+ * the device (frames_fec.hip) is held to, bit for bit. Integer arithmetic
+ * apart from one double expression per soft value. Pure host work, no device.
+ */
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../include/demod.h"
+
+#define FEC_G0 0171u
+#define FEC_G1 0133u
+#define FEC_STATES 64
+
+static unsigned parity7(unsigned v)
+{
+    v ^= v >> 4;
+    v ^= v >> 2;
+    v ^= v >> 1;
+    return v & 1u;
+}
+
+/* c: the CRC's bytes, or 0 for an unknown kind */
+static size_t crc_bytes(int crc)
+{
+    return crc == DEMOD_CRC16_CCITT_FALSE ? 2 : crc == DEMOD_CRC32_MPEG2 ? 4 : 0;
+}
+
+long long demod_coded_frame_steps(size_t len, int len_bytes, int crc)
+{
+    const long long n = demod_checked_frame_size(len, len_bytes, crc);
+    if (n < 0) return n;
+    const long long body = 8 * n + 6, least = 8 * (long long)len_bytes + DEMOD_FEC_DEPTH;
+    return body > least ? body : least;
+}
+
+long long demod_coded_frame_symbols(size_t len, int len_bytes, int crc, int bits)
+{
+    const long long T = demod_coded_frame_steps(len, len_bytes, crc);
+    if (T < 0) return T;
+    if (bits < 1 || bits > 4) return DEMOD_BAD_ARG;
+    return (2 * T + bits - 1) / bits;
+}
+
+int demod_coded_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, uint8_t *out,
+                             size_t cap)
+{
+    const long long T = demod_coded_frame_steps(len, len_bytes, crc);
+    if (T < 0) return (int)T;
+    if ((!data && len) || !out) return DEMOD_BAD_ARG;
+    const size_t need = (size_t)(2 * T + 7) / 8;
+    if (need > cap) return DEMOD_BUFFER_TOO_SMALL;
+    uint8_t info[2 + DEMOD_MAX_FRAME_PAYLOAD + 4];
+    const int n = demod_checked_frame_encode(data, len, len_bytes, crc, info, sizeof(info));
+    if (n < 0) return n;
+    memset(out, 0, need);
+    unsigned reg = 0;
+    for (long long t = 0; t < T; ++t) {
+        const unsigned u = t < 8 * (long long)n ? (info[t >> 3] >> (7 - (t & 7))) & 1u : 0u;
+        reg = ((reg << 1) | u) & 0x7Fu;
+        const unsigned v0 = parity7(reg & FEC_G0), v1 = parity7(reg & FEC_G1);
+        out[(2 * t) >> 3] |= (uint8_t)(v0 << (7 - ((2 * t) & 7)));
+        out[(2 * t + 1) >> 3] |= (uint8_t)(v1 << (7 - ((2 * t + 1) & 7)));
+    }
+    return (int)need;
+}
+
+long long demod_coded_row_bytes(size_t frame_symbols, int bits, int len_bytes)
+{
+    if (bits < 1 || bits > 4 || (len_bytes != 1 && len_bytes != 2) || frame_symbols > 0x7FFFFFFF)
+        return DEMOD_BAD_ARG;
+    const long long St = (long long)frame_symbols * bits / 2;
+    if (St < 8 * len_bytes + DEMOD_FEC_DEPTH) return DEMOD_BAD_ARG;
+    return (St - 6) / 8;
+}
+
+int demod_soft_bits(const float *powers, uint32_t k, int8_t *soft)
+{
+    if (!powers || !soft || k < 2 || k > DEMOD_MAX_TONES || (k & (k - 1)) != 0) return DEMOD_BAD_ARG;
+    const int bits = demod_bits_per_symbol(k);
+    for (int b = 0; b < bits; ++b) {
+        const uint32_t m = 1u << (bits - 1 - b);
+        /* each maximum from the lowest such tone, replaced by a strictly greater one alone */
+        float a0 = powers[0], a1 = powers[m];
+        for (uint32_t i = 1; i < k; ++i) {
+            if (i & m) {
+                if (powers[i] > a1) a1 = powers[i];
+            } else if (powers[i] > a0) {
+                a0 = powers[i];
+            }
+        }
+        const double d = (double)a0 - (double)a1, s = fabs((double)a0) + fabs((double)a1);
+        soft[b] = (s > 0.0 && s <= 1.7976931348623157e308) ? (int8_t)(int)rint(127.0 * d / s) : 0;
+    }
+    return bits;
+}
+
+/* u_t of steps t_end-1 .. 0 from state s at step t_end, into bits[] (one byte a bit) */
+static void trace_back(const uint64_t *surv, size_t t_end, unsigned s, uint8_t *bits)
+{
+    for (size_t t = t_end; t-- > 0;) {
+        bits[t] = (uint8_t)(s & 1u);
+        s = (s >> 1) | ((unsigned)((surv[t] >> s) & 1u) << 5);
+    }
+}
+
+static void forward(const int8_t *soft, size_t t_from, size_t t_to, int32_t *M, uint64_t *surv)
+{
+    for (size_t t = t_from; t < t_to; ++t) {
+        const int32_t q0 = soft[2 * t], q1 = soft[2 * t + 1];
+        int32_t next[FEC_STATES];
+        uint64_t word = 0;
+        for (unsigned s = 0; s < FEC_STATES; ++s) {
+            const unsigned p0 = s >> 1, p1 = p0 | 32u;
+            int32_t sum[2];
+            for (int j = 0; j < 2; ++j) {
+                const unsigned reg = (((j ? p1 : p0) << 1) | (s & 1u)) & 0x7Fu;
+                const int32_t bm = (parity7(reg & FEC_G0) ? -q0 : q0) + (parity7(reg & FEC_G1) ? -q1 : q1);
+                sum[j] = M[j ? p1 : p0] + bm;
+            }
+            const int d = sum[1] > sum[0];
+            next[s] = d ? sum[1] : sum[0];
+            word |= (uint64_t)d << s;
+        }
+        memcpy(M, next, sizeof(next));
+        surv[t] = word;
+    }
+}
+
+int demod_coded_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, uint8_t *row,
+                             size_t cap, demod_frame_decode_t *decode)
+{
+    const size_t c = crc_bytes(crc), h = (size_t)len_bytes;
+    if (!soft || !row || !decode || c == 0 || (len_bytes != 1 && len_bytes != 2)) return DEMOD_BAD_ARG;
+    if (n_soft > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const size_t St = n_soft / 2, t0 = 8 * h + DEMOD_FEC_DEPTH;
+    if (St < t0) return DEMOD_BAD_ARG;
+    const size_t Bd = (St - 6) / 8;
+    if (Bd < h + c || Bd - h - c > DEMOD_MAX_FRAME_PAYLOAD) return DEMOD_BAD_ARG;
+    if (cap < Bd) return DEMOD_BUFFER_TOO_SMALL;
+    const size_t max_len = Bd - h - c;
+    uint64_t *surv = (uint64_t *)malloc(St * sizeof(uint64_t));
+    uint8_t *bits = (uint8_t *)malloc(St);
+    if (!surv || !bits) {
+        free(surv);
+        free(bits);
+        return DEMOD_ALLOC_FAIL;
+    }
+    int32_t M[FEC_STATES];
+    M[0] = 0;
+    for (unsigned s = 1; s < FEC_STATES; ++s) M[s] = -(1 << 28);
+    forward(soft, 0, t0, M, surv);
+    unsigned best = 0;
+    for (unsigned s = 1; s < FEC_STATES; ++s)
+        if (M[s] > M[best]) best = s;
+    trace_back(surv, t0, best, bits);
+    size_t len = 0;
+    for (size_t t = 0; t < 8 * h; ++t) len = (len << 1) | bits[t];
+    int written;
+    if (len > max_len) {
+        decode->length = (uint32_t)len;
+        decode->metric = 0;
+        decode->status = DEMOD_DECODE_BAD_LENGTH;
+        decode->steps = 0;
+        for (size_t b = 0; b < h; ++b) row[b] = (uint8_t)(len >> (8 * (h - 1 - b)));
+        written = (int)h;
+    } else {
+        const size_t n = h + len + c;
+        const size_t T = 8 * n + 6 > t0 ? 8 * n + 6 : t0;   /* <= St: n <= Bd */
+        forward(soft, t0, T, M, surv);
+        trace_back(surv, T, 0, bits);
+        for (size_t b = 0; b < n; ++b) {
+            unsigned v = 0;
+            for (int i = 0; i < 8; ++i) v = (v << 1) | bits[8 * b + i];
+            row[b] = (uint8_t)v;
+        }
+        decode->length = (uint32_t)len;
+        decode->metric = M[0];
+        decode->status = DEMOD_DECODE_OK;
+        decode->steps = (uint32_t)T;
+        written = (int)n;
+    }
+    free(surv);
+    free(bits);
+    return written;
+}

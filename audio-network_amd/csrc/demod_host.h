@@ -173,6 +173,10 @@ struct demod {
     fskd::DevBuf<demod_frame_hit_t> d_chk_hits;
     fskd::DevBuf<uint32_t> d_chk_len;
     std::vector<uint8_t> h_chk_body;    // the body rows on their way to the caller's bytes
+    // demod_frames_coded: the decoded rows, their reports and the survivor words (first use)
+    fskd::DevBuf<uint8_t> d_fec_rows;
+    fskd::DevBuf<demod_frame_decode_t> d_fec_decode;
+    fskd::DevBuf<unsigned char> d_fec_work;
     fskd::PinnedBuf<int16_t> h_in;      // pinned staging for small host calls
     fskd::PinnedBuf<uint8_t> h_sym;
     fskd::PinnedBuf<float> h_mag;       // [h_sym.cap][k]

@@ -11,6 +11,7 @@ struct demod_frames_result;
 struct demod_frame_hit;
 struct demod_frame_check;
 struct demod_frames_check_result;
+struct demod_frame_decode;
 
 namespace fskd {
 
@@ -352,6 +353,7 @@ struct FramesCheckParams {
     int bits;                             // demod_bits_per_symbol(k)
     int phases;                           // R
     int sync_len;                         // L
+    int fec_depth;                        // 0: S = ceil(8 n / bits); DEMOD_FEC_DEPTH: the coded span
     ::demod_frame_check *check;           // [n_groups][max_frames]
     uint32_t *kept;                       // [n_groups][max_frames]
     uint8_t *body;                        // [n_groups][max_frames][max_len] or nullptr
@@ -364,5 +366,37 @@ hipError_t launch_frames_kept_rows(const ::demod_frame_hit *hits, const ::demod_
                                    const uint32_t *kept, const ::demod_frames_check_result *summary,
                                    unsigned max_frames, ::demod_frame_hit *out_hits, uint32_t *out_len,
                                    hipStream_t s);
+
+// frames_fec.hip: soft values and Viterbi decode of the rows a frame scan
+// listed (groups and rows as frames_check.hip). One wave per row; wave v of the
+// launch keeps the survivor words of its current row in work[v steps ..).
+constexpr unsigned kFecMaxWaves = 16384;  // waves per call (or one per group), as the check's
+constexpr unsigned fec_waves_per_group(unsigned n_groups, unsigned max_frames)
+{
+    const unsigned most = kFecMaxWaves / n_groups ? kFecMaxWaves / n_groups : 1;
+    return max_frames < most ? max_frames : most;
+}
+struct FramesFecParams {
+    const ::demod_frame_hit *hits;        // [n_groups][max_frames]
+    const float *mag;                     // [n_windows][k]
+    const unsigned long long *first;      // [n_groups] or nullptr: every base 0
+    const ::demod_frames_result *res;     // [n_groups]
+    unsigned n_windows;                   // < 2^31
+    unsigned n_groups;
+    unsigned max_frames;                  // n_groups * max_frames < 2^31
+    unsigned frame_symbols;               // N
+    unsigned steps;                       // St = floor(N bits / 2)
+    unsigned row_bytes;                   // Bd = (St - 6) / 8
+    unsigned max_len;                     // Bd - len_bytes - crc_bytes
+    int len_bytes;                        // h
+    int crc_bytes;                        // c
+    int k, bits;                          // k = 2^bits
+    int phases;                           // R
+    int sync_len;                         // L; (L + N) R < 2^31
+    uint8_t *rows;                        // [n_groups][max_frames][row_bytes]
+    struct ::demod_frame_decode *decode;  // [n_groups][max_frames] (struct: demod.h has a function of the name)
+    unsigned long long *work;             // [waves of the launch][steps]
+};
+hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s);
 
 }  // namespace fskd

@@ -27,7 +27,9 @@
 //          row's own window: a wave scan by shuffle, wave totals through LDS. A
 //          kept row's rank is the rows kept before the chunk, in the waves
 //          before (LDS) and in the lanes before (ballot), as frames_emit_kernel:
-//          ascending by construction. covered, kept, summary.
+//          ascending by construction. covered, kept, summary. A frame's span on
+//          the air is its bytes' symbols, or with fec_depth (the coded check
+//          over frames_fec.hip's rows) its 2 T(len) coded bits' symbols.
 //  body    one thread per data byte of the kept rows, coalesced along the byte
 //          index; reads n_kept, kept and length as select and check left them.
 //
@@ -146,7 +148,13 @@ __global__ __launch_bounds__(kAcqThreads) void frames_select_kernel(FramesCheckP
             if (in && p.check[row0 + i].status == DEMOD_CHECK_OK) {
                 ok = true;
                 window = p.hits[row0 + i].window;
-                const unsigned S = ((hc + p.check[row0 + i].length) * 8 + bits - 1) / bits;
+                // the frame's bits on the air: its bytes, or coded 2 T(len) (include/demod.h "coded frames")
+                unsigned span = (hc + p.check[row0 + i].length) * 8;
+                if (p.fec_depth) {
+                    const unsigned least = 8u * (unsigned)p.len_bytes + (unsigned)p.fec_depth;
+                    span = 2u * (span + 6u > least ? span + 6u : least);
+                }
+                const unsigned S = (span + bits - 1) / bits;
                 end = window + (L + S) * R;
             }
             // inclusive maximum over the lanes up to this one, then over the waves before

@@ -1,0 +1,185 @@
+// frames_fec.hip — coded frames (include/demod.h "coded frames", DESIGN.md §4.9
+// "Coded frames"): the soft values of the rows a frame scan listed, from the
+// detector's per-tone powers, and their soft-decision Viterbi decode under the
+// constraint-length-7, rate-1/2 code 0171/0133. The 64 trellis states are one
+// wave: lane = state. Groups and rows as frames_check.hip: group g owns rows
+// g max_frames + i, i < nw_g = min(res[g].n_written, max_frames), the count
+// read and clamped here; wave c of a group's wpg waves takes rows c, c + wpg, ..
+// One launch, no atomics; every output byte is a function of the inputs alone
+// (demod_fec.c's demod_coded_frame_decode restates it on the host).
+//
+//  soft     64 values at a time, one per lane: value m = j bits + b of the row
+//           reads the K powers of window base + window + (L + j) R and keeps
+//           the largest with bit b clear and with bit b set. A window at or
+//           past n_windows is an erasure (0) and is not read.
+//  forward  lane s holds M[s]. Its predecessors are p0 = s >> 1 and p1 = p0 |
+//           32, read by two ds_bpermute. The branch from p0 has register s, the
+//           one from p1 register s | 64; both generators have bit 6 set, so the
+//           second branch metric is minus the first, and the first's two signs
+//           are lane constants. __ballot of the decision is the step's survivor
+//           word. A pass of up to 32 steps keeps step i's word in lane i and
+//           stores the words with one coalesced store to the wave's slot of
+//           d_work ([waves of the launch][St] words).
+//  header   at t0 = 8 h + DEMOD_FEC_DEPTH: the best state (the wave's maximum,
+//           then the lowest lane that holds it), traced back to step 0.
+//  trace    serial in the state: 64 words per load (lane i holds step 64 c +
+//           i's), then one lane read and a shift per step on wave-uniform
+//           values. The 64 input bits of a chunk are 8 row bytes, stored by
+//           lanes 0 .. 7 where they are below the bytes to write.
+//
+// The forward pass stops at t0 for the header and at T(len) for the row: the
+// outputs do not depend on later steps. A wave's loads of its slot follow its
+// own stores in program order behind a workgroup fence.
+#include "acquire_scan.h"
+
+namespace fskd {
+
+constexpr int kFecLanes = 64;
+constexpr int kFecWaves = kAcqThreads / kFecLanes;
+constexpr unsigned kFecPass = kFecLanes / 2;   // steps of one pass: 64 soft values
+
+// soft value m of a row whose symbol 0 of the word sits at window bw
+static __device__ __forceinline__ int fec_soft(const FramesFecParams &p, bool live,
+                                               unsigned long long bw, unsigned m)
+{
+    if (!live || m >= 2u * p.steps) return 0;
+    const unsigned bits = (unsigned)p.bits, j = m / bits, b = m - j * bits;   // j < N
+    const unsigned long long w = bw + ((unsigned long long)p.sync_len + j) * (unsigned)p.phases;
+    if (w >= p.n_windows) return 0;
+    const float *P = p.mag + (size_t)w * (unsigned)p.k;
+    const unsigned mask = 1u << (bits - 1u - b);
+    float a0 = P[0], a1 = P[mask];
+    for (unsigned i = 1; i < (unsigned)p.k; ++i) {
+        const float f = P[i];
+        if (i & mask) {
+            if (f > a1) a1 = f;
+        } else if (f > a0) {
+            a0 = f;
+        }
+    }
+    const double d = (double)a0 - (double)a1, s = fabs((double)a0) + fabs((double)a1);
+    return (s > 0.0 && s <= 1.7976931348623157e308) ? (int)rint(127.0 * d / s) : 0;
+}
+
+struct FecLane {
+    int sgn0, sgn1;   // the branch from p0: -1 where the expected bit is 1
+    int at0, at1;     // ds_bpermute addresses of p0 and p1
+};
+
+// steps t .. t + count - 1, count <= kFecPass and t + count <= St
+static __device__ __forceinline__ void fec_steps(const FramesFecParams &p, const FecLane &c, bool live,
+                                                 unsigned long long bw, unsigned t, unsigned count,
+                                                 int &M, unsigned long long *slot, int lane)
+{
+    const int q = fec_soft(p, live && (unsigned)lane < 2u * count, bw, 2u * t + (unsigned)lane);
+    unsigned long long mine = 0;
+#pragma unroll 4
+    for (unsigned i = 0; i < count; ++i) {
+        const int q0 = __builtin_amdgcn_readlane(q, (int)(2u * i));
+        const int q1 = __builtin_amdgcn_readlane(q, (int)(2u * i + 1u));
+        const int bm = c.sgn0 * q0 + c.sgn1 * q1;
+        const int a = __builtin_amdgcn_ds_bpermute(c.at0, M) + bm;
+        const int b = __builtin_amdgcn_ds_bpermute(c.at1, M) - bm;
+        const bool d = b > a;
+        M = d ? b : a;
+        const unsigned long long word = __ballot(d);
+        if ((unsigned)lane == i) mine = word;
+    }
+    if ((unsigned)lane < count) slot[t + (unsigned)lane] = mine;
+}
+
+// u_t of steps t_end - 1 .. 0 from state s at step t_end (t_end >= 1). Row bytes
+// below n_write are stored where row is given. Returns u_0 .. u_63, u_0 highest.
+static __device__ __forceinline__ unsigned long long fec_trace(const unsigned long long *slot,
+                                                               unsigned t_end, unsigned s, uint8_t *row,
+                                                               unsigned n_write, int lane)
+{
+    s = (unsigned)__builtin_amdgcn_readfirstlane((int)s);
+    unsigned long long acc = 0;
+    for (int ch = (int)((t_end - 1u) / 64u); ch >= 0; --ch) {
+        const unsigned tb = (unsigned)ch * 64u;
+        const unsigned cnt = t_end - tb < 64u ? t_end - tb : 64u;
+        const unsigned long long w = (unsigned)lane < cnt ? slot[tb + (unsigned)lane] : 0ull;
+        const int lo = (int)(unsigned)w, hi = (int)(unsigned)(w >> 32);
+        acc = 0;
+        for (int i = (int)cnt - 1; i >= 0; --i) {
+            acc |= (unsigned long long)(s & 1u) << (63 - i);
+            const unsigned half = (unsigned)__builtin_amdgcn_readlane(s & 32u ? hi : lo, i);
+            s = (s >> 1) | (((half >> (s & 31u)) & 1u) << 5);
+        }
+        const unsigned at = tb / 8u + (unsigned)lane;
+        if (row && lane < 8 && at < n_write) row[at] = (uint8_t)(acc >> (56 - 8 * lane));
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecParams p, unsigned wpg)
+{
+    const int wave = threadIdx.x / kFecLanes, lane = threadIdx.x % kFecLanes;
+    const unsigned long long gw = (unsigned long long)blockIdx.x * kFecWaves + wave;
+    const unsigned long long g64 = gw / wpg;
+    if (g64 >= p.n_groups) return;
+    const unsigned g = (unsigned)g64, c0 = (unsigned)(gw % wpg);
+    unsigned nw;
+    {
+        const unsigned long long n = p.res[g].n_written;
+        nw = n < p.max_frames ? (unsigned)n : p.max_frames;
+    }
+    unsigned long long base = 0;
+    if (p.first) base = p.first[g] < p.n_windows ? p.first[g] : p.n_windows;
+    unsigned long long *slot = p.work + (size_t)gw * p.steps;   // gw < n_groups wpg
+    FecLane c;
+    c.sgn0 = (__popc((unsigned)lane & 0171u) & 1) ? -1 : 1;
+    c.sgn1 = (__popc((unsigned)lane & 0133u) & 1) ? -1 : 1;
+    c.at0 = (lane >> 1) * 4;
+    c.at1 = ((lane >> 1) | 32) * 4;
+    const unsigned h = (unsigned)p.len_bytes, t0 = 8u * h + DEMOD_FEC_DEPTH;   // t0 <= St
+    for (unsigned i = c0; i < nw; i += wpg) {   // the same for every lane of the wave
+        const size_t r = (size_t)g * p.max_frames + i;
+        const unsigned long long window = p.hits[r].window;
+        const bool live = window < p.n_windows;   // else every value an erasure; no wrap below
+        const unsigned long long bw = live ? base + window : 0;
+        int M = lane == 0 ? 0 : -(1 << 28);
+        for (unsigned t = 0; t < t0; t += kFecPass)
+            fec_steps(p, c, live, bw, t, t0 - t < kFecPass ? t0 - t : kFecPass, M, slot, lane);
+        __threadfence_block();
+        int mx = M;
+        for (int d = kFecLanes / 2; d > 0; d >>= 1) {
+            const int y = __shfl_xor(mx, d);
+            if (y > mx) mx = y;
+        }
+        const unsigned best = (unsigned)__ffsll((long long)__ballot(M == mx)) - 1u;
+        const unsigned long long head = fec_trace(slot, t0, best, nullptr, 0, lane);
+        const unsigned len = (unsigned)(head >> (64u - 8u * h));
+        uint8_t *row = p.rows + r * p.row_bytes;
+        demod_frame_decode_t out;
+        out.length = len;
+        if (len > p.max_len) {
+            if ((unsigned)lane < h) row[lane] = (uint8_t)(len >> (8u * (h - 1u - (unsigned)lane)));
+            out.metric = 0;
+            out.status = DEMOD_DECODE_BAD_LENGTH;
+            out.steps = 0;
+        } else {
+            const unsigned n = h + len + (unsigned)p.crc_bytes;             // <= row_bytes
+            const unsigned T = 8u * n + 6u > t0 ? 8u * n + 6u : t0;         // <= St
+            for (unsigned t = t0; t < T; t += kFecPass)
+                fec_steps(p, c, live, bw, t, T - t < kFecPass ? T - t : kFecPass, M, slot, lane);
+            __threadfence_block();
+            fec_trace(slot, T, 0u, row, n, lane);
+            out.metric = __builtin_amdgcn_readfirstlane(M);   // lane 0: state 0
+            out.status = DEMOD_DECODE_OK;
+            out.steps = T;
+        }
+        if (lane == 0) p.decode[r] = out;
+    }
+}
+
+hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s)
+{
+    const unsigned wpg = fec_waves_per_group(p.n_groups, p.max_frames);
+    const unsigned long long blocks = ((unsigned long long)p.n_groups * wpg + kFecWaves - 1) / kFecWaves;
+    hipLaunchKernelGGL(frames_decode_kernel, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
+    return hipGetLastError();
+}
+
+}  // namespace fskd

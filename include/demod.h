@@ -828,6 +828,166 @@ int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, cons
                          size_t max_frames, demod_frames_result_t *result,
                          demod_frames_check_result_t *summary);
 
+/* ---- coded frames: soft-decision Viterbi decode of a frame scan's rows --- */
+/*
+ * The check above drops a frame for one wrongly decided payload symbol. Here
+ * the frame is convolutionally coded and a stage between the scan and the
+ * check decodes each row from the per-tone powers P[W][K] the detector left
+ * beside the symbols; the hard symbols are not read:
+ *
+ *   demod_frames[_segments]_async   (hits and results; d_packed, d_payload NULL)
+ *     -> demod_frames_decode_async       soft values from d_mags, Viterbi, rows
+ *     -> demod_frames_check_coded_async  the check's launches over those rows
+ *
+ * All arithmetic is integer apart from one double expression per soft value;
+ * every output byte is a function of the inputs alone, the same on the device
+ * and in demod_coded_frame_decode. K must be a power of two (K = 2^bits; a
+ * coded bit would otherwise ask for a tone that does not exist): every entry
+ * that takes K refuses another with DEMOD_BAD_ARG.
+ *
+ * The code (DEMOD_FEC_CONV_K7, the only one): constraint length 7, rate 1/2,
+ * generators 0171 and 0133 (octal). reg_-1 = 0, reg_t = ((reg_t-1 << 1) | u_t)
+ * & 0x7F, v_2t = parity(reg_t & 0171), v_2t+1 = parity(reg_t & 0133); the state
+ * after step t is reg_t & 63. The information bits u_t are the checked frame
+ * len || data || CRC (n = h + len + c bytes, MSB first) and 0 for t >= 8 n,
+ * for T(len) = max(8 n + 6, 8 h + DEMOD_FEC_DEPTH) steps: six tail bits, and
+ * for short frames zero fill, so that the decoder's header look-ahead stays
+ * inside the frame. A coded frame is 2 T bits, MSB first in ceil(2 T / 8)
+ * bytes, pad bits 0; on the air it occupies L + Sc symbols, Sc = ceil(2 T /
+ * bits).
+ *
+ * Soft values: symbol j of a row sits at window w_j = base_g + window_i + (L +
+ * j) R, base_g = 0 without a segment table and min(d_first[g], n_windows) with
+ * one. Soft value m = j bits + b (bit b of the symbol, MSB first): a0 = the
+ * maximum of P[w_j][k] over the tones k < K whose bit b is 0, a1 over those
+ * whose bit b is 1, each maximum started from the lowest such k and replaced in
+ * ascending k by a strictly greater value alone; in double d = a0 - a1, s =
+ * |a0| + |a1|; q_m = (int) rint(127 d / s) (to nearest even) when s > 0 and s
+ * is finite, else 0. |q| <= 127. window_i >= n_windows or w_j >= n_windows (no
+ * wrap-around) gives q_m = 0, an erasure: no content of d_hits, d_first or
+ * d_results moves a read outside d_mags. The value is normalised per symbol:
+ * a faded symbol weighs as much as a loud one.
+ *
+ * The decoder, per row of C = N bits soft values: St = floor(C / 2) steps (an
+ * odd C leaves its last value unused), Bd = (St - 6) / 8 decoded bytes,
+ * max_len = Bd - h - c. Refused: St < 8 h + DEMOD_FEC_DEPTH, Bd < h + c,
+ * max_len > DEMOD_MAX_FRAME_PAYLOAD.
+ *
+ *   forward  int32 metrics, M[0] = 0 and M[s != 0] = -2^28. At step t state s
+ *            has u = s & 1 and predecessors p0 = s >> 1, p1 = p0 | 32; the
+ *            branch from p has register (p << 1) | u, expected bits c0, c1 as
+ *            the encoder gives them and metric bm = (c0 ? -q_2t : q_2t) + (c1 ?
+ *            -q_2t+1 : q_2t+1); M'[s] = max(M[p0] + bm0, M[p1] + bm1) and the
+ *            decision d_t[s] = 1 only when the p1 sum is strictly greater.
+ *   header   at t0 = 8 h + DEMOD_FEC_DEPTH the state of the greatest metric
+ *            (ties: the lowest state) is traced back to step 0 (u_t = s & 1, s
+ *            <- (s >> 1) | (d_t[s] << 5)); the first 8 h bits are len.
+ *   len > max_len   status DEMOD_DECODE_BAD_LENGTH, length = len, metric = 0,
+ *            steps = 0; the h header bytes of the row alone are written (the
+ *            check then reports DEMOD_CHECK_BAD_LENGTH).
+ *   else     traced back from state 0 at step T(len); bytes 0 .. n-1 of the row
+ *            are written; status DEMOD_DECODE_OK, length = len, metric =
+ *            M_T[0], steps = T.
+ *
+ * Row bytes at or past what is written, and rows i >= nw_g, are left alone.
+ */
+#define DEMOD_FEC_CONV_K7       1
+#define DEMOD_FEC_DEPTH         64
+
+#define DEMOD_DECODE_OK         0
+#define DEMOD_DECODE_BAD_LENGTH 1   /* len > max_len; metric and steps 0 */
+
+typedef struct demod_frame_decode {
+    uint32_t length;
+    int32_t metric;
+    uint32_t status, steps;
+} demod_frame_decode_t;
+
+/* T(len), or what demod_checked_frame_size refuses. No device needed. */
+long long demod_coded_frame_steps(size_t len, int len_bytes, int crc);
+
+/* Sc = ceil(2 T(len) / bits); DEMOD_BAD_ARG also for bits outside 1 .. 4. */
+long long demod_coded_frame_symbols(size_t len, int len_bytes, int crc, int bits);
+
+/* The transmit side: the coded bits of len || data || CRC into out[0 .. cap),
+ * ceil(2 T / 8) bytes that demod_unpack_symbols turns into Sc symbols. Returns
+ * the bytes written, what demod_checked_frame_encode refuses, or
+ * DEMOD_BUFFER_TOO_SMALL. */
+int demod_coded_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, uint8_t *out,
+                             size_t cap);
+
+/* Bd of rows of frame_symbols symbols; DEMOD_BAD_ARG for bits outside 1 .. 4,
+ * a bad len_bytes, frame_symbols >= 2^31 or St < 8 h + DEMOD_FEC_DEPTH. */
+long long demod_coded_row_bytes(size_t frame_symbols, int bits, int len_bytes);
+
+/* The soft values of one window: soft[b], b < bits, from powers[0 .. k).
+ * Returns bits, or DEMOD_BAD_ARG for a NULL pointer or k not 2, 4, 8 or 16. */
+int demod_soft_bits(const float *powers, uint32_t k, int8_t *soft);
+
+/* The decoder above on a host array of n_soft = C soft values: the reference of
+ * demod_frames_decode_async. row[0 .. cap) must hold Bd bytes
+ * (DEMOD_BUFFER_TOO_SMALL otherwise). Returns the row bytes written (h or n),
+ * DEMOD_BAD_ARG for a NULL pointer, a bad len_bytes or crc or a refused row
+ * shape, or DEMOD_ALLOC_FAIL. */
+int demod_coded_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, uint8_t *row,
+                             size_t cap, demod_frame_decode_t *decode);
+
+/* Bytes of d_work: the launch's waves (min(max_frames, max(16384 / n_groups,
+ * 1)) per group, as the check caps them) x St x 8, the survivor words of each
+ * wave's current row. 0 when the configuration is invalid, K is not a power of
+ * two, n_groups is 0 or above DEMOD_MAX_SEGMENTS, max_frames is 0, n_groups *
+ * max_frames >= 2^31, or frame_symbols is 0 or >= 2^31. No device needed. */
+size_t demod_frames_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
+                                          size_t frame_symbols);
+
+/*
+ * Enqueued on `stream`: one launch whatever the counts are. Nothing is
+ * allocated or synchronised, no atomics, and the handle keeps no state of the
+ * call; d_work may hold anything on entry (every word read is written first by
+ * the same call), so the call can be captured behind either scan and replayed
+ * after the powers and the tables were rewritten in place. Groups and rows as
+ * "checked frames": group g owns rows g max_frames + i, i < nw_g. d_hits and
+ * d_results are the scan's; d_mags [n_windows][K] the detector's; d_first NULL
+ * (every base 0) or the segmented scan's table [n_groups]; d_rows is
+ * [n_groups][max_frames][Bd], d_decode [n_groups][max_frames]. Returns DEMOD_OK
+ * once enqueued; DEMOD_BAD_ARG, before any launch, for what
+ * demod_frames_check_async refuses about its own arguments and: K not a power
+ * of two, the refused row shapes above, fec not DEMOD_FEC_CONV_K7, a NULL
+ * d_mags, d_rows, d_decode or d_work, a misaligned d_decode (4 bytes), d_work
+ * or d_first (8 bytes), work_bytes below demod_frames_decode_workspace_size,
+ * n_windows >= 2^31, (sync_len + frame_symbols) R >= 2^31.
+ */
+int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, const float *d_mags,
+                              size_t n_windows, const uint64_t *d_first,
+                              const demod_frames_result_t *d_results, size_t n_groups,
+                              size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                              int crc, int fec, uint8_t *d_rows, demod_frame_decode_t *d_decode,
+                              void *d_work, size_t work_bytes, void *stream);
+
+/*
+ * demod_frames_check_async over decoded rows: the same launches and outputs
+ * with the row width Bd (max_len = Bd - h - c) and, for `covered`, the coded
+ * span S = ceil(2 T(len) / bits). Refuses what demod_frames_check_async and
+ * demod_frames_decode_async refuse about the same arguments.
+ */
+int demod_frames_check_coded_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_rows,
+                                   const demod_frames_result_t *d_results, size_t n_groups,
+                                   size_t max_frames, size_t sync_len, size_t frame_symbols,
+                                   int len_bytes, int crc, int fec, demod_frame_check_t *d_check,
+                                   uint32_t *d_kept, uint8_t *d_body,
+                                   demod_frames_check_result_t *d_summary, void *stream);
+
+/*
+ * demod_frames_checked for coded frames: detector, frame scan (no packed rows),
+ * decode, coded check and the kept rows, on handle-owned buffers. Arguments,
+ * outputs and return value as demod_frames_checked, with max_len = Bd - h - c.
+ */
+int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
+                       size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
+                       int crc, int fec, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
+                       size_t max_frames, demod_frames_result_t *result,
+                       demod_frames_check_result_t *summary);
+
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
  * n_streams independent streams that share one configuration, each behaving
