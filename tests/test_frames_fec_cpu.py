@@ -60,6 +60,23 @@ def test_workspace_size(A):
             A.frames_decode_workspace_size(*args)
 
 
+def test_workspace_size_across_the_wave_cap(A):
+    """include/demod.h's description as a closed form, n_groups min(max_frames,
+    max(16384 / n_groups, 1)) St 8, on both sides of the cap of 16384 waves:
+    where 16384 / n_groups is below max_frames, exactly 1, and 0; at 1 and 4
+    bits a symbol."""
+    pairs = [(4096, 5), (5461, 4), (8193, 3), (16384, 2), (16385, 3), (65536, 2),
+             (1, 1), (1, 16384), (1, 16385), (16383, 2), (65536, 1)]
+    for K, N in ((2, 145), (16, 36), (16, 39)):
+        bits = K.bit_length() - 1
+        cfg = A.make_cfg(n=1024, hop=256, freqs=tuple(1500.0 + 375.0 * i for i in range(K)))
+        St = N * bits // 2
+        for S, max_frames in pairs:
+            want = S * min(max_frames, max(16384 // S, 1)) * St * 8
+            assert A.frames_decode_workspace_size(cfg, S, max_frames, N) == want, (K, N, S, max_frames)
+    assert A.frames_decode_workspace_size(cfg, 65536, 2, 36) == 65536 * 72 * 8
+
+
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("h", [1, 2])
 def test_encoder(A, h, kind):

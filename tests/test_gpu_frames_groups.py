@@ -1,0 +1,596 @@
+"""The frame check (frames_check.hip) and the soft-decision decode
+(frames_fec.hip) at every group count a segmented scan can hand them, up to
+DEMOD_MAX_SEGMENTS, against tests/frames_check_ref.py, tests/frames_fec_ref.py
+and tests/frames_segments_ref.py.
+
+Both stages size their launch from a cap of 16384 waves a call: with most =
+16384 / S (at least 1) a group gets wpg = min(max_frames, most) waves (the
+body kernel min(ceil(max_frames max_len / 64), most)). The cases here reach
+what the neighbouring files do not: most below max_frames, most = 1 and the
+16384 / S == 0 fallback, a last block with waves that leave beside live ones,
+the body kernel's stride loop running more than once, workspace slots above
+16383, and the chain segmented scan -> decode -> coded check behind 20000
+segments, nearly all of them empty.
+
+A group's outputs depend on its own content alone (test_groups and
+test_segments of the neighbouring files assert that), so the host reference is
+computed once for a pool of at most 64 distinct groups (hits, rows or powers,
+stored count) and laid out by the same seeded indices that fill the S groups.
+As everywhere: every output is poisoned and compared WHOLE with the reference
+laid over the same poison, and the inputs are compared byte for byte after the
+call.
+
+Out of scope: frames_kept_rows_kernel's grid is capped at 1024 blocks, which
+matters only above 262144 kept frames in one synchronous call (its loop then
+strides); no group count reaches it.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import frames_check_ref as C
+import frames_fec_ref as X
+import frames_ref as F
+import frames_segments_ref as FS
+import guards as G
+import test_gpu_frames_check as TC
+import test_gpu_frames_fec as TF
+import test_gpu_frames_segments as TS
+from test_gpu_frames import result_bytes
+
+pytestmark = pytest.mark.gpu
+
+MAX_WAVES = 16384            # kChkMaxWaves, kFecMaxWaves
+WAVES_PER_BLOCK = 4
+LANES = 64
+LEAD = 4096
+# (S, max_frames, most, waves of the check's and the decode's launch)
+GEOMETRY = [(4096, 5, 4, 16384), (5461, 4, 3, 16383), (8193, 3, 1, 8193), (16384, 2, 1, 16384),
+            (16385, 3, 1, 16385), (65536, 2, 1, 65536)]
+POOL = 48                    # distinct groups of a case
+LIVE = {5461: 3, 8193: 1, 16385: 1}   # live waves of a partial last block (wpg = most in every launch here)
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    if not t.cuda.is_available():
+        pytest.skip("no GPU visible")
+    return t
+
+
+_HANDLES = {}
+
+
+@pytest.fixture(scope="module")
+def handle(A, torch):
+    """handle(R, K): one Demodulator per (R, K), closed with the module."""
+    def get(Rn, K):
+        if (Rn, K) not in _HANDLES:
+            n, hop = TC.SHAPE_OF_R[Rn]
+            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
+            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
+            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
+        return _HANDLES[Rn, K]
+    yield get
+    for d in _HANDLES.values():
+        d.close()
+    _HANDLES.clear()
+
+
+# ---- the launch arithmetic, restated from the kernels' comments ---------------------
+
+def waves_per_group(S, max_frames):
+    most = MAX_WAVES // S if MAX_WAVES // S else 1
+    return min(max_frames, most)
+
+
+def body_waves_per_group(S, max_frames, max_len):
+    most = MAX_WAVES // S if MAX_WAVES // S else 1
+    return min(-(-max_frames * max_len // LANES), most)
+
+
+def last_block(S, wpg):
+    """(live waves of the launch's last block, the groups they belong to)."""
+    waves = S * wpg
+    live = waves % WAVES_PER_BLOCK or WAVES_PER_BLOCK
+    return live, sorted({w // wpg for w in range(waves - live, waves)})
+
+
+def stored_counts(rng, max_frames):
+    """POOL stored n_written: entry 0 max_frames, 1 zero, 2 above max_frames,
+    3 2^64 - 1, the rest drawn from [0, max_frames]."""
+    counts = [int(v) for v in rng.integers(0, max_frames + 1, POOL)]
+    counts[:4] = [max_frames, 0, max_frames + 7, 2 ** 64 - 1]
+    return counts
+
+
+def draw_slots(rng, S):
+    """The pool entry of each of the S groups: entry 0 (max_frames rows) in
+    groups 0 and S - 1, entry 1 (no rows) in group 1."""
+    idx = rng.integers(0, POOL, S)
+    idx[0], idx[1], idx[S - 1] = 0, 1, 0
+    assert {2, 3} <= set(idx.tolist())             # a stored count above max_frames, and 2^64 - 1
+    return idx
+
+
+def tally(S, max_frames, idx, counts, statuses):
+    """Groups, rows, empty groups and rows per status of a case (statuses: per
+    pool entry, the statuses of its rows)."""
+    nw = np.array([min(c, max_frames) for c in counts])[idx]
+    per = {}
+    use = np.bincount(idx, minlength=POOL)
+    for p, st in enumerate(statuses):
+        for s in st:
+            per[int(s)] = per.get(int(s), 0) + int(use[p])
+    return dict(groups=S, rows=int(nw.sum()), empty=int((nw == 0).sum()), status=dict(sorted(per.items())))
+
+
+def assert_last_block_holds_rows(S, wpg, idx, counts, max_frames, want_live):
+    live, groups = last_block(S, wpg)
+    assert live == want_live, (S, wpg, live)
+    if live < WAVES_PER_BLOCK:                     # a wave leaves beside these: they must have work
+        for g in groups:
+            assert min(counts[idx[g]], max_frames) > 0, (S, g)
+
+
+# ---- Part 1: the check ----------------------------------------------------------------
+
+BIG = dict(Rn=1, K=16, L=24, B=65, h=2, kind=C.CRC32)           # max_len 59: the body kernel strides
+SMALL = dict(Rn=4, K=2, L=TC.SELECT_L, B=TC.SELECT_B, h=TC.SELECT_H, kind=TC.SELECT_KIND)
+
+
+def big_group(rng, n_rows, full, Rn, L, B, h, kind, bits):
+    """n_rows rows with ascending windows and drawn roles: kept (at or past
+    everything before it), covered (inside a valid frame before it), invalid (a
+    flipped bit in data or CRC), random (a drawn header, random bytes) and long
+    (a header of max_len + 1). full: every row a kept frame of max_len bytes."""
+    c = C.CRC_BYTES[kind]
+    max_len = B - h - c
+    windows = np.zeros(n_rows, np.uint64)
+    rows = np.zeros((n_rows, B), np.uint8)
+    w, reach = int(rng.integers(0, 3)) * Rn, 0
+    for i in range(n_rows):
+        role = "kept" if full else ("kept", "covered", "invalid", "random", "long")[int(rng.integers(0, 5))]
+        length = max_len if full or rng.integers(0, 3) == 0 else int(rng.integers(0, max_len + 1))
+        w += Rn
+        if role == "kept":
+            w = max(w, reach) + Rn * int(rng.integers(0, 3))
+        if role in ("kept", "covered"):
+            rows[i] = TC.frame_row(rng, length, B, h, kind)
+        elif role == "invalid":
+            rows[i] = TC.flip(TC.frame_row(rng, length, B, h, kind), h, h + length + c, rng)
+        else:
+            rows[i] = rng.integers(0, 256, B)
+            head = max_len + 1 if role == "long" else int(rng.integers(0, max_len + 3))
+            rows[i, :h] = np.frombuffer(head.to_bytes(h, "big"), np.uint8)
+        windows[i] = w
+        got = C.check_row(rows[i], h, kind)
+        if got[2] == C.OK:
+            reach = max(reach, w + (L + C.frame_symbols(h + got[0] + c, bits)) * Rn)
+    return windows, rows
+
+
+@functools.lru_cache(maxsize=2)
+def check_case(S, max_frames, small=False):
+    """One case: (shape, the pool's hits [POOL][max_frames], packed rows and
+    stored counts, idx: the pool entry of each of the S groups)."""
+    shape = SMALL if small else BIG
+    Rn, K, L, B, h, kind = (shape[k] for k in ("Rn", "K", "L", "B", "h", "kind"))
+    bits = F.bits_per_symbol(K)
+    rng = np.random.default_rng(S * 10 + max_frames + (1 if small else 0))
+    counts = stored_counts(rng, max_frames)
+    hits = np.zeros((POOL, max_frames), C.HIT_DTYPE)
+    packed = np.zeros((POOL, max_frames, B), np.uint8)
+    for p in range(POOL):
+        if small:
+            hits["window"][p], packed[p], _ = TC.select_group(rng, min(counts[p], max_frames), max_frames, Rn, bits)
+        else:
+            hits["window"][p], packed[p] = big_group(rng, max_frames, p == 0, Rn, L, B, h, kind, bits)
+        hits["errors"][p] = rng.integers(0, 3, max_frames)
+    idx = draw_slots(rng, S)
+    return shape, hits, packed, counts, idx
+
+
+def check_expected(case, poison=TC.POISON):
+    """The four outputs of the S groups whole, from the pool's reference."""
+    shape, hits, packed, counts, idx = case
+    bits = F.bits_per_symbol(shape["K"])
+    want, refs = TC.expected(hits, packed, counts, shape["L"], shape["Rn"], bits, shape["h"], shape["kind"], poison)
+    return {k: v[idx] for k, v in want.items()}, refs
+
+
+def late_bytes(refs, idx, max_len, step):
+    """Body bytes at e = r max_len + b >= step: written by a second or later
+    pass of the body kernel's loop alone."""
+    per = [sum(len(d) - min(max(step - r * max_len, 0), len(d)) for r, d in enumerate(ref[2])) for ref in refs]
+    return int(np.array(per)[idx].sum())
+
+
+def run_check(torch, d, case, hits, packed, counts, body=True, poison=TC.POISON, guard=False):
+    shape = case[0]
+    N = TC.symbols_for(shape["B"], F.bits_per_symbol(shape["K"]))
+    return TC.Run(torch, hits, packed, counts, body=body, poison=poison, guard=guard)(
+        d, shape["L"], N, shape["h"], shape["kind"])
+
+
+def check_fixture(case, refs, S, max_frames, most, waves):
+    """The fixture's conditions, on the reference alone. Returns the tally."""
+    shape, hits, packed, counts, idx = case
+    max_len = shape["B"] - shape["h"] - C.CRC_BYTES[shape["kind"]]
+    wpg = waves_per_group(S, max_frames)
+    assert (MAX_WAVES // S if MAX_WAVES // S else 1) == most and S * wpg == waves
+    assert_last_block_holds_rows(S, wpg, idx, counts, max_frames, LIVE.get(S, WAVES_PER_BLOCK))
+    status = np.concatenate([r[0]["status"] for r in refs])
+    covered = np.concatenate([r[0]["covered"] for r in refs])
+    assert set(status.tolist()) == {C.OK, C.BAD_LENGTH, C.BAD_CRC}
+    assert covered.sum() > 0 and sum(len(r[1]) for r in refs) > 0
+    stats = tally(S, max_frames, idx, counts, [r[0]["status"] for r in refs])
+    if shape is BIG:
+        bwpg = body_waves_per_group(S, max_frames, max_len)
+        assert max_frames * max_len > LANES * most and bwpg == most          # the loop strides
+        assert_last_block_holds_rows(S, bwpg, idx, counts, max_frames, LIVE.get(S, WAVES_PER_BLOCK))
+        chk, kept, bodies, summ = refs[0]                                    # groups 0 and S - 1
+        assert summ["n_kept"] == max_frames and len(bodies[-1]) == max_len
+        stats["late_bytes"] = late_bytes(refs, idx, max_len, bwpg * LANES)
+        assert stats["late_bytes"] > 0
+    return stats
+
+
+@pytest.mark.parametrize("S,max_frames,most,waves", GEOMETRY)
+def test_check_geometry(A, torch, handle, S, max_frames, most, waves):
+    """h 2, CRC-32, rows of 65 bytes (max_len 59) at every (S, max_frames) of
+    the table: the check, the selection and the body, whose loop strides. At
+    S = 16385 also the same content rotated by one slot: each group's bytes move
+    with it."""
+    case = check_case(S, max_frames)
+    shape, hits, packed, counts, idx = case
+    want, refs = check_expected(case)
+    stats = check_fixture(case, refs, S, max_frames, most, waves)
+    print(f"check S={S} max_frames={max_frames}: {stats}")
+    d = handle(shape["Rn"], shape["K"])
+    full = [counts[p] for p in idx]
+    got = run_check(torch, d, case, hits[idx], packed[idx], full)
+    TC.same(got, want, S)
+    if S == 16385:
+        order = np.roll(np.arange(S), -1)                     # slot g holds group g + 1's content
+        got2 = run_check(torch, d, case, hits[idx[order]], packed[idx[order]], [full[g] for g in order])
+        TC.same(got2, {k: v[order] for k, v in want.items()}, "rotated")
+        for k in got:
+            assert np.array_equal(got2[k], got[k][order]), k
+
+
+@pytest.mark.parametrize("small,body,guard", [(False, False, False), (True, True, True)])
+def test_check_fallback_shapes(A, torch, handle, small, body, guard):
+    """S = 16385 x 3 rows again: without d_body, and in the CRC-16, h 1, 8-byte
+    shape of test_select_shapes between poisoned guards with two poisons."""
+    S, max_frames, most, waves = GEOMETRY[4]
+    case = check_case(S, max_frames, small)
+    shape, hits, packed, counts, idx = case
+    d = handle(shape["Rn"], shape["K"])
+    full = [counts[p] for p in idx]
+    for poison in (0xFF, 0x5A) if guard else (0xFF,):
+        want, refs = check_expected(case, poison)
+        stats = check_fixture(case, refs, S, max_frames, most, waves)
+        got = run_check(torch, d, case, hits[idx], packed[idx], full, body=body, poison=poison, guard=guard)
+        assert ("body" in got) == body
+        TC.same(got, want, poison)
+    print(f"check S={S} max_frames={max_frames} small={small} body={body}: {stats}")
+
+
+# ---- Part 1: the decode ------------------------------------------------------------------
+
+def decode_rows_pool(rng, K, Rn, h, kind, N, count=40):
+    """`count` rows of one shape laid in one batch: frames of drawn lengths (0,
+    1 and max_len among them) with 4 flipped coded bits each, every fourth a
+    random row, one a header of max_len + 1. Returns (P, starts, frames: the
+    planted frame of each row, or None)."""
+    bits = F.bits_per_symbol(K)
+    St, Bd, max_len = X.row_shape(N, bits, h, kind)
+    rows, frames = [], []
+    for r in range(count):
+        if r % 4 == 3:
+            rows.append(rng.integers(0, K, N).astype(np.uint8))
+            frames.append(None)
+        elif r == 5:
+            info = (max_len + 1).to_bytes(h, "big") + rng.integers(0, 256, Bd).astype(np.uint8).tobytes()
+            rows.append(TF.info_symbols(info, St, N, bits, rng, 0))
+            frames.append(None)
+        else:
+            length = (0, 1, max_len)[r] if r < 3 else int(rng.integers(0, max_len + 1))
+            row, frame = TF.frame_symbols(rng, length, N, bits, h, kind)
+            rows.append(row)
+            frames.append(frame)
+    P, starts = TF.lay_rows(rows, K, Rn, rng)
+    return P, starts, frames
+
+
+@functools.lru_cache(maxsize=2)
+def decode_case(S, max_frames, K, Rn, tables):
+    """One case's inputs with its pool: h 1, CRC-16, the minimal N. tables: the
+    groups carry a first[] entry of 0, `shift` (the same rows, their windows
+    relative), n_windows - a few symbols (the row's end erased), n_windows and
+    two above it."""
+    h, kind = 1, C.CRC16
+    bits = F.bits_per_symbol(K)
+    N = TF.min_symbols(bits, h)
+    assert X.row_shape(N, bits, h, kind) == (72, 8, 5)
+    rng = np.random.default_rng(S * 10 + max_frames + K)
+    P, starts, frames = decode_rows_pool(rng, K, Rn, h, kind, N)
+    W = len(P)
+    counts = stored_counts(rng, max_frames)
+    hits = np.zeros((POOL, max_frames), C.HIT_DTYPE)
+    hits["window"] = starts[rng.integers(0, len(starts), hits.shape)]
+    hits["errors"] = rng.integers(0, 3, hits.shape)
+    first = None
+    shift = int(starts[3])
+    if tables:
+        choices = [0, shift, W - (TF.L0 + 20) * Rn, 0, W, shift, W + 9, 2 ** 64 - 1]
+        first = [choices[p % len(choices)] for p in range(POOL)]
+        for p, f in enumerate(first):
+            if f == shift:
+                hits["window"][p] = starts[rng.integers(3, len(starts), max_frames)] - np.uint64(shift)
+            elif f:
+                hits["window"][p] = rng.integers(0, 3 * Rn + 1, max_frames).astype(np.uint64)
+    idx = draw_slots(rng, S)
+    planted = {int(s): f for s, f in zip(starts, frames) if f is not None}
+    return dict(K=K, Rn=Rn, h=h, kind=kind, N=N, P=P, W=W, hits=hits, counts=counts, first=first, idx=idx,
+                planted=planted, bases=(0, shift) if tables else (0,))
+
+
+def decode_expected(case, S, max_frames, most, waves, poison=TF.POISON):
+    """rows and decode of the S groups whole, from the pool's reference; the
+    fixture's conditions on the reference alone; the tally."""
+    c = case
+    rows, dec, by_key = TF.reference(c["P"], c["W"], c["first"], c["hits"], c["counts"], TF.L0, c["Rn"], c["N"],
+                                     c["h"], c["kind"], poison)
+    idx = c["idx"]
+    wpg = waves_per_group(S, max_frames)
+    assert (MAX_WAVES // S if MAX_WAVES // S else 1) == most and S * wpg == waves
+    assert_last_block_holds_rows(S, wpg, idx, c["counts"], max_frames, LIVE.get(S, WAVES_PER_BLOCK))
+    back = 0
+    for key, (written, d) in by_key.items():
+        base, w = key if key is not None else (None, 0)
+        frame = c["planted"].get(base + w) if base in c["bases"] else None
+        if frame is not None:
+            assert written == frame and d["status"] == X.OK, (base, w)
+            back += 1
+    assert back >= 10
+    assert {int(v[1]["status"]) for v in by_key.values()} == {X.OK, X.BAD_LENGTH}
+    statuses = [dec[p, :min(c["counts"][p], max_frames)].copy().view(X.DECODE_DTYPE)["status"].reshape(-1)
+                for p in range(POOL)]
+    return (rows[idx], dec[idx]), tally(S, max_frames, idx, c["counts"], statuses)
+
+
+def run_decode(A, torch, d, case, idx, **kw):
+    c = case
+    first = None if c["first"] is None else [c["first"][p] for p in idx]
+    return TF.Run(A, torch, c["P"], c["hits"][idx], [c["counts"][p] for p in idx], first=first, **kw)(
+        d, TF.L0, c["N"], c["h"], c["kind"])
+
+
+@pytest.mark.parametrize("S,max_frames,most,waves", GEOMETRY)
+def test_decode_geometry(A, torch, handle, S, max_frames, most, waves):
+    """16 tones, R 1, h 1, CRC-16, the minimal rows (72 steps, 8 bytes) at
+    every (S, max_frames) of the table; the workspace (S wpg slots of 72 words:
+    37748736 bytes at S = 65536) under two poisons. At S = 16385 also the same
+    content rotated by one slot."""
+    K, Rn = 16, 1
+    case = decode_case(S, max_frames, K, Rn, False)
+    want, stats = decode_expected(case, S, max_frames, most, waves)
+    print(f"decode S={S} max_frames={max_frames}: {stats}")
+    d = handle(Rn, K)
+    need = A.frames_decode_workspace_size(d.cfg, S, max_frames, case["N"])
+    assert need == waves * 72 * 8 and (S != 65536 or need == 65536 * 72 * 8)
+    idx = case["idx"]
+    for work_poison in (0xFF, 0x00):
+        got = run_decode(A, torch, d, case, idx, work_poison=work_poison)
+        TF.same(got, want, (S, work_poison))
+    if S == 16385:
+        order = np.roll(np.arange(S), -1)                     # slot g holds group g + 1's content
+        got2 = run_decode(A, torch, d, case, idx[order])
+        TF.same(got2, [v[order] for v in want], "rotated")
+        for a, b in zip(got2, got):
+            assert np.array_equal(a, b[order])
+
+
+def test_decode_fallback_tables(A, torch, handle):
+    """S = 16385 x 3 rows again at 2 tones, R 4, with a first[] table (entries
+    at n_windows and above it among them), between poisoned guards with two
+    poisons."""
+    S, max_frames, most, waves = GEOMETRY[4]
+    K, Rn = 2, 4
+    case = decode_case(S, max_frames, K, Rn, True)
+    assert case["W"] in case["first"] and max(case["first"]) > case["W"]
+    d = handle(Rn, K)
+    for poison in (0xFF, 0x5A):
+        want, stats = decode_expected(case, S, max_frames, most, waves, poison)
+        got = run_decode(A, torch, d, case, case["idx"], poison=poison, guard=True)
+        TF.same(got, want, poison)
+    print(f"decode S={S} max_frames={max_frames} K={K} R={Rn} with first[]: {stats}")
+
+
+# ---- Part 3: the chain behind a sparse segmented scan -----------------------------------------
+
+CH = dict(S=20000, Rn=1, K=16, L=8, h=1, kind=C.CRC16, cap=2, planted=64, short=300)
+CH_N = X.symbols_for(6, 4, CH["h"], CH["kind"])
+CH_ST, CH_BD, CH_MAX = X.row_shape(CH_N, 4, CH["h"], CH["kind"])
+
+
+@functools.lru_cache(maxsize=1)
+def chain_content():
+    """sym[Wb], P[Wb][16], the word, first[], count[] and what was planted: 64
+    of the 20000 segments (the last among them) hold one coded frame each, from
+    a pool of 16, with three payload symbols on a wrong tone; 300 are shorter
+    than L + N windows (every third starts with the word: a tail, no frame);
+    the rest have count 0."""
+    S, K, L, h, kind, N = CH["S"], CH["K"], CH["L"], CH["h"], CH["kind"], CH_N
+    rng = np.random.default_rng(S)
+    word = np.array([3, 14, 1, 5, 9, 2, 6, 11], np.uint8)
+    picks = rng.choice(S - 1, CH["planted"] - 1 + CH["short"], replace=False)
+    planted = np.sort(np.r_[picks[:CH["planted"] - 1], S - 1])
+    short = np.sort(picks[CH["planted"] - 1:])
+    assert (planted > 16384).sum() >= 3 and planted[-1] == S - 1
+    lead = {int(s): int(rng.integers(0, 6)) for s in planted}
+    count = np.zeros(S, np.int64)
+    for s in planted:
+        count[s] = lead[int(s)] + L + N + int(rng.integers(0, 7))
+    count[short] = rng.integers(1, L + N, len(short))
+    first = np.cumsum(count + rng.integers(0, 3, S)) - count
+    Wb = int(first[-1] + count[-1]) + 3
+    sym = rng.integers(0, K, Wb).astype(np.uint8)
+    lengths = [0, 1, 6, 6] + [int(v) for v in rng.integers(0, 7, 12)]
+    frames = [TF.frame_symbols(rng, n, N, 4, h, kind, flips=0) for n in lengths]
+    datas = {}
+    for s in planted:
+        row, frame = frames[int(rng.integers(0, len(frames)))]
+        row = row.copy()
+        Sc = X.coded_symbols(len(frame) - h - 2, h, kind, 4)
+        for j in (Sc // 6, Sc // 2, (5 * Sc) // 6):
+            row[j] = (row[j] + 1 + int(rng.integers(0, K - 1))) % K
+        w = int(first[s]) + lead[int(s)]
+        sym[w:w + L] = word
+        sym[w + L:w + L + N] = row
+        datas[int(s)] = (lead[int(s)], frame[h:len(frame) - 2])
+    for s in short[::3]:
+        if count[s] >= L:
+            sym[first[s]:first[s] + L] = word
+    P = TF.powers_for(sym, K, rng)
+    return sym, P, word, first, count, planted, short, datas
+
+
+@functools.lru_cache(maxsize=1)
+def chain_reference(A):
+    """Every output of the three calls whole over 0xFF, and the fixture's
+    conditions on the reference alone."""
+    sym, P, word, first, count, planted, short, datas = chain_content()
+    S, Rn, L, h, kind, cap, N = CH["S"], CH["Rn"], CH["L"], CH["h"], CH["kind"], CH["cap"], CH_N
+    B = (N * 4 + 7) // 8
+    Wb = len(sym)
+    want = dict(hits=np.full((S, cap, TS.HIT), 0xFF, np.uint8), payload=np.full((S, cap, N), 0xFF, np.uint8),
+                packed=np.full((S, cap, B), 0xFF, np.uint8))
+    # segments without windows: the closed form of a short segment (test_max_segments checks its
+    # all-hit cousin the same way), held to the reference on a sample below
+    empty = np.zeros((), TS.RESULT_DTYPE)
+    empty["phases"], empty["tail_window"] = Rn, -1
+    res = np.tile(np.frombuffer(empty.tobytes(), np.uint8), (S, 1))
+    some = np.flatnonzero(count > 0)
+    assert len(some) == CH["planted"] + CH["short"]
+    h2 = np.zeros((S, cap), C.HIT_DTYPE)
+    n_written = np.zeros(S, np.int64)
+    tails = 0
+    for s, (r_hits, r_pay, r_pak, r_res) in zip(some, FS.frames_segments(sym, P, Rn, first[some], count[some], word,
+                                                                         0, N, max_frames=cap)):
+        nw = r_res["n_written"]
+        res[s] = np.frombuffer(result_bytes(A, r_res), np.uint8)
+        want["hits"][s, :nw] = r_hits.view(np.uint8).reshape(nw, TS.HIT)
+        want["payload"][s, :nw], want["packed"][s, :nw] = r_pay, r_pak
+        h2[s, :nw], n_written[s] = r_hits, nw
+        tails += r_res["tail_window"] >= 0
+    assert tails >= 50
+    none = np.flatnonzero(count == 0)
+    pick = none[::397]
+    for s, r in zip(pick, FS.frames_segments(sym, P, Rn, first[pick], count[pick], word, 0, N, max_frames=cap)):
+        assert result_bytes(A, r[3]) == empty.tobytes() and len(r[0]) == 0, s
+    want["results"] = res
+    rows, dec, _ = TF.reference(P, Wb, first, h2, n_written, L, Rn, N, h, kind)
+    chk, refs = TF.coded_expected(h2, rows, n_written, L, Rn, 4, h, kind)
+    want.update(rows=rows, decode=dec, **chk)
+    # the fixture's conditions: every planted frame is kept, with its exact bytes
+    for s in planted:
+        at, data = datas[int(s)]
+        kept = [int(h2[s, i]["window"]) for i in refs[s][1]]
+        assert at in kept and refs[s][2][kept.index(at)] == data, s
+    extra = sum(len(r[1]) for r in refs) - len(planted)
+    assert extra == 0            # counted on the reference: the filler of this seed holds no frame of its own
+    stats = dict(groups=S, rows=int(n_written.sum()), empty=int((n_written == 0).sum()),
+                 no_windows=len(none), kept=sum(len(r[1]) for r in refs),
+                 status={int(k): int(v) for k, v in zip(*np.unique(
+                     np.concatenate([r[0]["status"] for r in refs]), return_counts=True))})
+    return want, stats
+
+
+class Chain:
+    """The three calls' device buffers, every output and workspace between
+    poisoned guards."""
+
+    SCAN = ("hits", "payload", "packed", "results")
+    LATER = ("rows", "decode", "check", "kept", "body", "summary")
+
+    def __init__(self, A, torch, d):
+        self.A, self.torch, self.d = A, torch, d
+        sym, P, word, first, count = chain_content()[:5]
+        S, cap, N = CH["S"], CH["cap"], CH_N
+        self.word, self.Wb = word, len(sym)
+        self.inputs = [sym, np.ascontiguousarray(P).reshape(-1), np.ascontiguousarray(first, np.uint64).view(np.int64),
+                       np.ascontiguousarray(count, np.uint32).view(np.int32)]
+        self.d_in = [torch.from_numpy(a.copy()).cuda() for a in self.inputs]
+        rows = S * cap
+        sizes = dict(hits=rows * TS.HIT, payload=rows * N, packed=rows * ((N * 4 + 7) // 8),
+                     results=S * TS.RES_BYTES, rows=rows * CH_BD, decode=rows * 16, check=rows * 16,
+                     kept=rows * 4, body=rows * CH_MAX, summary=S * 32,
+                     work=A.frames_segments_workspace_size(d.cfg, S, self.Wb),
+                     fwork=A.frames_decode_workspace_size(d.cfg, S, cap, N))
+        assert sizes["fwork"] == S * CH_ST * 8
+        self.shape = dict(hits=(S, cap, TS.HIT), payload=(S, cap, N), packed=(S, cap, (N * 4 + 7) // 8),
+                          results=(S, TS.RES_BYTES), rows=(S, cap, CH_BD), decode=(S, cap, 16), check=(S, cap, 16),
+                          kept=(S, cap, 4), body=(S, cap, CH_MAX), summary=(S, 32))
+        self.t, self.guards = {}, []
+        for k, nbytes in sizes.items():
+            self.t[k], chk = G.guarded(torch, nbytes, torch.uint8, LEAD, LEAD, 0xFF)
+            self.guards.append(chk)
+
+    def poison(self, names):
+        for k in names:
+            self.t[k].fill_(0xFF)
+
+    def scan(self, stream=0):
+        t, i = self.t, self.d_in
+        self.d.frames_segments_async(i[0], i[1], self.Wb, i[2], i[3], CH["S"], self.word, 0, CH_N, t["hits"],
+                                     t["payload"], t["packed"], CH["cap"], t["results"], t["work"], stream=stream)
+
+    def later(self, stream=0):
+        t, i, c = self.t, self.d_in, CH
+        self.d.frames_decode_async(t["hits"], i[1], self.Wb, i[2], t["results"], c["S"], c["cap"], c["L"], CH_N,
+                                   c["h"], c["kind"], t["rows"], t["decode"], t["fwork"], stream=stream)
+        self.d.frames_check_coded_async(t["hits"], t["rows"], t["results"], c["S"], c["cap"], c["L"], CH_N, c["h"],
+                                        c["kind"], t["check"], t["kept"].view(self.torch.int32), t["body"],
+                                        t["summary"], stream=stream)
+
+    def results(self, names):
+        self.torch.cuda.synchronize()
+        for chk in self.guards:
+            chk(written=False)
+        for t, a in zip(self.d_in, self.inputs):
+            assert t.cpu().numpy().tobytes() == a.tobytes(), "an input was written to"
+        return {k: self.t[k].cpu().numpy().reshape(self.shape[k]) for k in names}
+
+
+def test_chain_behind_sparse_scan(A, torch, handle):
+    """demod_frames_segments_async -> demod_frames_decode_async (the scan's
+    d_first) -> demod_frames_check_coded_async with a body on 20000 segments,
+    19636 of them without a window: every output of the three calls is the
+    reference's, whole; all 64 planted frames are kept although three payload
+    symbols of each sit on a wrong tone. Then the last two calls captured on a
+    side stream and replayed once over poisoned outputs."""
+    want, stats = chain_reference(A)
+    print(f"chain: {stats}")
+    ch = Chain(A, torch, handle(CH["Rn"], CH["K"]))
+    ch.scan()
+    ch.later()
+    TF.same_dict(ch.results(Chain.SCAN + Chain.LATER), want, "eager")
+    side = torch.cuda.Stream()
+    ch.poison(Chain.LATER + ("fwork",))
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        ch.later(stream=side.cuda_stream)                 # an eager call of the shape on the stream first
+        side.synchronize()
+    TF.same_dict(ch.results(Chain.LATER), want, "side stream")
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        ch.later(stream=torch.cuda.current_stream().cuda_stream)
+    ch.poison(Chain.LATER + ("fwork",))
+    torch.cuda.synchronize()
+    g.replay()
+    TF.same_dict(ch.results(Chain.SCAN + Chain.LATER), want, "replay")
