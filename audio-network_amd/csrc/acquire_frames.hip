@@ -43,19 +43,13 @@ static __device__ __forceinline__ AcqScanArgs scan_args(const FramesParams &p)
     return {p.sym, p.mag, p.n_windows, p.per_phase, p.phases, p.k, p.sync_len, p.max_errors, p.part};
 }
 
-// a hit at w is complete when w + frame_span < W: its word and payload fit
-static __device__ __forceinline__ long long frame_span(const FramesParams &p)
-{
-    return ((long long)p.sync_len + p.frame_symbols - 1) * p.phases;
-}
-
 __global__ __launch_bounds__(kAcqThreads) void frames_scan_kernel(FramesParams p)
 {
     __shared__ AcqScanLds s;
     __shared__ unsigned long long s_tail[DEMOD_MAX_PHASES];
     __shared__ unsigned s_cnt[DEMOD_MAX_PHASES];
     const int t = threadIdx.x, R = p.phases;
-    const long long W = p.n_windows, span = frame_span(p);
+    const long long W = p.n_windows, span = frame_span(p.sync_len, p.frame_symbols, p.phases);
     if (t < DEMOD_MAX_PHASES) {
         s_tail[t] = kAcqNone;
         s_cnt[t] = 0;
@@ -140,7 +134,7 @@ __global__ __launch_bounds__(kAcqThreads) void frames_emit_kernel(FramesParams p
     const int t = threadIdx.x, wave = t / 64, lane = t % 64;
     const int R = p.phases, L = p.sync_len, phase = (int)p.res->phase;
     const int halo = (L - 1) * R, starts = kAcqTile / R;   // starts on the phase per tile
-    const long long W = p.n_windows, span = frame_span(p);
+    const long long W = p.n_windows, span = frame_span(p.sync_len, p.frame_symbols, p.phases);
     if (t < DEMOD_MAX_SYNC) s_sync[t] = p.sync[t];
     const long long tiles = (W + kAcqTile - 1) / kAcqTile;
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -207,28 +201,11 @@ __global__ __launch_bounds__(kAcqThreads) void frames_gather_kernel(FramesParams
         }
     }
     if (p.packed) {
-        // MSB first, each symbol masked to `bits` bits, pad bits 0 (demod_pack_symbols)
         const unsigned bits = (unsigned)p.bits, mask = (1u << bits) - 1u;
         const unsigned long long B = (N * bits + 7) / 8;
         for (unsigned long long e = first; e < nw * B; e += step) {
             const unsigned long long i = e / B, b = e - i * B;
-            const uint8_t *src = p.sym + p.hits[i].window + L * R;
-            unsigned long long j = b * 8 / bits;
-            unsigned used = (unsigned)(b * 8 - j * bits);   // bits of symbol j in the bytes before
-            unsigned byte = 0;
-            for (unsigned q = 0; q < 8 && j < N;) {
-                const unsigned v = src[j * R] & mask;
-                const unsigned left = bits - used, room = 8 - q;
-                const unsigned take = left < room ? left : room;
-                byte |= ((v >> (left - take)) & ((1u << take) - 1u)) << (room - take);
-                q += take;
-                used += take;
-                if (used == bits) {
-                    used = 0;
-                    ++j;
-                }
-            }
-            p.packed[e] = (uint8_t)byte;
+            p.packed[e] = frame_packed_byte(p.sym + p.hits[i].window + L * R, R, N, bits, mask, b);
         }
     }
 }

@@ -35,7 +35,7 @@
 //  gather    a bounded number of waves per segment, each looping over its
 //            segment's n_written N symbols / n_written B packed bytes (read
 //            from device memory), so a batch without hits costs one load per
-//            segment. Byte assembly as frames_gather_kernel.
+//            segment. Byte assembly as frames_gather_kernel (frame_packed_byte).
 //
 // Every output byte of a segment depends on its contents and (count', R) alone.
 // No floating-point atomics, no atomics on d_work, none that decide a position;
@@ -45,12 +45,6 @@
 
 namespace fskd {
 
-// a hit at w is complete when w + frame_span < count': its word and payload fit
-static __device__ __forceinline__ long long frame_span(const FrameSegParams &q)
-{
-    return ((long long)q.seg.sync_len + q.frame_symbols - 1) * q.seg.phases;
-}
-
 __global__ __launch_bounds__(kSegThreads) void frames_seg_scan_kernel(FrameSegParams q)
 {
     __shared__ uint8_t s_sym[kSegWaves][kAcqTile + kSegHalo];
@@ -58,7 +52,7 @@ __global__ __launch_bounds__(kSegThreads) void frames_seg_scan_kernel(FrameSegPa
     const AcquireSegParams &p = q.seg;
     const int t = threadIdx.x, wave = t / kSegLanes, lane = t % kSegLanes;
     const int R = p.phases;
-    const long long span = frame_span(q);
+    const long long span = frame_span(q.seg.sync_len, q.frame_symbols, q.seg.phases);
     if (t < DEMOD_MAX_SYNC) s_sync[t] = p.sync[t];
     const unsigned total = *p.w_total;
     for (unsigned g0 = blockIdx.x * kSegWaves; g0 < total; g0 += gridDim.x * kSegWaves) {
@@ -146,7 +140,7 @@ __global__ __launch_bounds__(kSegThreads) void frames_seg_emit_kernel(FrameSegPa
     const int R = p.phases, L = p.sync_len;
     const int halo = (L - 1) * R, starts = kAcqTile / R;   // starts on the phase per tile
     const int rounds = (starts + kSegLanes - 1) / kSegLanes;
-    const long long span = frame_span(q);
+    const long long span = frame_span(q.seg.sync_len, q.frame_symbols, q.seg.phases);
     if (t < DEMOD_MAX_SYNC) s_sync[t] = p.sync[t];
     const unsigned total = *p.w_total;
     for (unsigned g0 = blockIdx.x * kSegWaves; g0 < total; g0 += gridDim.x * kSegWaves) {
@@ -219,29 +213,12 @@ __global__ __launch_bounds__(kSegThreads) void frames_seg_gather_kernel(FrameSeg
         }
     }
     if (q.packed) {
-        // MSB first, each symbol masked to `bits` bits, pad bits 0 (demod_pack_symbols)
         const unsigned bits = (unsigned)q.bits, mask = (1u << bits) - 1u;
         const unsigned long long B = (N * bits + 7) / 8;
         uint8_t *dst = q.packed + s * q.max_frames * B;
         for (unsigned long long e = first; e < nw * B; e += step) {
             const unsigned long long i = e / B, b = e - i * B;
-            const uint8_t *src = sym + hits[i].window + L * R;
-            unsigned long long j = b * 8 / bits;
-            unsigned used = (unsigned)(b * 8 - j * bits);   // bits of symbol j in the bytes before
-            unsigned byte = 0;
-            for (unsigned k = 0; k < 8 && j < N;) {
-                const unsigned v = src[j * R] & mask;
-                const unsigned left = bits - used, room = 8 - k;
-                const unsigned take = left < room ? left : room;
-                byte |= ((v >> (left - take)) & ((1u << take) - 1u)) << (room - take);
-                k += take;
-                used += take;
-                if (used == bits) {
-                    used = 0;
-                    ++j;
-                }
-            }
-            dst[e] = (uint8_t)byte;
+            dst[e] = frame_packed_byte(sym + hits[i].window + L * R, R, N, bits, mask, b);
         }
     }
 }

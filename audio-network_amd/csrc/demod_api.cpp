@@ -1,4 +1,7 @@
-// demod_api.cpp — C ABI host layer of libfskdemod.so (include/demod.h).
+// demod_api.cpp — C ABI host layer of libfskdemod.so (include/demod.h): the
+// handle, the batch and streaming entry points, the segment layout, synth,
+// framing, strerror and version. What runs on the detector's outputs
+// (acquisition, frames) is demod_acquire.cpp; many streams, demod_streams.cpp.
 //
 // Handle lifecycle mirrors the Opus decoder the reference receiver drives
 // (opus_decoder_create/destroy, hardware/src/playback.cpp:67-74); streaming
@@ -432,7 +435,7 @@ int fskd::enqueue_batch(demod_t *st, const int16_t *d_pcm, size_t n_windows, uin
 
 // Device staging of host-pointer calls: samples, and windows of symbols and
 // magnitudes (the two also grow when magnitudes are first asked for).
-static int ensure_dev(demod_t *st, size_t samples, size_t windows, bool mags)
+int fskd::ensure_dev(demod_t *st, size_t samples, size_t windows, bool mags)
 {
     HIP_TRY(st->d_in.reserve(samples, samples / 4 + 64));
     if (windows > st->d_sym.cap || (mags && !st->d_mag.p))
@@ -440,7 +443,7 @@ static int ensure_dev(demod_t *st, size_t samples, size_t windows, bool mags)
     return DEMOD_OK;
 }
 
-static bool is_device_ptr(const void *p)
+bool fskd::is_device_ptr(const void *p)
 {
     if (!p) return false;
     hipPointerAttribute_t a;
@@ -628,788 +631,6 @@ int demod_batch_spectrum_async(demod_t *st, const int16_t *d_pcm, size_t n_windo
     DeviceGuard guard(st->device);
     HIP_TRY(guard.err);
     return enqueue_fft(st, d_pcm, n_windows, d_symbols, d_mags, d_spectrum, (hipStream_t)stream);
-}
-
-// ---- acquisition (acquire.hip) -------------------------------------------
-
-// R = n / hop when it divides and is at most DEMOD_MAX_PHASES, else 0 (n and
-// hop are powers of two for every valid configuration, so R is one)
-static uint32_t acquire_phases(const demod_cfg_t &c)
-{
-    if (c.hop == 0 || c.n % c.hop != 0) return 0;
-    const uint32_t r = c.n / c.hop;
-    return (r >= 1 && r <= DEMOD_MAX_PHASES && (r & (r - 1)) == 0) ? r : 0;
-}
-
-size_t demod_acquire_workspace_size(const demod_cfg_t *cfg)
-{
-    if (validate_cfg(cfg) != DEMOD_OK) return 0;
-    // [kAcqMaxBlocks][R] doubles, then as many 64-bit first-match words
-    return (size_t)2 * kAcqMaxBlocks * acquire_phases(*cfg) * sizeof(double);
-}
-
-// The handle's R when the shape and the sync word are acceptable, else 0.
-// whole: the batch is acquired as one stream and needs R windows (a segment
-// with fewer is an outcome of the segmented call, not a refusal).
-static uint32_t acquire_check(const demod_t *st, size_t n_windows, const uint8_t *sync,
-                              size_t sync_len, uint32_t max_errors, bool whole = true)
-{
-    if (!st) return 0;
-    const uint32_t R = acquire_phases(st->cfg);
-    if (R == 0 || (whole && n_windows < R) || n_windows > 0x7FFFFFFF) return 0;
-    if (sync_len > DEMOD_MAX_SYNC || (sync_len && (!sync || max_errors >= sync_len))) return 0;
-    for (size_t i = 0; i < sync_len; ++i)
-        if (sync[i] >= st->cfg.k) return 0;
-    return R;
-}
-
-int demod_acquire_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
-                        size_t n_windows, const uint8_t *sync, size_t sync_len,
-                        uint32_t max_errors, uint8_t *d_out, size_t cap,
-                        demod_acquire_result_t *d_result, void *d_work, void *stream)
-{
-    if (!d_symbols || !d_mags || !d_result || !d_work) return DEMOD_BAD_ARG;
-    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
-    if (R == 0) return DEMOD_BAD_ARG;
-    if ((cap && !d_out) || ((uintptr_t)d_result & 7) != 0 || ((uintptr_t)d_work & 7) != 0)
-        return DEMOD_BAD_ARG;
-    AcquireParams p;
-    std::memset(&p, 0, sizeof(p));
-    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
-    p.sym = d_symbols;
-    p.mag = d_mags;
-    p.n_windows = (long long)n_windows;
-    p.per_phase = (long long)(n_windows / R);
-    p.phases = (int)R;
-    p.k = (int)st->cfg.k;
-    p.sync_len = (int)sync_len;
-    p.max_errors = max_errors;
-    p.cap = cap;
-    p.out = d_out;
-    p.res = d_result;
-    p.part = static_cast<double *>(d_work);
-    p.first = reinterpret_cast<unsigned long long *>(p.part + (size_t)kAcqMaxBlocks * R);
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    HIP_TRY(launch_acquire(p, (hipStream_t)stream));
-    return DEMOD_OK;
-}
-
-int demod_acquire(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
-                  size_t sync_len, uint32_t max_errors, uint8_t *out, size_t cap,
-                  demod_acquire_result_t *result)
-{
-    if (!pcm || !result || (cap && !out) || ((uintptr_t)pcm & 15) != 0) return DEMOD_BAD_ARG;
-    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
-    if (R == 0) return DEMOD_BAD_ARG;   // before the detector runs
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
-    const bool din = is_device_ptr(pcm);
-    int rc;
-    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
-    HIP_TRY(st->d_acq_work.reserve(demod_acquire_workspace_size(&st->cfg)));  // bytes
-    HIP_TRY(st->d_acq_res.reserve(1));
-    const size_t dcap = std::min(cap, n_windows / R + 1);  // n_out <= ceil(W / R)
-    HIP_TRY(st->d_acq_out.reserve(dcap, dcap / 4 + 16));
-    if (!din)
-        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
-                               st->stream));
-    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
-    if (rc < 0) return rc;
-    rc = demod_acquire_async(st, st->d_sym.p, st->d_mag.p, n_windows, sync, sync_len, max_errors,
-                             dcap ? st->d_acq_out.p : nullptr, dcap, st->d_acq_res.p,
-                             st->d_acq_work.p, st->stream);
-    if (rc < 0) return rc;
-    HIP_TRY(hipMemcpyAsync(result, st->d_acq_res.p, sizeof(*result), hipMemcpyDeviceToHost, st->stream));
-    HIP_TRY(hipStreamSynchronize(st->stream));
-    if (result->n_written)
-        HIP_TRY(hipMemcpy(out, st->d_acq_out.p, result->n_written, hipMemcpyDeviceToHost));
-    return (int)result->n_written;
-}
-
-// ---- segmented acquisition (acquire_segments.hip) --------------------------
-
-size_t demod_acquire_segments_workspace_size(const demod_cfg_t *cfg, size_t max_segments,
-                                             size_t max_windows)
-{
-    if (validate_cfg(cfg) != DEMOD_OK) return 0;
-    const uint32_t R = acquire_phases(*cfg);
-    if (R == 0 || max_segments == 0 || max_segments > DEMOD_MAX_SEGMENTS || max_windows > 0x7FFFFFFF)
-        return 0;
-    const size_t tiles = (max_windows + kAcqTile - 1) / kAcqTile + max_segments;
-    return acquire_seg_header_bytes(max_segments) + tiles * acquire_seg_tile_bytes(R);
-}
-
-int demod_acquire_segments_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
-                                 size_t n_windows, const uint64_t *d_first,
-                                 const uint32_t *d_count, size_t n_segments, const uint8_t *sync,
-                                 size_t sync_len, uint32_t max_errors, uint8_t *d_out, size_t cap,
-                                 demod_acquire_result_t *d_results, void *d_work,
-                                 size_t work_bytes, void *stream)
-{
-    if (!d_symbols || !d_mags || !d_results || !d_work || !d_first || !d_count) return DEMOD_BAD_ARG;
-    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors, false);
-    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
-    if ((cap && !d_out) || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_work & 7) != 0 ||
-        ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_count & 3) != 0)
-        return DEMOD_BAD_ARG;
-    const size_t need = demod_acquire_segments_workspace_size(&st->cfg, n_segments, n_windows);
-    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
-    const size_t head = acquire_seg_header_bytes(n_segments);
-    const size_t budget = (work_bytes - head) / acquire_seg_tile_bytes(R);
-    AcquireSegParams p;
-    std::memset(&p, 0, sizeof(p));
-    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
-    p.sym = d_symbols;
-    p.mag = d_mags;
-    p.seg_first = reinterpret_cast<const unsigned long long *>(d_first);
-    p.seg_count = d_count;
-    p.n_windows = (long long)n_windows;
-    p.n_segments = (unsigned)n_segments;
-    p.budget = (unsigned)std::min<size_t>(budget, 0xFFFFFFFFu);
-    p.phases = (int)R;
-    p.k = (int)st->cfg.k;
-    p.sync_len = (int)sync_len;
-    p.max_errors = max_errors;
-    p.cap = cap;
-    p.out = d_out;
-    p.res = d_results;
-    // the header: first'[S] (8 bytes each), then count', first tile and tiles
-    // [S] and the call's total (4 bytes each); then the tiles' words
-    unsigned char *w = static_cast<unsigned char *>(d_work);
-    p.w_first = reinterpret_cast<unsigned long long *>(w);
-    p.w_count = reinterpret_cast<unsigned *>(w + 8 * n_segments);
-    p.w_tile0 = p.w_count + n_segments;
-    p.w_tiles = p.w_tile0 + n_segments;
-    p.w_total = p.w_tiles + n_segments;
-    p.part = reinterpret_cast<double *>(w + head);
-    p.first = reinterpret_cast<unsigned long long *>(p.part + (size_t)p.budget * R);
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    HIP_TRY(launch_acquire_segments(p, (hipStream_t)stream));
-    return DEMOD_OK;
-}
-
-int demod_acquire_segments(demod_t *st, const int16_t *pcm, size_t n_windows,
-                           const uint64_t *first, const uint32_t *count, size_t n_segments,
-                           const uint8_t *sync, size_t sync_len, uint32_t max_errors,
-                           uint8_t *out, size_t cap, demod_acquire_result_t *results)
-{
-    if (!pcm || !results || !first || !count || (cap && !out) || ((uintptr_t)pcm & 15) != 0)
-        return DEMOD_BAD_ARG;
-    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors);
-    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
-    // the tables are host memory here: refuse what the kernels would clamp
-    size_t longest = 0;
-    unsigned long long tiles = 0, rows = 0;
-    for (size_t s = 0; s < n_segments; ++s) {
-        if (count[s] < R || first[s] > n_windows || count[s] > n_windows - first[s])
-            return DEMOD_BAD_ARG;
-        longest = std::max<size_t>(longest, count[s]);
-        tiles += (count[s] + (size_t)kAcqTile - 1) / kAcqTile;
-        rows += std::min<unsigned long long>(cap, count[s] / R + 1);
-    }
-    if (rows > 0x7FFFFFFF) return DEMOD_BAD_ARG;   // the return value is their sum at most
-    // a workspace for every tile: ceil(cover / T) + S of them. Disjoint segments
-    // fit cover = n_windows; overlapping ones may hold more tiles than the batch
-    const unsigned long long cover = std::max<unsigned long long>(
-        n_windows, tiles > n_segments ? (tiles - n_segments) * kAcqTile : 0);
-    if (cover > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const size_t work = demod_acquire_segments_workspace_size(&st->cfg, n_segments, (size_t)cover);
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
-    const bool din = is_device_ptr(pcm);
-    int rc;
-    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
-    HIP_TRY(st->d_seg_work.reserve(work));  // bytes
-    HIP_TRY(st->d_seg_first.reserve(n_segments));
-    HIP_TRY(st->d_seg_count.reserve(n_segments));
-    HIP_TRY(st->d_seg_res.reserve(n_segments));
-    const size_t dcap = std::min(cap, longest / R + 1);  // n_out <= ceil(count / R)
-    HIP_TRY(st->d_seg_out.reserve(dcap * n_segments, 16));
-    HIP_TRY(st->h_seg_out.reserve(dcap * n_segments));
-    HIP_TRY(hipMemcpyAsync(st->d_seg_first.p, first, n_segments * sizeof(uint64_t),
-                           hipMemcpyHostToDevice, st->stream));
-    HIP_TRY(hipMemcpyAsync(st->d_seg_count.p, count, n_segments * sizeof(uint32_t),
-                           hipMemcpyHostToDevice, st->stream));
-    if (!din)
-        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
-                               st->stream));
-    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
-    if (rc < 0) return rc;
-    rc = demod_acquire_segments_async(st, st->d_sym.p, st->d_mag.p, n_windows, st->d_seg_first.p,
-                                      st->d_seg_count.p, n_segments, sync, sync_len, max_errors,
-                                      dcap ? st->d_seg_out.p : nullptr, dcap, st->d_seg_res.p,
-                                      st->d_seg_work.p, work, st->stream);
-    if (rc < 0) return rc;
-    HIP_TRY(hipMemcpyAsync(results, st->d_seg_res.p, n_segments * sizeof(*results),
-                           hipMemcpyDeviceToHost, st->stream));
-    // the rows through pinned staging in the same pass, then each row's written
-    // bytes to the caller's [S][cap]
-    if (dcap)
-        HIP_TRY(hipMemcpyAsync(st->h_seg_out.p, st->d_seg_out.p, dcap * n_segments,
-                               hipMemcpyDeviceToHost, st->stream));
-    HIP_TRY(hipStreamSynchronize(st->stream));
-    unsigned long long total = 0;
-    for (size_t s = 0; s < n_segments; ++s) {
-        const size_t nw = (size_t)results[s].n_written;
-        if (nw) std::memcpy(out + s * cap, st->h_seg_out.p + s * dcap, nw);
-        total += nw;
-    }
-    return (int)total;
-}
-
-// ---- frame scan (acquire_frames.hip) ---------------------------------------
-
-size_t demod_frames_workspace_size(const demod_cfg_t *cfg, size_t max_windows)
-{
-    if (validate_cfg(cfg) != DEMOD_OK) return 0;
-    const uint32_t R = acquire_phases(*cfg);
-    if (R == 0 || max_windows > 0x7FFFFFFF) return 0;
-    return frames_work_bytes((max_windows + kAcqTile - 1) / kAcqTile, R);
-}
-
-// The handle's R when a frame scan of these arguments is acceptable, else 0:
-// what acquire_check refuses, no word, or a frame of 2^31 windows or more.
-static uint32_t frames_check(const demod_t *st, size_t n_windows, const uint8_t *sync,
-                             size_t sync_len, uint32_t max_errors, size_t frame_symbols,
-                             size_t max_frames, bool whole = true)
-{
-    const uint32_t R = acquire_check(st, n_windows, sync, sync_len, max_errors, whole);
-    if (R == 0 || sync_len == 0 || max_frames > 0x7FFFFFFF) return 0;
-    if (frame_symbols > 0x7FFFFFFF || (sync_len + frame_symbols) * R > 0x7FFFFFFF) return 0;
-    return R;
-}
-
-int demod_frames_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
-                       size_t n_windows, const uint8_t *sync, size_t sync_len,
-                       uint32_t max_errors, size_t frame_symbols, demod_frame_hit_t *d_hits,
-                       uint8_t *d_payload, uint8_t *d_packed, size_t max_frames,
-                       demod_frames_result_t *d_result, void *d_work, size_t work_bytes,
-                       void *stream)
-{
-    if (!d_symbols || !d_mags || !d_result || !d_work) return DEMOD_BAD_ARG;
-    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
-    if (R == 0) return DEMOD_BAD_ARG;
-    if ((max_frames && !d_hits) || ((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_result & 7) != 0 ||
-        ((uintptr_t)d_work & 7) != 0)
-        return DEMOD_BAD_ARG;
-    const size_t need = demod_frames_workspace_size(&st->cfg, n_windows);
-    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
-    const size_t tiles = (n_windows + kAcqTile - 1) / kAcqTile;
-    FramesParams p;
-    std::memset(&p, 0, sizeof(p));
-    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
-    p.sym = d_symbols;
-    p.mag = d_mags;
-    p.n_windows = (long long)n_windows;
-    p.per_phase = (long long)(n_windows / R);
-    p.frame_symbols = (long long)frame_symbols;
-    p.phases = (int)R;
-    p.k = (int)st->cfg.k;
-    p.bits = demod_bits_per_symbol(st->cfg.k);
-    p.sync_len = (int)sync_len;
-    p.max_errors = max_errors;
-    p.max_frames = max_frames;
-    p.hits = d_hits;
-    p.payload = d_payload;
-    p.packed = d_packed;
-    p.res = d_result;
-    p.part = static_cast<double *>(d_work);
-    p.tail = reinterpret_cast<unsigned long long *>(p.part + (size_t)kAcqMaxBlocks * R);
-    p.offs = reinterpret_cast<unsigned *>(p.tail + (size_t)kAcqMaxBlocks * R);
-    p.count = p.offs + (tiles + 1) / 2 * 2;
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    HIP_TRY(launch_frames(p, (hipStream_t)stream));
-    return DEMOD_OK;
-}
-
-int demod_frames(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
-                 size_t sync_len, uint32_t max_errors, size_t frame_symbols,
-                 demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed, size_t max_frames,
-                 demod_frames_result_t *result)
-{
-    if (!pcm || !result || (max_frames && !hits) || ((uintptr_t)pcm & 15) != 0) return DEMOD_BAD_ARG;
-    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
-    if (R == 0) return DEMOD_BAD_ARG;   // before the detector runs
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
-    const bool din = is_device_ptr(pcm);
-    const size_t N = frame_symbols;
-    const size_t B = (N * (size_t)demod_bits_per_symbol(st->cfg.k) + 7) / 8;
-    int rc;
-    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
-    const size_t work = demod_frames_workspace_size(&st->cfg, n_windows);
-    HIP_TRY(st->d_frm_work.reserve(work));  // bytes
-    HIP_TRY(st->d_frm_res.reserve(1));
-    // complete hits are starts on one phase whose frame fits: W / R + 1 bounds them
-    const size_t dcap = std::min(max_frames, n_windows / R + 1);
-    const bool want_payload = payload && N && dcap, want_packed = packed && N && dcap;
-    HIP_TRY(st->d_frm_hits.reserve(dcap));
-    if (want_payload) HIP_TRY(st->d_frm_payload.reserve(dcap * N));
-    if (want_packed) HIP_TRY(st->d_frm_packed.reserve(dcap * B));
-    if (!din)
-        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
-                               st->stream));
-    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
-    if (rc < 0) return rc;
-    rc = demod_frames_async(st, st->d_sym.p, st->d_mag.p, n_windows, sync, sync_len, max_errors, N,
-                            dcap ? st->d_frm_hits.p : nullptr,
-                            want_payload ? st->d_frm_payload.p : nullptr,
-                            want_packed ? st->d_frm_packed.p : nullptr, dcap, st->d_frm_res.p,
-                            st->d_frm_work.p, work, st->stream);
-    if (rc < 0) return rc;
-    HIP_TRY(hipMemcpyAsync(result, st->d_frm_res.p, sizeof(*result), hipMemcpyDeviceToHost, st->stream));
-    HIP_TRY(hipStreamSynchronize(st->stream));
-    // the device list was cut at dcap >= every possible n_hits or at max_frames
-    const size_t nw = (size_t)result->n_written;
-    if (nw) {
-        HIP_TRY(hipMemcpy(hits, st->d_frm_hits.p, nw * sizeof(*hits), hipMemcpyDeviceToHost));
-        if (want_payload) HIP_TRY(hipMemcpy(payload, st->d_frm_payload.p, nw * N, hipMemcpyDeviceToHost));
-        if (want_packed) HIP_TRY(hipMemcpy(packed, st->d_frm_packed.p, nw * B, hipMemcpyDeviceToHost));
-    }
-    return (int)nw;
-}
-
-// ---- segmented frame scan (acquire_frames_segments.hip) ---------------------
-
-size_t demod_frames_segments_workspace_size(const demod_cfg_t *cfg, size_t max_segments,
-                                            size_t max_windows)
-{
-    if (validate_cfg(cfg) != DEMOD_OK) return 0;
-    const uint32_t R = acquire_phases(*cfg);
-    if (R == 0 || max_segments == 0 || max_segments > DEMOD_MAX_SEGMENTS || max_windows > 0x7FFFFFFF)
-        return 0;
-    const size_t tiles = (max_windows + kAcqTile - 1) / kAcqTile + max_segments;
-    return acquire_seg_header_bytes(max_segments) + frames_seg_tiles_bytes(tiles, R);
-}
-
-int demod_frames_segments_async(demod_t *st, const uint8_t *d_symbols, const float *d_mags,
-                                size_t n_windows, const uint64_t *d_first, const uint32_t *d_count,
-                                size_t n_segments, const uint8_t *sync, size_t sync_len,
-                                uint32_t max_errors, size_t frame_symbols, demod_frame_hit_t *d_hits,
-                                uint8_t *d_payload, uint8_t *d_packed, size_t max_frames,
-                                demod_frames_result_t *d_results, void *d_work, size_t work_bytes,
-                                void *stream)
-{
-    if (!d_symbols || !d_mags || !d_results || !d_work || !d_first || !d_count) return DEMOD_BAD_ARG;
-    const uint32_t R =
-        frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames, false);
-    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
-    if ((unsigned long long)n_segments * max_frames > 0x7FFFFFFFull) return DEMOD_BAD_ARG;
-    if ((max_frames && !d_hits) || ((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 ||
-        ((uintptr_t)d_work & 7) != 0 || ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_count & 3) != 0)
-        return DEMOD_BAD_ARG;
-    const size_t need = demod_frames_segments_workspace_size(&st->cfg, n_segments, n_windows);
-    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
-    const size_t head = acquire_seg_header_bytes(n_segments);
-    const size_t budget = std::min<size_t>(frames_seg_budget(work_bytes - head, R), 0xFFFFFFFFu);
-    FrameSegParams q;
-    std::memset(&q, 0, sizeof(q));
-    AcquireSegParams &p = q.seg;
-    for (size_t i = 0; i < sync_len; ++i) p.sync[i] = sync[i];
-    p.sym = d_symbols;
-    p.mag = d_mags;
-    p.seg_first = reinterpret_cast<const unsigned long long *>(d_first);
-    p.seg_count = d_count;
-    p.n_windows = (long long)n_windows;
-    p.n_segments = (unsigned)n_segments;
-    p.budget = (unsigned)budget;
-    p.phases = (int)R;
-    p.k = (int)st->cfg.k;
-    p.sync_len = (int)sync_len;
-    p.max_errors = max_errors;
-    // the header as demod_acquire_segments_async lays it out, then the tiles'
-    // words: part and tail [B][R], count [B][R], offs [B]
-    unsigned char *w = static_cast<unsigned char *>(d_work);
-    p.w_first = reinterpret_cast<unsigned long long *>(w);
-    p.w_count = reinterpret_cast<unsigned *>(w + 8 * n_segments);
-    p.w_tile0 = p.w_count + n_segments;
-    p.w_tiles = p.w_tile0 + n_segments;
-    p.w_total = p.w_tiles + n_segments;
-    p.part = reinterpret_cast<double *>(w + head);
-    p.first = reinterpret_cast<unsigned long long *>(p.part + budget * R);
-    q.count = reinterpret_cast<unsigned *>(p.first + budget * R);
-    q.offs = q.count + (budget * R + 1) / 2 * 2;
-    q.frame_symbols = (long long)frame_symbols;
-    q.bits = demod_bits_per_symbol(st->cfg.k);
-    q.max_frames = max_frames;
-    q.hits = d_hits;
-    q.payload = d_payload;
-    q.packed = d_packed;
-    q.res = d_results;
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    HIP_TRY(launch_frames_segments(q, (hipStream_t)stream));
-    return DEMOD_OK;
-}
-
-int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, const uint64_t *first,
-                          const uint32_t *count, size_t n_segments, const uint8_t *sync,
-                          size_t sync_len, uint32_t max_errors, size_t frame_symbols,
-                          demod_frame_hit_t *hits, uint8_t *payload, uint8_t *packed,
-                          size_t max_frames, demod_frames_result_t *results)
-{
-    if (!pcm || !results || !first || !count || (max_frames && !hits) || ((uintptr_t)pcm & 15) != 0)
-        return DEMOD_BAD_ARG;
-    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
-    if (R == 0 || n_segments == 0 || n_segments > DEMOD_MAX_SEGMENTS) return DEMOD_BAD_ARG;
-    // the tables are host memory here: refuse what the kernels would clamp
-    size_t longest = 0;
-    unsigned long long tiles = 0, rows = 0;
-    for (size_t s = 0; s < n_segments; ++s) {
-        if (count[s] < R || first[s] > n_windows || count[s] > n_windows - first[s])
-            return DEMOD_BAD_ARG;
-        longest = std::max<size_t>(longest, count[s]);
-        tiles += (count[s] + (size_t)kAcqTile - 1) / kAcqTile;
-        rows += std::min<unsigned long long>(max_frames, count[s] / R + 1);
-    }
-    if (rows > 0x7FFFFFFF) return DEMOD_BAD_ARG;   // the return value is their sum at most
-    // complete hits are starts on one phase whose frame fits: count / R + 1 bounds them
-    const size_t dcap = std::min(max_frames, longest / R + 1);
-    if ((unsigned long long)n_segments * dcap > 0x7FFFFFFFull) return DEMOD_BAD_ARG;
-    // a workspace for every tile (overlapping segments may hold more than the batch)
-    const unsigned long long cover = std::max<unsigned long long>(
-        n_windows, tiles > n_segments ? (tiles - n_segments) * kAcqTile : 0);
-    if (cover > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const size_t work = demod_frames_segments_workspace_size(&st->cfg, n_segments, (size_t)cover);
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
-    const bool din = is_device_ptr(pcm);
-    const size_t N = frame_symbols;
-    const size_t B = (N * (size_t)demod_bits_per_symbol(st->cfg.k) + 7) / 8;
-    const size_t n_rows = dcap * n_segments;
-    const bool want_payload = payload && N && dcap, want_packed = packed && N && dcap;
-    int rc;
-    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
-    HIP_TRY(st->d_seg_work.reserve(work));  // bytes
-    HIP_TRY(st->d_seg_first.reserve(n_segments));
-    HIP_TRY(st->d_seg_count.reserve(n_segments));
-    HIP_TRY(st->d_fsg_res.reserve(n_segments));
-    HIP_TRY(st->d_fsg_hits.reserve(n_rows));
-    HIP_TRY(st->h_fsg_hits.reserve(n_rows));
-    if (want_payload) {
-        HIP_TRY(st->d_fsg_payload.reserve(n_rows * N));
-        HIP_TRY(st->h_fsg_payload.reserve(n_rows * N));
-    }
-    if (want_packed) {
-        HIP_TRY(st->d_fsg_packed.reserve(n_rows * B));
-        HIP_TRY(st->h_fsg_packed.reserve(n_rows * B));
-    }
-    HIP_TRY(hipMemcpyAsync(st->d_seg_first.p, first, n_segments * sizeof(uint64_t),
-                           hipMemcpyHostToDevice, st->stream));
-    HIP_TRY(hipMemcpyAsync(st->d_seg_count.p, count, n_segments * sizeof(uint32_t),
-                           hipMemcpyHostToDevice, st->stream));
-    if (!din)
-        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
-                               st->stream));
-    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
-    if (rc < 0) return rc;
-    rc = demod_frames_segments_async(st, st->d_sym.p, st->d_mag.p, n_windows, st->d_seg_first.p,
-                                     st->d_seg_count.p, n_segments, sync, sync_len, max_errors, N,
-                                     dcap ? st->d_fsg_hits.p : nullptr,
-                                     want_payload ? st->d_fsg_payload.p : nullptr,
-                                     want_packed ? st->d_fsg_packed.p : nullptr, dcap, st->d_fsg_res.p,
-                                     st->d_seg_work.p, work, st->stream);
-    if (rc < 0) return rc;
-    HIP_TRY(hipMemcpyAsync(results, st->d_fsg_res.p, n_segments * sizeof(*results),
-                           hipMemcpyDeviceToHost, st->stream));
-    // the rows through pinned staging in the same pass, then each segment's
-    // written rows to the caller's [S][max_frames]
-    if (dcap) {
-        HIP_TRY(hipMemcpyAsync(st->h_fsg_hits.p, st->d_fsg_hits.p, n_rows * sizeof(*hits),
-                               hipMemcpyDeviceToHost, st->stream));
-        if (want_payload)
-            HIP_TRY(hipMemcpyAsync(st->h_fsg_payload.p, st->d_fsg_payload.p, n_rows * N,
-                                   hipMemcpyDeviceToHost, st->stream));
-        if (want_packed)
-            HIP_TRY(hipMemcpyAsync(st->h_fsg_packed.p, st->d_fsg_packed.p, n_rows * B,
-                                   hipMemcpyDeviceToHost, st->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(st->stream));
-    unsigned long long total = 0;
-    for (size_t s = 0; s < n_segments; ++s) {
-        const size_t nw = (size_t)results[s].n_written;
-        if (nw) {
-            std::memcpy(hits + s * max_frames, st->h_fsg_hits.p + s * dcap, nw * sizeof(*hits));
-            if (want_payload)
-                std::memcpy(payload + s * max_frames * N, st->h_fsg_payload.p + s * dcap * N, nw * N);
-            if (want_packed)
-                std::memcpy(packed + s * max_frames * B, st->h_fsg_packed.p + s * dcap * B, nw * B);
-        }
-        total += nw;
-    }
-    return (int)total;
-}
-
-// ---- checked frames (frames_check.hip) ---------------------------------------
-
-// Fills what the shape decides (row width, max_len, the CRC's constants, R,
-// bits, L); false for what demod_frames_check_async refuses about it.
-static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_frames, size_t sync_len,
-                               size_t frame_symbols, int len_bytes, int crc, FramesCheckParams &p,
-                               int fec = 0)
-{
-    if (!st) return false;
-    const uint32_t R = acquire_phases(st->cfg);
-    if (R == 0 || n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames == 0) return false;
-    if (max_frames > 0x7FFFFFFF || (unsigned long long)n_groups * max_frames > 0x7FFFFFFFull) return false;
-    if (sync_len == 0 || sync_len > DEMOD_MAX_SYNC || (len_bytes != 1 && len_bytes != 2)) return false;
-    if (crc != DEMOD_CRC16_CCITT_FALSE && crc != DEMOD_CRC32_MPEG2) return false;
-    const size_t bits = (size_t)demod_bits_per_symbol(st->cfg.k);
-    const size_t c = crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4, h = (size_t)len_bytes;
-    if (frame_symbols > 0x7FFFFFFF) return false;
-    size_t B = (frame_symbols * bits + 7) / 8;
-    if (fec) {
-        // coded rows: St = floor(N bits / 2) steps decode to Bd = (St - 6) / 8 bytes
-        const size_t St = frame_symbols * bits / 2;
-        if (fec != DEMOD_FEC_CONV_K7 || st->cfg.k != (1u << bits)) return false;
-        if (St < 8 * h + DEMOD_FEC_DEPTH) return false;
-        B = (St - 6) / 8;
-        p.fec_depth = DEMOD_FEC_DEPTH;
-    }
-    if (B < h + c || B - h - c > DEMOD_MAX_FRAME_PAYLOAD) return false;
-    p.n_groups = (unsigned)n_groups;
-    p.max_frames = (unsigned)max_frames;
-    p.row_bytes = (unsigned)B;
-    p.max_len = (unsigned)(B - h - c);
-    p.len_bytes = len_bytes;
-    p.crc_bytes = (int)c;
-    p.poly = c == 2 ? 0x1021u << 16 : 0x04C11DB7u;
-    p.init = c == 2 ? 0xFFFFu << 16 : 0xFFFFFFFFu;
-    // x^8, then its squares mod P (Horner over the square's own coefficients, highest first)
-    static_assert(DEMOD_MAX_FRAME_PAYLOAD + 2 < (1 << kCrcPowBits), "bytes after a lane's chunk");
-    const int width = 8 * (int)c;
-    p.xpow8[0] = 1u << (32 - width + 8);
-    for (int j = 1; j < kCrcPowBits; ++j) {
-        const uint32_t a = p.xpow8[j - 1];
-        uint32_t r = 0, b = a;
-        for (int i = 0; i < width; ++i, b <<= 1)
-            r = (r << 1) ^ ((r >> 31) ? p.poly : 0u) ^ ((b >> 31) ? a : 0u);
-        p.xpow8[j] = r;
-    }
-    p.bits = (int)bits;
-    p.phases = (int)R;
-    p.sync_len = (int)sync_len;
-    return true;
-}
-
-// fec 0: the scan's packed rows; else decoded rows (the coded entry has refused fec 0)
-static int frames_check_enqueue(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_packed,
-                                const demod_frames_result_t *d_results, size_t n_groups,
-                                size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
-                                int crc, int fec, demod_frame_check_t *d_check, uint32_t *d_kept,
-                                uint8_t *d_body, demod_frames_check_result_t *d_summary, void *stream)
-{
-    if (!st || !d_hits || !d_packed || !d_results || !d_check || !d_kept || !d_summary) return DEMOD_BAD_ARG;
-    if (((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_summary & 7) != 0 ||
-        ((uintptr_t)d_check & 3) != 0 || ((uintptr_t)d_kept & 3) != 0)
-        return DEMOD_BAD_ARG;
-    FramesCheckParams p;
-    std::memset(&p, 0, sizeof(p));
-    if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, p, fec))
-        return DEMOD_BAD_ARG;
-    p.hits = d_hits;
-    p.packed = d_packed;
-    p.res = d_results;
-    p.check = d_check;
-    p.kept = d_kept;
-    p.body = d_body;
-    p.summary = d_summary;
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    HIP_TRY(launch_frames_check(p, (hipStream_t)stream));
-    return DEMOD_OK;
-}
-
-int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_packed,
-                             const demod_frames_result_t *d_results, size_t n_groups,
-                             size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
-                             int crc, demod_frame_check_t *d_check, uint32_t *d_kept, uint8_t *d_body,
-                             demod_frames_check_result_t *d_summary, void *stream)
-{
-    return frames_check_enqueue(st, d_hits, d_packed, d_results, n_groups, max_frames, sync_len,
-                                frame_symbols, len_bytes, crc, 0, d_check, d_kept, d_body, d_summary, stream);
-}
-
-// ---- coded frames (frames_fec.hip) -------------------------------------------
-
-size_t demod_frames_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
-                                          size_t frame_symbols)
-{
-    if (validate_cfg(cfg) != DEMOD_OK || cfg->k < 2 || (cfg->k & (cfg->k - 1)) != 0) return 0;
-    if (n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames == 0 || max_frames > 0x7FFFFFFF) return 0;
-    if ((unsigned long long)n_groups * max_frames > 0x7FFFFFFFull) return 0;
-    if (frame_symbols == 0 || frame_symbols > 0x7FFFFFFF) return 0;
-    const size_t St = frame_symbols * (size_t)demod_bits_per_symbol(cfg->k) / 2;
-    return n_groups * (size_t)fec_waves_per_group((unsigned)n_groups, (unsigned)max_frames) * St * 8;
-}
-
-int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, const float *d_mags,
-                              size_t n_windows, const uint64_t *d_first,
-                              const demod_frames_result_t *d_results, size_t n_groups,
-                              size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
-                              int crc, int fec, uint8_t *d_rows, demod_frame_decode_t *d_decode,
-                              void *d_work, size_t work_bytes, void *stream)
-{
-    if (!st || !d_hits || !d_mags || !d_results || !d_rows || !d_decode || !d_work) return DEMOD_BAD_ARG;
-    if (((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_work & 7) != 0 ||
-        ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_decode & 3) != 0)
-        return DEMOD_BAD_ARG;
-    if (fec != DEMOD_FEC_CONV_K7 || n_windows > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    FramesCheckParams q;   // the shape the coded check will see: the same refusals
-    std::memset(&q, 0, sizeof(q));
-    if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, q, fec))
-        return DEMOD_BAD_ARG;
-    if ((sync_len + frame_symbols) * (size_t)q.phases > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const size_t need = demod_frames_decode_workspace_size(&st->cfg, n_groups, max_frames, frame_symbols);
-    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
-    FramesFecParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.hits = d_hits;
-    p.mag = d_mags;
-    p.first = reinterpret_cast<const unsigned long long *>(d_first);
-    p.res = d_results;
-    p.n_windows = (unsigned)n_windows;
-    p.n_groups = q.n_groups;
-    p.max_frames = q.max_frames;
-    p.frame_symbols = (unsigned)frame_symbols;
-    p.steps = (unsigned)(frame_symbols * (size_t)q.bits / 2);
-    p.row_bytes = q.row_bytes;
-    p.max_len = q.max_len;
-    p.len_bytes = q.len_bytes;
-    p.crc_bytes = q.crc_bytes;
-    p.k = (int)st->cfg.k;
-    p.bits = q.bits;
-    p.phases = q.phases;
-    p.sync_len = q.sync_len;
-    p.rows = d_rows;
-    p.decode = d_decode;
-    p.work = static_cast<unsigned long long *>(d_work);
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    HIP_TRY(launch_frames_decode(p, (hipStream_t)stream));
-    return DEMOD_OK;
-}
-
-int demod_frames_check_coded_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_rows,
-                                   const demod_frames_result_t *d_results, size_t n_groups,
-                                   size_t max_frames, size_t sync_len, size_t frame_symbols,
-                                   int len_bytes, int crc, int fec, demod_frame_check_t *d_check,
-                                   uint32_t *d_kept, uint8_t *d_body,
-                                   demod_frames_check_result_t *d_summary, void *stream)
-{
-    if (fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
-    return frames_check_enqueue(st, d_hits, d_rows, d_results, n_groups, max_frames, sync_len,
-                                frame_symbols, len_bytes, crc, fec, d_check, d_kept, d_body, d_summary, stream);
-}
-
-// demod_frames_checked (fec 0: the scan's packed rows) and demod_frames_coded
-static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
-                              size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
-                              int crc, int fec, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
-                              size_t max_frames, demod_frames_result_t *result,
-                              demod_frames_check_result_t *summary)
-{
-    if (!pcm || !result || !summary || !hits || !lengths || ((uintptr_t)pcm & 15) != 0) return DEMOD_BAD_ARG;
-    const uint32_t R = frames_check(st, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames);
-    if (R == 0) return DEMOD_BAD_ARG;   // before the detector runs
-    // complete hits are starts on one phase whose frame fits: W / R + 1 bounds them
-    const size_t dcap = std::min(max_frames, n_windows / R + 1);
-    FramesCheckParams p;
-    std::memset(&p, 0, sizeof(p));
-    if (!frames_check_shape(st, 1, dcap, sync_len, frame_symbols, len_bytes, crc, p, fec)) return DEMOD_BAD_ARG;
-    const size_t fec_work = fec ? demod_frames_decode_workspace_size(&st->cfg, 1, dcap, frame_symbols) : 0;
-    DeviceGuard guard(st->device);
-    HIP_TRY(guard.err);
-    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
-    const bool din = is_device_ptr(pcm);
-    const size_t N = frame_symbols, B = p.row_bytes, M = p.max_len;
-    const bool want_body = body && M;
-    int rc;
-    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
-    const size_t work = demod_frames_workspace_size(&st->cfg, n_windows);
-    HIP_TRY(st->d_frm_work.reserve(work));  // bytes
-    HIP_TRY(st->d_frm_res.reserve(1));
-    HIP_TRY(st->d_frm_hits.reserve(dcap));
-    if (fec) {
-        HIP_TRY(st->d_fec_rows.reserve(dcap * B));
-        HIP_TRY(st->d_fec_decode.reserve(dcap));
-        HIP_TRY(st->d_fec_work.reserve(fec_work));  // bytes
-    } else {
-        HIP_TRY(st->d_frm_packed.reserve(dcap * B));
-    }
-    HIP_TRY(st->d_chk_check.reserve(dcap));
-    HIP_TRY(st->d_chk_kept.reserve(dcap));
-    HIP_TRY(st->d_chk_sum.reserve(1));
-    HIP_TRY(st->d_chk_hits.reserve(dcap));
-    HIP_TRY(st->d_chk_len.reserve(dcap));
-    if (want_body) HIP_TRY(st->d_chk_body.reserve(dcap * M));
-    if (!din)
-        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
-                               st->stream));
-    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
-    if (rc < 0) return rc;
-    rc = demod_frames_async(st, st->d_sym.p, st->d_mag.p, n_windows, sync, sync_len, max_errors, N,
-                            st->d_frm_hits.p, nullptr, fec ? nullptr : st->d_frm_packed.p, dcap,
-                            st->d_frm_res.p, st->d_frm_work.p, work, st->stream);
-    if (rc < 0) return rc;
-    if (fec) {
-        rc = demod_frames_decode_async(st, st->d_frm_hits.p, st->d_mag.p, n_windows, nullptr, st->d_frm_res.p,
-                                       1, dcap, sync_len, N, len_bytes, crc, fec, st->d_fec_rows.p,
-                                       st->d_fec_decode.p, st->d_fec_work.p, fec_work, st->stream);
-        if (rc < 0) return rc;
-    }
-    rc = frames_check_enqueue(st, st->d_frm_hits.p, fec ? st->d_fec_rows.p : st->d_frm_packed.p,
-                              st->d_frm_res.p, 1, dcap, sync_len, N, len_bytes, crc, fec, st->d_chk_check.p,
-                              st->d_chk_kept.p, want_body ? st->d_chk_body.p : nullptr, st->d_chk_sum.p,
-                              st->stream);
-    if (rc < 0) return rc;
-    // the kept rows' hits and lengths side by side, so that only they cross to the host
-    HIP_TRY(launch_frames_kept_rows(st->d_frm_hits.p, st->d_chk_check.p, st->d_chk_kept.p, st->d_chk_sum.p,
-                                    (unsigned)dcap, st->d_chk_hits.p, st->d_chk_len.p, st->stream));
-    HIP_TRY(hipMemcpyAsync(result, st->d_frm_res.p, sizeof(*result), hipMemcpyDeviceToHost, st->stream));
-    HIP_TRY(hipMemcpyAsync(summary, st->d_chk_sum.p, sizeof(*summary), hipMemcpyDeviceToHost, st->stream));
-    HIP_TRY(hipStreamSynchronize(st->stream));
-    const size_t nk = (size_t)summary->n_kept;
-    if (nk) {
-        HIP_TRY(hipMemcpy(hits, st->d_chk_hits.p, nk * sizeof(*hits), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(lengths, st->d_chk_len.p, nk * sizeof(*lengths), hipMemcpyDeviceToHost));
-        if (want_body) {
-            // a body row holds its frame's bytes alone: the rest of the caller's row is left as it is
-            st->h_chk_body.resize(nk * M);
-            HIP_TRY(hipMemcpy(st->h_chk_body.data(), st->d_chk_body.p, nk * M, hipMemcpyDeviceToHost));
-            for (size_t r = 0; r < nk; ++r)
-                std::memcpy(body + r * M, st->h_chk_body.data() + r * M, lengths[r]);
-        }
-    }
-    return (int)nk;
-}
-
-int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
-                         size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
-                         int crc, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
-                         size_t max_frames, demod_frames_result_t *result,
-                         demod_frames_check_result_t *summary)
-{
-    return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
-                              0, hits, lengths, body, max_frames, result, summary);
-}
-
-int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
-                       size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
-                       int crc, int fec, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
-                       size_t max_frames, demod_frames_result_t *result,
-                       demod_frames_check_result_t *summary)
-{
-    if (fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
-    return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
-                              fec, hits, lengths, body, max_frames, result, summary);
 }
 
 int demod_segments_layout(const demod_cfg_t *cfg, size_t n_segments, const size_t *n_samples,

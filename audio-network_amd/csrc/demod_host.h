@@ -1,5 +1,6 @@
-// demod_host.h — what the host layer's two files share (private):
-// demod_api.cpp (handle, batch, acquire and streaming entry points) and
+// demod_host.h — what the host layer's three files share (private):
+// demod_api.cpp (handle, batch and streaming entry points), demod_acquire.cpp
+// (acquisition and frame entry points on the detector's outputs) and
 // demod_streams.cpp (many streams behind one handle).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -209,5 +210,9 @@ int run_host(demod_t *st, const int16_t *pcm, size_t n_samples, size_t n_windows
              float *mags);
 // The pinned staging buffers of small host calls.
 int ensure_host(demod_t *st, size_t samples, size_t windows);
+// The device staging of host-pointer calls: st->d_in, st->d_sym and st->d_mag.
+int ensure_dev(demod_t *st, size_t samples, size_t windows, bool mags);
+// Device or managed memory (a host pointer, or one the runtime does not know: false).
+bool is_device_ptr(const void *p);
 
 }  // namespace fskd

@@ -264,6 +264,21 @@ struct AcquireSegParams {
 // Bytes of the header for S segments, and of one tile's words (8-byte multiples).
 constexpr size_t acquire_seg_header_bytes(size_t S) { return (20 * S + 4 + 7) / 8 * 8; }
 constexpr size_t acquire_seg_tile_bytes(size_t R) { return 16 * R; }
+// The pointers into d_work, for both segmented scans. The header: first'[S]
+// (8 bytes each), then count', first tile and tiles [S] and the call's total
+// (4 bytes each); then the tiles' words, which begin with part and first
+// [budget][R] (acquire_frames_segments.hip's count and offs follow them).
+inline void carve_seg_header(AcquireSegParams &p, void *d_work, size_t n_segments, size_t budget, size_t R)
+{
+    unsigned char *w = static_cast<unsigned char *>(d_work);
+    p.w_first = reinterpret_cast<unsigned long long *>(w);
+    p.w_count = reinterpret_cast<unsigned *>(w + 8 * n_segments);
+    p.w_tile0 = p.w_count + n_segments;
+    p.w_tiles = p.w_tile0 + n_segments;
+    p.w_total = p.w_tiles + n_segments;
+    p.part = reinterpret_cast<double *>(w + acquire_seg_header_bytes(n_segments));
+    p.first = reinterpret_cast<unsigned long long *>(p.part + budget * R);
+}
 hipError_t launch_acquire_segments(const AcquireSegParams &p, hipStream_t s);
 
 // acquire_frames.hip: every sync-word hit on the acquired phase, in window
