@@ -234,6 +234,48 @@ FRAME_DECODE_DTYPE = np.dtype([("length", "<u4"), ("metric", "<i4"), ("status", 
                                ("steps", "<u4")])                                         # DemodFrameDecode
 
 
+class DemodRxCfg(ctypes.Structure):
+    """demod_rx_cfg_t (include/demod.h "receiver"): the frame format and the
+    sizes of a receiver."""
+    _fields_ = [("sync", ctypes.c_uint8 * DEMOD_MAX_SYNC), ("sync_len", ctypes.c_uint32),
+                ("max_errors", ctypes.c_uint32), ("frame_symbols", ctypes.c_uint32),
+                ("len_bytes", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("fec", ctypes.c_uint32),
+                ("max_frames", ctypes.c_uint32), ("ring_windows", ctypes.c_uint32)]
+
+
+class DemodRxFrame(ctypes.Structure):
+    """demod_rx_frame_t: one emitted frame of a push."""
+    _fields_ = [("stream", ctypes.c_uint32), ("length", ctypes.c_uint32), ("window", ctypes.c_uint64),
+                ("body", ctypes.c_uint64), ("errors", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class DemodRxStreamState(ctypes.Structure):
+    """demod_rx_stream_state_t: one stream's carry state, device and host."""
+    _fields_ = [("base", ctypes.c_uint64), ("hold", ctypes.c_uint64), ("dropped", ctypes.c_uint64),
+                ("cut_hits", ctypes.c_uint64), ("fill", ctypes.c_uint32), ("keep", ctypes.c_uint32)]
+
+
+class DemodRxSummary(ctypes.Structure):
+    """demod_rx_summary_t: the totals of one push."""
+    _fields_ = [("n_frames", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("n_checked", ctypes.c_uint64),
+                ("n_valid", ctypes.c_uint64)]
+
+
+class DemodRxSizes(ctypes.Structure):
+    """demod_rx_sizes_t: what demod_rx_sizes reports."""
+    _fields_ = [(f, ctypes.c_uint64) for f in (
+        "max_len", "row_bytes", "ring_sym_bytes", "ring_mag_bytes", "scan_work_bytes", "decode_work_bytes",
+        "collect_work_bytes", "frames_bytes", "bodies_bytes")]
+
+
+RX_FRAME_DTYPE = np.dtype([("stream", "<u4"), ("length", "<u4"), ("window", "<u8"), ("body", "<u8"),
+                           ("errors", "<u4"), ("reserved", "<u4")])                       # DemodRxFrame
+RX_STATE_DTYPE = np.dtype([("base", "<u8"), ("hold", "<u8"), ("dropped", "<u8"), ("cut_hits", "<u8"),
+                           ("fill", "<u4"), ("keep", "<u4")])                             # DemodRxStreamState
+RX_SUMMARY_DTYPE = np.dtype([("n_frames", "<u8"), ("n_bytes", "<u8"), ("n_checked", "<u8"),
+                             ("n_valid", "<u8")])                                         # DemodRxSummary
+
+
 class DemodError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -368,6 +410,21 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "demod_streams_push": (ctypes.c_int, [_P, _P, _P, _P, _P, _SZ, _P]),
         "demod_streams_push_packets": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _SZ,
                                                       _P]),
+        "demod_rx_sizes": (ctypes.c_int, [ctypes.POINTER(DemodCfg), ctypes.POINTER(DemodRxCfg), _SZ,
+                                          ctypes.POINTER(DemodRxSizes)]),
+        "demod_rx_advance_async": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _P, _P, _P,
+                                                  _P, _P]),
+        "demod_rx_collect_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), _SZ]),
+        "demod_rx_collect_async": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _SZ, _SZ,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
+                                                  _SZ, _P]),
+        "demod_rx_create": (_P, [ctypes.POINTER(DemodCfg), ctypes.POINTER(DemodRxCfg), _SZ,
+                                 ctypes.POINTER(ctypes.c_int)]),
+        "demod_rx_destroy": (None, [_P]),
+        "demod_rx_reset": (ctypes.c_int, [_P, _SZ]),
+        "demod_rx_state": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(DemodRxStreamState)]),
+        "demod_rx_push": (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_P),
+                                         ctypes.POINTER(DemodRxSummary)]),
         "demod_synth_fsk": (ctypes.c_int, [ctypes.POINTER(DemodCfg), ctypes.c_uint64,
                                            ctypes.c_uint64, _SZ, ctypes.c_int, ctypes.c_int,
                                            _P, _P, _P]),
@@ -562,6 +619,49 @@ def frames_decode_workspace_size(cfg: DemodCfg, n_groups: int, max_frames: int, 
                                                                 int(max_frames), int(frame_symbols)))
     if size == 0:
         raise DemodError(DEMOD_BAD_ARG, "demod_frames_decode_workspace_size")
+    return size
+
+
+def make_rx_cfg(sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
+                crc: int = DEMOD_CRC16_CCITT_FALSE, fec: int = 0, max_frames: int = 8,
+                ring_windows: int = 0) -> DemodRxCfg:
+    """A demod_rx_cfg_t (include/demod.h "receiver"). Nothing is judged here:
+    rx_sizes and Receiver refuse what the library refuses."""
+    word = _sync_bytes(sync)
+    if word.size > DEMOD_MAX_SYNC:
+        raise DemodError(DEMOD_BAD_ARG, "sync longer than DEMOD_MAX_SYNC")
+    x = DemodRxCfg()
+    for i, v in enumerate(word.tolist()):
+        x.sync[i] = v
+    x.sync_len = word.size
+    for name, v in (("max_errors", max_errors), ("frame_symbols", frame_symbols), ("len_bytes", len_bytes),
+                    ("crc", crc), ("fec", fec), ("max_frames", max_frames), ("ring_windows", ring_windows)):
+        if not 0 <= int(v) < 2 ** 32:
+            raise DemodError(DEMOD_BAD_ARG, f"{name} not in 0 .. 2^32 - 1")
+        setattr(x, name, int(v))
+    return x
+
+
+def rx_sizes(cfg: DemodCfg, rxcfg: DemodRxCfg, n_streams: int) -> dict:
+    """demod_rx_sizes: max_len, the row width, the ring bytes and every
+    workspace size of a push for n_streams streams (no GPU). Raises
+    DemodError(DEMOD_BAD_ARG) for what the library refuses."""
+    if n_streams < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_rx_sizes")
+    out = DemodRxSizes()
+    rc = load_library().demod_rx_sizes(ctypes.byref(cfg), ctypes.byref(rxcfg), int(n_streams), ctypes.byref(out))
+    if rc != DEMOD_OK:
+        raise DemodError(rc, "demod_rx_sizes")
+    return {f: int(getattr(out, f)) for f, _ in DemodRxSizes._fields_}
+
+
+def rx_collect_workspace_size(cfg: DemodCfg, n_streams: int) -> int:
+    """demod_rx_collect_workspace_size (no GPU). Raises DemodError(DEMOD_BAD_ARG)
+    where it is 0."""
+    size = int(load_library().demod_rx_collect_workspace_size(ctypes.byref(cfg), int(n_streams))) \
+        if n_streams >= 0 else 0
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_rx_collect_workspace_size")
     return size
 
 
@@ -1214,6 +1314,80 @@ class Demodulator:
         if rc < 0:
             raise DemodError(rc, "demod_frames_check_coded_async")
 
+    def rx_advance_async(self, d_state, d_ring_sym_in, d_ring_mag_in, d_new_sym, d_new_mag,
+                         n_new_windows: int, d_new_first, d_new_count, n_streams: int, ring_windows: int,
+                         d_ring_sym_out, d_ring_mag_out, d_first, d_count, stream: int = 0) -> None:
+        """demod_rx_advance_async (include/demod.h "receiver", step 1): every
+        stream's kept windows and its new ones from ring "in" to ring "out".
+        d_state (uint8, n_streams * sizeof(DemodRxStreamState) bytes), the rings
+        (uint8 n_streams * ring_windows; float32 that times k), the new batch
+        (uint8 n_new_windows, float32 that times k), d_new_first and d_first
+        (int64 tensors holding the uint64 tables) and d_new_count and d_count
+        (int32 holding uint32) are device tensors, checked like the batch
+        calls' (dtype, contiguity, device, size)."""
+        S, C, W = int(n_streams), int(ring_windows), int(n_new_windows)
+        if S < 1 or S > DEMOD_MAX_SEGMENTS or C < 1 or S * C >= 2 ** 31 or W < 0 or W >= 2 ** 31:
+            raise DemodError(DEMOD_BAD_ARG, "n_streams not in 1 .. DEMOD_MAX_SEGMENTS, ring_windows < 1, "
+                                            "n_streams * ring_windows >= 2^31 or n_new_windows not in "
+                                            "0 .. 2^31 - 1")
+        dev = int(self.cfg.device)
+        _check_dev(d_state, "d_state", "uint8", S * ctypes.sizeof(DemodRxStreamState), dev)
+        _check_dev(d_ring_sym_in, "d_ring_sym_in", "uint8", S * C, dev)
+        _check_dev(d_ring_mag_in, "d_ring_mag_in", "float32", S * C * self.k, dev)
+        _check_dev(d_new_sym, "d_new_sym", "uint8", max(W, 1), dev)
+        _check_dev(d_new_mag, "d_new_mag", "float32", max(W, 1) * self.k, dev)
+        _check_dev(d_new_first, "d_new_first", "int64", S, dev)
+        _check_dev(d_new_count, "d_new_count", "int32", S, dev)
+        _check_dev(d_ring_sym_out, "d_ring_sym_out", "uint8", S * C, dev)
+        _check_dev(d_ring_mag_out, "d_ring_mag_out", "float32", S * C * self.k, dev)
+        _check_dev(d_first, "d_first", "int64", S, dev)
+        _check_dev(d_count, "d_count", "int32", S, dev)
+        rc = self._lib.demod_rx_advance_async(
+            self._h, _ptr(d_state), _ptr(d_ring_sym_in), _ptr(d_ring_mag_in), _ptr(d_new_sym), _ptr(d_new_mag),
+            W, _ptr(d_new_first), _ptr(d_new_count), S, C, _ptr(d_ring_sym_out), _ptr(d_ring_mag_out),
+            _ptr(d_first), _ptr(d_count), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_rx_advance_async")
+
+    def rx_collect_async(self, d_state, d_hits, d_results, d_check, d_kept, d_body, d_check_summary,
+                         n_streams: int, max_frames: int, sync_len: int, frame_symbols: int, len_bytes: int,
+                         crc: int, fec: int, d_frames, d_bodies, d_summary, d_work, stream: int = 0) -> None:
+        """demod_rx_collect_async (include/demod.h "receiver", steps 3 and 4)
+        over the outputs of frames_segments_async and frames_check_async (fec
+        0) or frames_check_coded_async. d_frames (uint8, n_streams * max_frames
+        * sizeof(DemodRxFrame) bytes), d_bodies (uint8, n_streams * max_frames
+        * max_len bytes), d_summary (uint8, sizeof(DemodRxSummary) bytes) and
+        d_state are written; d_work (uint8, at least rx_collect_workspace_size
+        bytes) may hold anything. Device tensors, checked like the batch
+        calls'."""
+        S, cap, L, N = int(n_streams), int(max_frames), int(sync_len), int(frame_symbols)
+        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31:
+            raise DemodError(DEMOD_BAD_ARG, "n_streams not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
+                                            "frame_symbols < 0 or n_streams * max_frames >= 2^31")
+        if fec not in (0, DEMOD_FEC_CONV_K7):
+            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        max_len = self._coded_shape(N, len_bytes, crc)[2] if fec else self._checked_shape(N, len_bytes, crc)[1]
+        dev = int(self.cfg.device)
+        rows = S * cap
+        _check_dev(d_state, "d_state", "uint8", S * ctypes.sizeof(DemodRxStreamState), dev)
+        _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_check, "d_check", "uint8", rows * ctypes.sizeof(DemodFrameCheck), dev)
+        _check_dev(d_kept, "d_kept", "int32", rows, dev)
+        _check_dev(d_body, "d_body", "uint8", rows * max_len, dev)
+        _check_dev(d_check_summary, "d_check_summary", "uint8", S * ctypes.sizeof(DemodFramesCheckResult), dev)
+        _check_dev(d_frames, "d_frames", "uint8", rows * ctypes.sizeof(DemodRxFrame), dev)
+        _check_dev(d_bodies, "d_bodies", "uint8", rows * max_len, dev)
+        _check_dev(d_summary, "d_summary", "uint8", ctypes.sizeof(DemodRxSummary), dev)
+        _check_dev(d_work, "d_work", "uint8", rx_collect_workspace_size(self.cfg, S), dev)
+        rc = self._lib.demod_rx_collect_async(
+            self._h, _ptr(d_state), _ptr(d_hits), _ptr(d_results), _ptr(d_check), _ptr(d_kept),
+            _ptr(d_body) if d_body is not None else None, _ptr(d_check_summary), S, cap, L, N, int(len_bytes),
+            int(crc), int(fec), _ptr(d_frames), _ptr(d_bodies) if d_bodies is not None else None,
+            _ptr(d_summary), _ptr(d_work), int(d_work.numel()), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_rx_collect_async")
+
     def frames_checked(self, pcm, sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
                        crc: int = DEMOD_CRC16_CCITT_FALSE, max_frames: Optional[int] = None,
                        n_windows: Optional[int] = None, body: bool = True):
@@ -1288,6 +1462,37 @@ class Demodulator:
         return hits[:rc], lengths[:rc], bodies, frames_result_dict(res), summary
 
 
+def _packet_tables(packets, S: int, ch: int):
+    """One packet per stream -> (the arrays kept alive, ptrs uintp [S], frames
+    uintp [S]), as demod_streams_push and demod_rx_push take them."""
+    if isinstance(packets, np.ndarray) and packets.ndim == 2:
+        if packets.shape[0] != S:
+            raise DemodError(DEMOD_BAD_ARG, "one packet row per stream")
+        rows_ok = (packets.dtype == np.int16 and packets.strides[0] >= 0
+                   and (packets.shape[1] <= 1 or packets.strides[1] == 2))
+        # rows need only be contiguous each (a column slice of a longer
+        # recording is not copied)
+        keep = packets if rows_ok else np.ascontiguousarray(packets, dtype=np.int16)
+        if keep.shape[1] % ch:
+            raise DemodError(DEMOD_BAD_ARG, "pcm length not a multiple of channels")
+        frames = np.full(S, keep.shape[1] // ch, dtype=np.uintp)
+        ptrs = np.zeros(S, dtype=np.uintp)
+        if keep.shape[1]:
+            ptrs += np.uintp(keep.ctypes.data)
+            ptrs += np.arange(S, dtype=np.uintp) * np.uintp(keep.strides[0])
+    else:
+        if len(packets) != S:
+            raise DemodError(DEMOD_BAD_ARG, "one packet (or None) per stream")
+        keep = [np.ascontiguousarray(p, dtype=np.int16) if p is not None else None for p in packets]
+        frames = np.array([0 if a is None else a.size // ch for a in keep], dtype=np.uintp)
+        for a in keep:
+            if a is not None and a.size % ch:
+                raise DemodError(DEMOD_BAD_ARG, "pcm length not a multiple of channels")
+        ptrs = np.array([0 if a is None or a.size == 0 else a.ctypes.data for a in keep],
+                        dtype=np.uintp)
+    return keep, ptrs, frames
+
+
 class Streams:
     """demod_streams_t: n_streams independent streams behind one detector,
     one batch per push (include/demod.h, "many streams, one launch")."""
@@ -1339,33 +1544,8 @@ class Streams:
         or one 2-D array whose rows are the streams' packets (equal lengths;
         its row addresses are computed, not read array by array).
         Returns the per-stream symbol arrays (and magnitude arrays)."""
-        ch = int(self.cfg.channels)
         S = self.n_streams
-        if isinstance(packets, np.ndarray) and packets.ndim == 2:
-            if packets.shape[0] != S:
-                raise DemodError(DEMOD_BAD_ARG, "one packet row per stream")
-            rows_ok = (packets.dtype == np.int16 and packets.strides[0] >= 0
-                       and (packets.shape[1] <= 1 or packets.strides[1] == 2))
-            # rows need only be contiguous each (a column slice of a longer
-            # recording is not copied)
-            keep = packets if rows_ok else np.ascontiguousarray(packets, dtype=np.int16)
-            if keep.shape[1] % ch:
-                raise DemodError(DEMOD_BAD_ARG, "pcm length not a multiple of channels")
-            frames = np.full(S, keep.shape[1] // ch, dtype=np.uintp)
-            ptrs = np.zeros(S, dtype=np.uintp)
-            if keep.shape[1]:
-                ptrs += np.uintp(keep.ctypes.data)
-                ptrs += np.arange(S, dtype=np.uintp) * np.uintp(keep.strides[0])
-        else:
-            if len(packets) != S:
-                raise DemodError(DEMOD_BAD_ARG, "one packet (or None) per stream")
-            keep = [np.ascontiguousarray(p, dtype=np.int16) if p is not None else None for p in packets]
-            frames = np.array([0 if a is None else a.size // ch for a in keep], dtype=np.uintp)
-            for a in keep:
-                if a is not None and a.size % ch:
-                    raise DemodError(DEMOD_BAD_ARG, "pcm length not a multiple of channels")
-            ptrs = np.array([0 if a is None or a.size == 0 else a.ctypes.data for a in keep],
-                            dtype=np.uintp)
+        keep, ptrs, frames = _packet_tables(packets, S, int(self.cfg.channels))
         if cap is None:
             cap = int(self._lib.demod_streams_max_symbols(self._h, frames.ctypes.data))
         sym = np.empty(max(cap, 1), dtype=np.uint8)
@@ -1381,6 +1561,76 @@ class Streams:
         if not mags:
             return out_s
         return out_s, [mag[e[i]:e[i + 1]] for i in range(S)]
+
+
+class Receiver:
+    """demod_rx_t: n_streams live streams in, their checked (or decoded and
+    checked) frames out, the carry between packets kept on the device
+    (include/demod.h "receiver")."""
+
+    def __init__(self, n_streams: int, rxcfg: DemodRxCfg, cfg: Optional[DemodCfg] = None, **kw):
+        self._lib = load_library()
+        self.cfg = cfg if cfg is not None else make_cfg(**kw)
+        self.rxcfg = rxcfg
+        self.n_streams = int(n_streams)
+        self.sizes = rx_sizes(self.cfg, rxcfg, self.n_streams)
+        err = ctypes.c_int(0)
+        h = self._lib.demod_rx_create(ctypes.byref(self.cfg), ctypes.byref(rxcfg), self.n_streams,
+                                      ctypes.byref(err))
+        if not h:
+            raise DemodError(err.value, "demod_rx_create")
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.demod_rx_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream: int) -> None:
+        rc = self._lib.demod_rx_reset(self._h, int(stream))
+        if rc < 0:
+            raise DemodError(rc, "demod_rx_reset")
+
+    def state(self, stream: int) -> dict:
+        """The stream's demod_rx_stream_state_t after the last push."""
+        if stream < 0:
+            raise DemodError(DEMOD_BAD_ARG, "demod_rx_state")
+        st = DemodRxStreamState()
+        rc = self._lib.demod_rx_state(self._h, int(stream), ctypes.byref(st))
+        if rc < 0:
+            raise DemodError(rc, "demod_rx_state")
+        return {f: int(getattr(st, f)) for f, _ in DemodRxStreamState._fields_}
+
+    def push(self, packets):
+        """packets as Streams.push takes them. Returns (frames: an
+        RX_FRAME_DTYPE array [n_frames], copied out of the handle's memory,
+        bodies: a list of n_frames bytes objects, the summary dict)."""
+        keep, ptrs, nfr = _packet_tables(packets, self.n_streams, int(self.cfg.channels))
+        frames, bodies, summ = _P(), _P(), DemodRxSummary()
+        rc = self._lib.demod_rx_push(self._h, ptrs.ctypes.data, nfr.ctypes.data, ctypes.byref(frames),
+                                     ctypes.byref(bodies), ctypes.byref(summ))
+        del keep
+        if rc < 0:
+            raise DemodError(rc, "demod_rx_push")
+        summary = {f: int(getattr(summ, f)) for f, _ in DemodRxSummary._fields_}
+        rec = np.zeros(rc, RX_FRAME_DTYPE)
+        if rc:
+            ctypes.memmove(rec.ctypes.data, frames.value, rc * RX_FRAME_DTYPE.itemsize)
+        raw = ctypes.string_at(bodies.value, summary["n_bytes"]) if summary["n_bytes"] else b""
+        out = [raw[int(r["body"]):int(r["body"]) + int(r["length"])] for r in rec]
+        return rec, out, summary
 
 
 # demod_decode_fn: opus_decode's signature (opus.h:462)

@@ -120,6 +120,21 @@ __device__ __forceinline__ uint8_t frame_packed_byte(const uint8_t *src, unsigne
     return (uint8_t)byte;
 }
 
+// the symbols a checked frame of `length` data bytes occupies behind its word
+// (include/demod.h "checked frames": S, its h + len + c bytes; with fec_depth
+// "coded frames": Sc, its 2 T(len) coded bits). The one copy of the span that
+// `covered` (frames_check.hip) and the receiver's `hold` (frames_carry.hip) use.
+__device__ __forceinline__ unsigned checked_frame_span(unsigned length, unsigned len_bytes, unsigned crc_bytes,
+                                                       unsigned bits, unsigned fec_depth)
+{
+    unsigned span = (len_bytes + crc_bytes + length) * 8;
+    if (fec_depth) {
+        const unsigned least = 8u * len_bytes + fec_depth;
+        span = 2u * (span + 6u > least ? span + 6u : least);
+    }
+    return (span + bits - 1) / bits;
+}
+
 template <typename OnHit, typename TileDone>
 __device__ __forceinline__ void acquire_scan_body(const AcqScanArgs &p, const uint8_t *sync,
                                                   AcqScanLds &s, OnHit &&on_hit, TileDone &&tile_done)

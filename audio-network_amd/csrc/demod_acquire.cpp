@@ -1,6 +1,7 @@
 // demod_acquire.cpp — the C ABI of everything downstream of the detector
 // (include/demod.h): acquisition, the frame scan, their segmented forms, the
-// frame check and the coded decode. Each stage has a workspace-size function,
+// frame check, the coded decode and the receiver's two stages (the receiver
+// handle itself is demod_rx.cpp). Each stage has a workspace-size function,
 // an *_async call on device memory and the caller's stream, and a synchronous
 // wrapper that stages host or device samples, runs the detector (enqueue_batch,
 // demod_api.cpp) and the stage on the handle's stream and copies the results.
@@ -507,24 +508,23 @@ int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, con
 
 // Fills what the shape decides (row width, max_len, the CRC's constants, R,
 // bits, L); false for what demod_frames_check_async refuses about it.
-static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_frames, size_t sync_len,
+static bool frames_check_shape(const demod_cfg_t &cfg, size_t n_groups, size_t max_frames, size_t sync_len,
                                size_t frame_symbols, int len_bytes, int crc, FramesCheckParams &p,
                                int fec = 0)
 {
-    if (!st) return false;
-    const uint32_t R = acquire_phases(st->cfg);
+    const uint32_t R = acquire_phases(cfg);
     if (R == 0 || n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames == 0) return false;
     if (max_frames > 0x7FFFFFFF || (unsigned long long)n_groups * max_frames > 0x7FFFFFFFull) return false;
     if (sync_len == 0 || sync_len > DEMOD_MAX_SYNC || (len_bytes != 1 && len_bytes != 2)) return false;
     if (crc != DEMOD_CRC16_CCITT_FALSE && crc != DEMOD_CRC32_MPEG2) return false;
-    const size_t bits = (size_t)demod_bits_per_symbol(st->cfg.k);
+    const size_t bits = (size_t)demod_bits_per_symbol(cfg.k);
     const size_t c = crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4, h = (size_t)len_bytes;
     if (frame_symbols > 0x7FFFFFFF) return false;
     size_t B = packed_row_bytes(frame_symbols, bits);
     if (fec) {
         // coded rows: St = floor(N bits / 2) steps decode to Bd = (St - 6) / 8 bytes
         const size_t St = frame_symbols * bits / 2;
-        if (fec != DEMOD_FEC_CONV_K7 || st->cfg.k != (1u << bits)) return false;
+        if (fec != DEMOD_FEC_CONV_K7 || cfg.k != (1u << bits)) return false;
         if (St < 8 * h + DEMOD_FEC_DEPTH) return false;
         B = (St - 6) / 8;
         p.fec_depth = DEMOD_FEC_DEPTH;
@@ -553,6 +553,13 @@ static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_fr
     p.phases = (int)R;
     p.sync_len = (int)sync_len;
     return true;
+}
+
+static bool frames_check_shape(const demod_t *st, size_t n_groups, size_t max_frames, size_t sync_len,
+                               size_t frame_symbols, int len_bytes, int crc, FramesCheckParams &p,
+                               int fec = 0)
+{
+    return st && frames_check_shape(st->cfg, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, p, fec);
 }
 
 // fec 0: the scan's packed rows; else decoded rows (the coded entry has refused fec 0)
@@ -758,6 +765,143 @@ int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const 
     if (fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
     return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
                               fec, hits, lengths, body, max_frames, result, summary);
+}
+
+// ---- receiver stages (frames_carry.hip) ----------------------------------------
+
+int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n_streams,
+                   demod_rx_sizes_t *out)
+{
+    if (!rxcfg || !out || validate_cfg(cfg) != DEMOD_OK) return DEMOD_BAD_ARG;
+    const demod_rx_cfg_t &x = *rxcfg;
+    const size_t S = n_streams, L = x.sync_len, N = x.frame_symbols, C = x.ring_windows;
+    // the scan's refusals (acquire_check and frames_check, on the configuration)
+    const uint32_t R = acquire_phases(*cfg);
+    if (R == 0 || L == 0 || L > DEMOD_MAX_SYNC || x.max_errors >= L) return DEMOD_BAD_ARG;
+    for (size_t i = 0; i < L; ++i)
+        if (x.sync[i] >= cfg->k) return DEMOD_BAD_ARG;
+    if (N > 0x7FFFFFFF || (L + N) * R > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    if (x.fec != 0 && x.fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    // the check's (or the decode's and the coded check's): S, max_frames, the row shape
+    FramesCheckParams p;
+    std::memset(&p, 0, sizeof(p));
+    if (!frames_check_shape(*cfg, S, x.max_frames, L, N, (int)x.len_bytes, (int)x.crc, p, (int)x.fec))
+        return DEMOD_BAD_ARG;
+    if (C < 2 * (L + N) * R || C >= ((size_t)1 << 31) / S || S * C > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const size_t rows = S * x.max_frames;
+    out->max_len = p.max_len;
+    out->row_bytes = p.row_bytes;
+    out->ring_sym_bytes = S * C;
+    out->ring_mag_bytes = S * C * cfg->k * sizeof(float);
+    out->scan_work_bytes = demod_frames_segments_workspace_size(cfg, S, S * C);
+    out->decode_work_bytes = x.fec ? demod_frames_decode_workspace_size(cfg, S, x.max_frames, N) : 0;
+    out->collect_work_bytes = demod_rx_collect_workspace_size(cfg, S);
+    out->frames_bytes = rows * sizeof(demod_rx_frame_t);
+    out->bodies_bytes = rows * p.max_len;
+    if (out->scan_work_bytes == 0 || (x.fec && out->decode_work_bytes == 0)) return DEMOD_BAD_ARG;
+    return DEMOD_OK;
+}
+
+int demod_rx_advance_async(demod_t *st, demod_rx_stream_state_t *d_state, const uint8_t *d_ring_sym_in,
+                           const float *d_ring_mag_in, const uint8_t *d_new_sym, const float *d_new_mag,
+                           size_t n_new_windows, const uint64_t *d_new_first,
+                           const uint32_t *d_new_count, size_t n_streams, size_t ring_windows,
+                           uint8_t *d_ring_sym_out, float *d_ring_mag_out, uint64_t *d_first,
+                           uint32_t *d_count, void *stream)
+{
+    if (!st || !d_state || !d_ring_sym_in || !d_ring_mag_in || !d_new_sym || !d_new_mag || !d_new_first ||
+        !d_new_count || !d_ring_sym_out || !d_ring_mag_out || !d_first || !d_count)
+        return DEMOD_BAD_ARG;
+    if (d_ring_sym_in == d_ring_sym_out || d_ring_mag_in == d_ring_mag_out) return DEMOD_BAD_ARG;
+    if (n_streams == 0 || n_streams > DEMOD_MAX_SEGMENTS || ring_windows == 0 || ring_windows > 0x7FFFFFFF ||
+        n_streams * ring_windows > 0x7FFFFFFF || n_new_windows > 0x7FFFFFFF)
+        return DEMOD_BAD_ARG;
+    if (((uintptr_t)d_state & 7) != 0 || ((uintptr_t)d_new_first & 7) != 0 || ((uintptr_t)d_first & 7) != 0 ||
+        ((uintptr_t)d_new_count & 3) != 0 || ((uintptr_t)d_count & 3) != 0 ||
+        ((uintptr_t)d_ring_mag_in & 3) != 0 || ((uintptr_t)d_ring_mag_out & 3) != 0 ||
+        ((uintptr_t)d_new_mag & 3) != 0)
+        return DEMOD_BAD_ARG;
+    RxAdvanceParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.state = d_state;
+    p.ring_sym_in = d_ring_sym_in;
+    p.ring_mag_in = d_ring_mag_in;
+    p.new_sym = d_new_sym;
+    p.new_mag = d_new_mag;
+    p.new_first = reinterpret_cast<const unsigned long long *>(d_new_first);
+    p.new_count = d_new_count;
+    p.n_new = n_new_windows;
+    p.n_streams = (unsigned)n_streams;
+    p.ring = (unsigned)ring_windows;
+    p.k = (int)st->cfg.k;
+    p.ring_sym_out = d_ring_sym_out;
+    p.ring_mag_out = d_ring_mag_out;
+    p.seg_first = reinterpret_cast<unsigned long long *>(d_first);
+    p.seg_count = d_count;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_rx_advance(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+size_t demod_rx_collect_workspace_size(const demod_cfg_t *cfg, size_t n_streams)
+{
+    if (validate_cfg(cfg) != DEMOD_OK || n_streams == 0 || n_streams > DEMOD_MAX_SEGMENTS) return 0;
+    return rx_collect_work_bytes(n_streams);
+}
+
+int demod_rx_collect_async(demod_t *st, demod_rx_stream_state_t *d_state, const demod_frame_hit_t *d_hits,
+                           const demod_frames_result_t *d_results, const demod_frame_check_t *d_check,
+                           const uint32_t *d_kept, const uint8_t *d_body,
+                           const demod_frames_check_result_t *d_check_summary, size_t n_streams,
+                           size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                           int crc, int fec, demod_rx_frame_t *d_frames, uint8_t *d_bodies,
+                           demod_rx_summary_t *d_summary, void *d_work, size_t work_bytes, void *stream)
+{
+    if (!st || !d_state || !d_hits || !d_results || !d_check || !d_kept || !d_check_summary || !d_frames ||
+        !d_summary || !d_work)
+        return DEMOD_BAD_ARG;
+    if (((uintptr_t)d_state & 7) != 0 || ((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 ||
+        ((uintptr_t)d_check_summary & 7) != 0 || ((uintptr_t)d_frames & 7) != 0 ||
+        ((uintptr_t)d_summary & 7) != 0 || ((uintptr_t)d_work & 7) != 0 || ((uintptr_t)d_check & 3) != 0 ||
+        ((uintptr_t)d_kept & 3) != 0)
+        return DEMOD_BAD_ARG;
+    if (fec != 0 && fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    FramesCheckParams q;   // the shape the check saw: the same refusals, the same span
+    std::memset(&q, 0, sizeof(q));
+    if (!frames_check_shape(st, n_streams, max_frames, sync_len, frame_symbols, len_bytes, crc, q, fec))
+        return DEMOD_BAD_ARG;
+    if (q.max_len && (!d_body || !d_bodies)) return DEMOD_BAD_ARG;
+    const size_t need = demod_rx_collect_workspace_size(&st->cfg, n_streams);
+    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
+    RxCollectParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.state = d_state;
+    p.hits = d_hits;
+    p.res = d_results;
+    p.check = d_check;
+    p.kept = d_kept;
+    p.body = d_body;
+    p.chk_sum = d_check_summary;
+    p.n_streams = q.n_groups;
+    p.max_frames = q.max_frames;
+    p.max_len = q.max_len;
+    p.len_bytes = q.len_bytes;
+    p.crc_bytes = q.crc_bytes;
+    p.bits = q.bits;
+    p.phases = q.phases;
+    p.sync_len = q.sync_len;
+    p.fec_depth = q.fec_depth;
+    p.frames = d_frames;
+    p.bodies = d_bodies;
+    p.summary = d_summary;
+    p.w_hold = static_cast<unsigned long long *>(d_work);
+    p.w_bytes = p.w_hold + n_streams;
+    p.w_cnt = reinterpret_cast<unsigned *>(p.w_bytes + n_streams);
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_rx_collect(p, (hipStream_t)stream));
+    return DEMOD_OK;
 }
 
 }  // extern "C"

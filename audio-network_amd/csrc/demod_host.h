@@ -1,7 +1,7 @@
-// demod_host.h — what the host layer's three files share (private):
-// demod_api.cpp (handle, batch and streaming entry points), demod_acquire.cpp
-// (acquisition and frame entry points on the detector's outputs) and
-// demod_streams.cpp (many streams behind one handle).
+// demod_host.h — what the host layer's files share (private): demod_api.cpp
+// (handle, batch and streaming entry points), demod_acquire.cpp (acquisition
+// and frame entry points on the detector's outputs), demod_streams.cpp (many
+// streams behind one handle) and demod_rx.cpp (the receiver handle).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -214,5 +214,27 @@ int ensure_host(demod_t *st, size_t samples, size_t windows);
 int ensure_dev(demod_t *st, size_t samples, size_t windows, bool mags);
 // Device or managed memory (a host pointer, or one the runtime does not know: false).
 bool is_device_ptr(const void *p);
+
+// demod_streams.cpp: the staging half of a push, shared by demod_streams_push
+// and demod_rx_push (demod_rx.cpp). After streams_check (plan.h) has admitted
+// the packets and laid the batch out: streams_stage, the batch, then
+// streams_commit, or streams_unstage when the batch failed.
+struct StreamsStage {
+    size_t W = 0;                 // the windows the streams emit
+    size_t Wb = 0;                // the batch's windows, the straddling ones included
+    size_t samples = 0;           // staged samples, (Wb - 1) hop + n; 0 without a window
+    int16_t *base = nullptr;      // the staging buffer (host view); stream s's run at first[s] hop
+    const size_t *first = nullptr;  // [S] batch window of each stream's first
+};
+int streams_stage(demod_streams_t *ms, const int16_t *const *pcm, const size_t *n_frames, size_t W,
+                  size_t Wb, size_t tail, StreamsStage *out);
+void streams_unstage(demod_streams_t *ms, const size_t *n_frames, const StreamsStage &sg);
+void streams_commit(demod_streams_t *ms, const int16_t *const *pcm, const size_t *n_frames,
+                    uint32_t *counts);
+demod_t *streams_detector(demod_streams_t *ms);
+// The handle's layout table [S]: what streams_check fills and streams_stage reads.
+size_t *streams_first(demod_streams_t *ms);
+// Stage in pinned memory whatever FSKD_STREAMS_MAPPED says (the receiver copies its runs in).
+void streams_copy_staging(demod_streams_t *ms);
 
 }  // namespace fskd

@@ -12,6 +12,9 @@ struct demod_frame_hit;
 struct demod_frame_check;
 struct demod_frames_check_result;
 struct demod_frame_decode;
+struct demod_rx_stream_state;
+struct demod_rx_frame;
+struct demod_rx_summary;
 
 namespace fskd {
 
@@ -413,5 +416,51 @@ struct FramesFecParams {
     unsigned long long *work;             // [waves of the launch][steps]
 };
 hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s);
+
+// frames_carry.hip: the receiver's device-resident carry (include/demod.h
+// "receiver"). advance moves each stream's kept windows and its new ones from
+// ring "in" to ring "out" and rewrites the scan's tables; collect turns the
+// check's per-stream outputs into one dense list of records and bytes.
+struct RxAdvanceParams {
+    ::demod_rx_stream_state *state;       // [n_streams]
+    const uint8_t *ring_sym_in;           // [n_streams][ring]
+    const float *ring_mag_in;             // [n_streams][ring][k]
+    const uint8_t *new_sym;               // [n_new]
+    const float *new_mag;                 // [n_new][k]
+    const unsigned long long *new_first;  // [n_streams], device, as the caller wrote it
+    const unsigned *new_count;            // [n_streams]
+    unsigned long long n_new;             // < 2^31
+    unsigned n_streams;
+    unsigned ring;                        // C; n_streams * ring < 2^31
+    int k;
+    uint8_t *ring_sym_out;
+    float *ring_mag_out;
+    unsigned long long *seg_first;        // [n_streams] s C
+    unsigned *seg_count;                  // [n_streams] fill
+};
+hipError_t launch_rx_advance(const RxAdvanceParams &p, hipStream_t s);
+
+struct RxCollectParams {
+    ::demod_rx_stream_state *state;       // [n_streams]
+    const ::demod_frame_hit *hits;        // [n_streams][max_frames]
+    const ::demod_frames_result *res;     // [n_streams]
+    const ::demod_frame_check *check;     // [n_streams][max_frames]
+    const uint32_t *kept;                 // [n_streams][max_frames]
+    const uint8_t *body;                  // [n_streams][max_frames][max_len]
+    const ::demod_frames_check_result *chk_sum;  // [n_streams]
+    unsigned n_streams;
+    unsigned max_frames;                  // n_streams * max_frames < 2^31
+    unsigned max_len;
+    int len_bytes, crc_bytes, bits, phases, sync_len, fec_depth;   // as FramesCheckParams
+    ::demod_rx_frame *frames;             // [n_streams max_frames]
+    uint8_t *bodies;                      // [n_streams max_frames max_len]
+    ::demod_rx_summary *summary;
+    // d_work
+    unsigned long long *w_hold;           // [n_streams] hold before this push
+    unsigned long long *w_bytes;          // [n_streams] emitted bytes, then their exclusive prefix
+    unsigned *w_cnt;                      // [n_streams] emitted rows, then their exclusive prefix
+};
+constexpr size_t rx_collect_work_bytes(size_t S) { return 16 * S + (4 * S + 7) / 8 * 8; }
+hipError_t launch_rx_collect(const RxCollectParams &p, hipStream_t s);
 
 }  // namespace fskd

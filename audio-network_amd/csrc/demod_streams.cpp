@@ -176,6 +176,102 @@ long long fskd::streams_check(const demod_streams_t *ms, const int16_t *const *p
 
 int fskd::streams_device(const demod_streams_t *ms) { return ms ? ms->st->device : -1; }
 
+demod_t *fskd::streams_detector(demod_streams_t *ms) { return ms->st; }
+
+size_t *fskd::streams_first(demod_streams_t *ms) { return ms->first.data(); }
+
+void fskd::streams_copy_staging(demod_streams_t *ms) { ms->mapped = false; }
+
+// stream s's fresh frames (past its lead-in) and where they start
+static size_t fresh_frames(const demod_streams_t *ms, const size_t *n_frames, size_t s)
+{
+    return n_frames[s] - std::min(ms->skip[s], n_frames[s]);
+}
+
+static const int16_t *fresh_at(const demod_streams_t *ms, const int16_t *const *pcm, const size_t *n_frames,
+                               size_t s, size_t f)
+{
+    return f ? pcm[s] + (n_frames[s] - f) * ms->cfg.channels : nullptr;
+}
+
+// The staging half of a push that streams_check admitted (W windows, Wb with
+// the straddling ones, the layout in ms->first): every stream's carry and fresh
+// frames to its run in the pinned staging buffer the host path copies from (or
+// the mapped one), with room for `tail` more samples behind the runs, and the
+// new carries formed. Until streams_commit the push can still be undone
+// (streams_unstage). Returns DEMOD_OK or a code with nothing consumed.
+int fskd::streams_stage(demod_streams_t *ms, const int16_t *const *pcm, const size_t *n_frames, size_t W,
+                        size_t Wb, size_t tail, StreamsStage *out)
+{
+    const demod_cfg_t &c = ms->cfg;
+    const size_t S = ms->carry.size(), n = c.n, hop = c.hop;
+    demod_t *st = ms->st;
+    // every carry holds < n samples after a push: n each, allocated once, so
+    // the carry updates below never allocate
+    for (Carry &cs : ms->carry) {
+        if (!cs.p) cs.p.reset(new (std::nothrow) int16_t[n]);
+        if (!cs.p) return DEMOD_ALLOC_FAIL;
+        cs.have = cs.len;
+    }
+    out->W = W;
+    out->Wb = Wb;
+    out->samples = 0;
+    out->base = nullptr;
+    out->first = ms->first.data();
+    if (!W && !tail) return DEMOD_OK;
+    // (Wb, with the straddling windows, was bounded by streams_check)
+    const int rc = ms->mapped ? ensure_mapped(ms, Wb * hop + n + tail, Wb)
+                              : ensure_host(st, std::max(Wb * hop + n + tail, kSmallHostSamples),
+                                            kSmallHostSamples / 8);
+    if (rc != DEMOD_OK) return rc;
+    out->base = ms->mapped ? ms->zm_in.p : st->h_in.p;
+    if (!W) return DEMOD_OK;
+    out->samples = (Wb - 1) * hop + n;  // the last run ends exactly here or earlier
+    int16_t *const stage_base = out->base;
+    // threads: ~1 per 2 MiB of staged samples, at most kPushThreads (1 per
+    // MiB measured no better: 0.47 / 0.75 / 0.54-0.61 ms against 0.49-0.53 /
+    // 0.67 / 0.55-0.59 for mono / stereo / hop 256 at 1024 streams); the
+    // threads persist in the handle's pool between pushes
+    const size_t T = std::min(std::min<size_t>(kPushThreads, Wb * hop / (1u << 20)), S);
+    ms->pool.each(T, S, [&](size_t s) {
+        const size_t f = fresh_frames(ms, n_frames, s);
+        Carry &cs = ms->carry[s];
+        cs.len = stage_stream(c, fresh_at(ms, pcm, n_frames, s, f), f, cs.p.get(), cs.have,
+                              stage_base + ms->first[s] * hop);
+    });
+    return DEMOD_OK;
+}
+
+// The batch failed, nothing consumed: the carries come back from the staged runs.
+void fskd::streams_unstage(demod_streams_t *ms, const size_t *n_frames, const StreamsStage &sg)
+{
+    if (!sg.W) return;
+    for (size_t s = 0; s < ms->carry.size(); ++s) {
+        Carry &cs = ms->carry[s];
+        cs.len = unstage_stream(ms->cfg, fresh_frames(ms, n_frames, s), cs.p.get(), cs.have,
+                                sg.base + ms->first[s] * ms->cfg.hop);
+    }
+}
+
+// The batch succeeded: counts[s] = the windows stream s emitted (batch windows
+// ms->first[s] ..), a stream without a complete window appends its frames to
+// its carry, and the lead-ins are consumed.
+void fskd::streams_commit(demod_streams_t *ms, const int16_t *const *pcm, const size_t *n_frames,
+                          uint32_t *counts)
+{
+    const demod_cfg_t &c = ms->cfg;
+    for (size_t s = 0; s < ms->carry.size(); ++s) {
+        Carry &cs = ms->carry[s];
+        const size_t f = fresh_frames(ms, n_frames, s), total = cs.have + f, w = windows_for(total, c.n, c.hop);
+        counts[s] = (uint32_t)w;
+        if (!w && f) {
+            mono_frames(c, fresh_at(ms, pcm, n_frames, s, f), f, cs.p.get() + cs.have);  // total < n
+            cs.len = total;
+        }
+        ms->skip[s] -= std::min(ms->skip[s], n_frames[s]);
+    }
+}
+
 extern "C" {
 
 demod_streams_t *demod_streams_create(const demod_cfg_t *cfg, size_t n_streams, int *error)
@@ -244,7 +340,7 @@ int demod_streams_push(demod_streams_t *ms, const int16_t *const *pcm, const siz
 {
     if (!ms || !n_frames || !counts) return DEMOD_BAD_ARG;
     const demod_cfg_t &c = ms->cfg;
-    const size_t S = ms->carry.size(), n = c.n, hop = c.hop;
+    const size_t S = ms->carry.size();
     size_t Wb = 0;
     const long long Wc = streams_check(ms, pcm, n_frames, nullptr, ms->first.data(), &Wb);
     if (Wc < 0) return (int)Wc;
@@ -254,44 +350,18 @@ int demod_streams_push(demod_streams_t *ms, const int16_t *const *pcm, const siz
     demod_t *st = ms->st;
     DeviceGuard guard(st->device);
     HIP_TRY(guard.err);
-    // every carry holds < n samples after a push: n each, allocated once, so
-    // the carry updates below never allocate
-    for (Carry &cs : ms->carry) {
-        if (!cs.p) cs.p.reset(new (std::nothrow) int16_t[n]);
-        if (!cs.p) return DEMOD_ALLOC_FAIL;
-        cs.have = cs.len;
-    }
-    // stream s's fresh frames (past its lead-in) and where they start
-    auto fresh = [&](size_t s) { return n_frames[s] - std::min(ms->skip[s], n_frames[s]); };
-    auto fresh_at = [&](size_t s, size_t f) {
-        return f ? pcm[s] + (n_frames[s] - f) * c.channels : nullptr;
-    };
     if (W) {
-        // the runs go to the pinned staging buffer the host path copies from
-        // (or the mapped one); (Wb, with the straddling windows, was bounded
-        // by streams_check)
-        const size_t samples = (Wb - 1) * hop + n;  // the last run ends exactly here or earlier
-        int rc = ms->mapped ? ensure_mapped(ms, Wb * hop + n, Wb)
-                            : ensure_host(st, std::max(Wb * hop + n, kSmallHostSamples),
-                                          kSmallHostSamples / 8);
-        if (rc != DEMOD_OK) return rc;
-        int16_t *const stage_base = ms->mapped ? ms->zm_in.p : st->h_in.p;
         try {
             ms->sym.resize(Wb);
             if (mags) ms->mag.resize(Wb * c.k);
         } catch (...) {
             return DEMOD_ALLOC_FAIL;
         }
-        // threads: ~1 per 2 MiB of staged samples, at most kPushThreads (1 per
-        // MiB measured no better: 0.47 / 0.75 / 0.54-0.61 ms against 0.49-0.53 /
-        // 0.67 / 0.55-0.59 for mono / stereo / hop 256 at 1024 streams); the
-        // threads persist in the handle's pool between pushes
-        const size_t T = std::min(std::min<size_t>(kPushThreads, Wb * hop / (1u << 20)), S);
-        ms->pool.each(T, S, [&](size_t s) {
-            const size_t f = fresh(s);
-            Carry &cs = ms->carry[s];
-            cs.len = stage_stream(c, fresh_at(s, f), f, cs.p.get(), cs.have, stage_base + ms->first[s] * hop);
-        });
+    }
+    StreamsStage sg;
+    int rc = streams_stage(ms, pcm, n_frames, W, Wb, 0, &sg);
+    if (rc != DEMOD_OK) return rc;
+    if (W) {
         if (ms->mapped) {
             // the detector reads the staged runs in place and writes the
             // results straight into mapped host memory: one launch (and the
@@ -304,35 +374,25 @@ int demod_streams_push(demod_streams_t *ms, const int16_t *const *pcm, const siz
                 if (mags) std::memcpy(ms->mag.data(), ms->zm_mag.p, Wb * c.k * sizeof(float));
             }
         } else {
-            rc = run_host(st, st->h_in.p, samples, Wb, ms->sym.data(), mags ? ms->mag.data() : nullptr);
+            rc = run_host(st, sg.base, sg.samples, Wb, ms->sym.data(), mags ? ms->mag.data() : nullptr);
         }
         if (rc < 0) {
-            // nothing consumed: the carries come back from the staged runs
-            for (size_t s = 0; s < S; ++s) {
-                Carry &cs = ms->carry[s];
-                cs.len = unstage_stream(c, fresh(s), cs.p.get(), cs.have, stage_base + ms->first[s] * hop);
-            }
+            streams_unstage(ms, n_frames, sg);
             return rc;
         }
     }
+    streams_commit(ms, pcm, n_frames, counts);
     uint8_t *so = symbols;
     float *mo = mags;
     for (size_t s = 0; s < S; ++s) {
-        Carry &cs = ms->carry[s];
-        const size_t f = fresh(s), total = cs.have + f, w = windows_for(total, n, hop);
-        counts[s] = (uint32_t)w;
-        if (w) {
-            std::memcpy(so, ms->sym.data() + ms->first[s], w);
-            so += w;
-            if (mags) {
-                std::memcpy(mo, ms->mag.data() + ms->first[s] * c.k, w * c.k * sizeof(float));
-                mo += w * c.k;
-            }
-        } else if (f) {
-            mono_frames(c, fresh_at(s, f), f, cs.p.get() + cs.have);  // total < n
-            cs.len = total;
+        const size_t w = counts[s];
+        if (!w) continue;
+        std::memcpy(so, ms->sym.data() + ms->first[s], w);
+        so += w;
+        if (mags) {
+            std::memcpy(mo, ms->mag.data() + ms->first[s] * c.k, w * c.k * sizeof(float));
+            mo += w * c.k;
         }
-        ms->skip[s] -= std::min(ms->skip[s], n_frames[s]);
     }
     return (int)W;
 }

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kAcqThreads) void frames_select_kernel(FramesCheckP
     __shared__ unsigned s_wkept[kChkWaves], s_wok[kChkWaves];
     const int t = threadIdx.x, wave = t / kChkLanes, lane = t % kChkLanes;
     const unsigned long long R = (unsigned long long)p.phases, L = (unsigned long long)p.sync_len;
-    const unsigned bits = (unsigned)p.bits, hc = (unsigned)(p.len_bytes + p.crc_bytes);
+    const unsigned bits = (unsigned)p.bits;
     for (unsigned g = blockIdx.x; g < p.n_groups; g += gridDim.x) {
         // the same for every thread of the block: the barriers below are uniform
         const unsigned nw = group_rows(p, g);
@@ -148,13 +148,9 @@ __global__ __launch_bounds__(kAcqThreads) void frames_select_kernel(FramesCheckP
             if (in && p.check[row0 + i].status == DEMOD_CHECK_OK) {
                 ok = true;
                 window = p.hits[row0 + i].window;
-                // the frame's bits on the air: its bytes, or coded 2 T(len) (include/demod.h "coded frames")
-                unsigned span = (hc + p.check[row0 + i].length) * 8;
-                if (p.fec_depth) {
-                    const unsigned least = 8u * (unsigned)p.len_bytes + (unsigned)p.fec_depth;
-                    span = 2u * (span + 6u > least ? span + 6u : least);
-                }
-                const unsigned S = (span + bits - 1) / bits;
+                // the frame's symbols on the air: its bytes, or coded 2 T(len) bits
+                const unsigned S = checked_frame_span(p.check[row0 + i].length, (unsigned)p.len_bytes,
+                                                      (unsigned)p.crc_bytes, bits, (unsigned)p.fec_depth);
                 end = window + (L + S) * R;
             }
             // inclusive maximum over the lanes up to this one, then over the waves before

@@ -1049,6 +1049,199 @@ int demod_streams_push_packets(demod_streams_t *ms, demod_decode_fn decode, void
                                const uint8_t *const *packets, const int32_t *lens, int frame_size,
                                uint8_t *symbols, float *mags, size_t cap, uint32_t *counts);
 
+/* ---- receiver: frames of live streams, carried on the device ------------- */
+/*
+ * demod_streams_push ends at raw symbols, and the frame stages above work on
+ * one finished batch: a frame that starts in one packet and ends in a later one
+ * needs a carry. The receiver keeps that carry on the device, in the detector's
+ * OUTPUT domain (1 + 4 K bytes a window instead of 2 hop bytes of samples), so
+ * the detector sees no sample twice, and returns the checked (or decoded and
+ * checked) frames of all streams as one dense list.
+ *
+ * Per stream the receiver holds a run X of detector outputs, sym[i] and
+ * P[i][K] for i < fill; window i is the stream's window base + i, counted from
+ * create or reset. With X it holds keep, hold and the counters dropped and
+ * cut_hits; all are 0 initially. C = ring_windows; R, L, N, h, c, bits, the
+ * span S and `complete` are as in the sections above. A push with `new` fresh
+ * windows for the stream does, in this order:
+ *
+ *   1 advance  keep' = min(keep, fill); Y = X[keep' ..) followed by the new
+ *              windows; base += keep'. If len(Y) > C the oldest d = len(Y) - C
+ *              windows of Y go: base += d, dropped += d. X = Y, fill = len(Y).
+ *   2 scan     X is scanned exactly as segment {first = slot, count = fill} of
+ *              "segmented frame scan" (group = stream). fec == 0: packed rows,
+ *              then "checked frames". fec == DEMOD_FEC_CONV_K7: no rows, then
+ *              the decode and the coded check of "coded frames".
+ *   3 collect  For the OK rows end_j = base + window_j + (L + S_j) R, S_j the
+ *              span the check's `covered` uses (plain or coded). A kept row i
+ *              is EMITTED when base + window_i >= hold, hold as the pushes
+ *              before left it (kept rows ascend: the rows not emitted are a
+ *              prefix). Then hold = max(hold, the largest end_j of this push,
+ *              covered rows included); keep = tail_window when the result's
+ *              tail_window >= 0, else max(0, fill - (L - 1) R): every start, on
+ *              any phase, whose word does not fit yet; cut_hits += n_hits -
+ *              n_written.
+ *   4 output   the emitted rows of stream 0, then stream 1, ..., each in
+ *              ascending window order; a row's data bytes at `body`, the
+ *              exclusive prefix of `length` in that order.
+ *
+ * With no overflow (dropped == 0), no cut (cut_hits == 0) and the same absolute
+ * phase (base + phase) mod R chosen at every push, the frames a stream emits
+ * over all pushes are exactly the kept frames of demod_frames_checked (or
+ * demod_frames_coded) on the whole recording, in the same order, whatever the
+ * packet sizes. The phase is decided per push over X alone: a stream whose
+ * timing metric is weak over a short X may pick another phase for that push and
+ * miss the frames that complete in it. That limitation is not solved here. (A
+ * frame completes only when X holds all of it, so the pushes that matter decide
+ * the phase on L + N symbols or more.)
+ *
+ * C >= 2 (L + N) R, so that a frame in flight and a full packet of the same
+ * length fit; a packet with more new windows than that overflows (the oldest
+ * windows go and `dropped` says how many).
+ */
+typedef struct demod_rx_cfg {
+    uint8_t  sync[DEMOD_MAX_SYNC];     /* the word, sync_len symbols */
+    uint32_t sync_len, max_errors;
+    uint32_t frame_symbols;            /* N */
+    uint32_t len_bytes, crc;           /* h; DEMOD_CRC16_CCITT_FALSE or DEMOD_CRC32_MPEG2 */
+    uint32_t fec;                      /* 0 or DEMOD_FEC_CONV_K7 */
+    uint32_t max_frames;               /* rows per stream and push */
+    uint32_t ring_windows;             /* C */
+} demod_rx_cfg_t;
+
+typedef struct demod_rx_frame {        /* 32 bytes */
+    uint32_t stream, length;
+    uint64_t window;                   /* base + hit window: stream-absolute */
+    uint64_t body;                     /* byte offset of its data in the dense body array:
+                                          the exclusive prefix of `length` in output order */
+    uint32_t errors, reserved;         /* the hit's errors; 0 */
+} demod_rx_frame_t;
+
+typedef struct demod_rx_stream_state { /* 40 bytes, one per stream, device and host */
+    uint64_t base, hold, dropped, cut_hits;
+    uint32_t fill, keep;
+} demod_rx_stream_state_t;
+
+typedef struct demod_rx_summary {
+    uint64_t n_frames, n_bytes;        /* emitted rows and their data bytes */
+    uint64_t n_checked, n_valid;       /* rows checked and rows OK in this push, all streams */
+} demod_rx_summary_t;
+
+typedef struct demod_rx_sizes {
+    uint64_t max_len;                  /* data bytes a frame can hold */
+    uint64_t row_bytes;                /* B (fec 0) or Bd */
+    uint64_t ring_sym_bytes;           /* one [S][C] symbol ring */
+    uint64_t ring_mag_bytes;           /* one [S][C][K] power ring */
+    uint64_t scan_work_bytes;          /* demod_frames_segments_workspace_size(cfg, S, S C) */
+    uint64_t decode_work_bytes;        /* demod_frames_decode_workspace_size, 0 with fec 0 */
+    uint64_t collect_work_bytes;       /* demod_rx_collect_workspace_size */
+    uint64_t frames_bytes;             /* d_frames: S max_frames records */
+    uint64_t bodies_bytes;             /* d_bodies: S max_frames max_len */
+} demod_rx_sizes_t;
+
+/* Validates the pair and fills *out. No device needed. DEMOD_BAD_ARG for a
+ * NULL pointer, whatever the scan, the check or the decode refuse for the same
+ * parameters (configuration, word, (L + N) R >= 2^31, row shape, K not a power
+ * of two with fec, an unknown crc, len_bytes or fec), n_streams == 0 or >
+ * DEMOD_MAX_SEGMENTS, max_frames == 0, n_streams * max_frames >= 2^31,
+ * ring_windows < 2 (L + N) R, ring_windows >= 2^31 / n_streams or n_streams *
+ * ring_windows >= 2^31. */
+int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n_streams,
+                   demod_rx_sizes_t *out);
+
+/*
+ * Step 1 for every stream, from ring "in" to ring "out": two distinct [S][C]
+ * symbol and [S][C][K] power arrays that the caller alternates between pushes,
+ * so no copy overlaps itself. Enqueued on `stream`: two launches whatever S and
+ * the counts are (copy, then state). The new windows of stream s are windows
+ * d_new_first[s] .. of (d_new_sym, d_new_mag), d_new_count[s] of them, in
+ * demod_segments_layout's layout; both are clamped into n_new_windows as the
+ * segment tables are, and the stored fill and keep to keep <= fill <= C: no
+ * content moves a read or a write outside the arrays. d_state[s] gets base,
+ * dropped and fill; keep is consumed (0 afterwards); hold and cut_hits stay.
+ * The scan's tables are written: d_first[s] = s C, d_count[s] = fill. Slot
+ * positions at or past fill are not written. Nothing is allocated or
+ * synchronised, no atomics, no floating-point operation; every output byte is
+ * a function of the inputs alone. Returns DEMOD_OK once enqueued; DEMOD_BAD_ARG,
+ * before any launch, for a NULL handle or pointer, ring "in" equal to ring
+ * "out", n_streams == 0 or > DEMOD_MAX_SEGMENTS, ring_windows == 0, n_streams *
+ * ring_windows >= 2^31, n_new_windows >= 2^31, or a misaligned d_state,
+ * d_new_first, d_first (8 bytes), d_new_count, d_count or power array (4 bytes).
+ */
+int demod_rx_advance_async(demod_t *st, demod_rx_stream_state_t *d_state, const uint8_t *d_ring_sym_in,
+                           const float *d_ring_mag_in, const uint8_t *d_new_sym, const float *d_new_mag,
+                           size_t n_new_windows, const uint64_t *d_new_first,
+                           const uint32_t *d_new_count, size_t n_streams, size_t ring_windows,
+                           uint8_t *d_ring_sym_out, float *d_ring_mag_out, uint64_t *d_first,
+                           uint32_t *d_count, void *stream);
+
+/* Bytes of demod_rx_collect_async's d_work for n_streams streams: two 8-byte
+ * words and one 4-byte word per stream, the last array rounded up to 8. 0 when
+ * the configuration is invalid or n_streams is 0 or above DEMOD_MAX_SEGMENTS.
+ * No device needed. */
+size_t demod_rx_collect_workspace_size(const demod_cfg_t *cfg, size_t n_streams);
+
+/*
+ * Steps 3 and 4 over the check's own outputs (d_hits and d_results the scan's;
+ * d_check, d_kept, d_body and d_check_summary the check's or the coded
+ * check's, group = stream). Enqueued on `stream`: three launches whatever S and
+ * the counts are (per stream, prefix, write). Ranks and body offsets are a
+ * deterministic two-level exclusive prefix, per stream and then over the
+ * streams; no atomics, no floating-point operation. d_frames is [S max_frames],
+ * d_bodies [S max_frames max_len]: nothing can overflow. Stored counts are
+ * clamped to max_frames, a length to max_len, and a kept entry at or above
+ * max_frames is skipped. d_state[s] gets hold, keep (at most fill) and
+ * cut_hits; base, dropped and fill are read. d_summary: the totals, n_checked
+ * and n_valid summed over the streams (each clamped to max_frames). Written:
+ * records < n_frames, body bytes < n_bytes, every byte of *d_summary and of
+ * d_state[0 .. S); nothing else. d_work may hold anything on entry. Returns
+ * DEMOD_OK once enqueued; DEMOD_BAD_ARG, before any launch, for what
+ * demod_frames_check_async (fec 0) or demod_frames_check_coded_async refuses
+ * about the shape, a NULL pointer (d_body and d_bodies excepted when max_len ==
+ * 0), work_bytes below demod_rx_collect_workspace_size, or a misaligned
+ * d_state, d_hits, d_results, d_check_summary, d_frames, d_summary, d_work (8
+ * bytes), d_check or d_kept (4 bytes).
+ */
+int demod_rx_collect_async(demod_t *st, demod_rx_stream_state_t *d_state, const demod_frame_hit_t *d_hits,
+                           const demod_frames_result_t *d_results, const demod_frame_check_t *d_check,
+                           const uint32_t *d_kept, const uint8_t *d_body,
+                           const demod_frames_check_result_t *d_check_summary, size_t n_streams,
+                           size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                           int crc, int fec, demod_rx_frame_t *d_frames, uint8_t *d_bodies,
+                           demod_rx_summary_t *d_summary, void *d_work, size_t work_bytes, void *stream);
+
+/* The receiver handle: n_streams streams of one configuration and one frame
+ * format. NULL on failure, *error set (what demod_rx_sizes and
+ * demod_streams_create refuse; DEMOD_NO_DEVICE, DEMOD_DEVICE_ERROR). */
+typedef struct demod_rx demod_rx_t;
+demod_rx_t *demod_rx_create(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n_streams,
+                            int *error);
+void demod_rx_destroy(demod_rx_t *rx);
+
+/* Drops the stream's sample carry, re-arms cfg.lead_in and zeroes its state: a
+ * frame in flight on that stream is lost, other streams are untouched. */
+int demod_rx_reset(demod_rx_t *rx, size_t stream);
+
+/* The stream's state after the last push (all 0 after create or reset). */
+int demod_rx_state(const demod_rx_t *rx, size_t stream, demod_rx_stream_state_t *state);
+
+/*
+ * One packet per stream, as demod_streams_push takes them (per-stream sample
+ * carry, lead-in, stereo modes, runs laid on hop boundaries). One H2D copy of
+ * the staged runs (the two layout tables ride behind them) goes in; on the
+ * handle's stream the detector, demod_rx_advance_async,
+ * demod_frames_segments_async, the check (or the decode and the coded check)
+ * and demod_rx_collect_async run; one D2H copy of the summary, the states, the
+ * records and the bytes comes back into handle-owned pinned memory (32 + 40 S
+ * + S max_frames (32 + max_len) bytes: max_frames is what sizes it).
+ * *frames[0 .. n_frames) and *bodies[0 .. n_bytes) point into that memory and
+ * stay valid until the next call on the handle; *summary is filled. Returns
+ * n_frames or a negative code; on a refusal (what demod_streams_push refuses
+ * about pcm and n_frames, a NULL frames, bodies or summary) nothing is consumed.
+ */
+int demod_rx_push(demod_rx_t *rx, const int16_t *const *pcm, const size_t *n_frames,
+                  const demod_rx_frame_t **frames, const uint8_t **bodies, demod_rx_summary_t *summary);
+
 /* ---- many streams over many GPUs (config 5), RCCL ---------------------- */
 /*
  * A group of `world` ranks, one per GPU, demodulating n_streams streams of one
