@@ -276,6 +276,42 @@ RX_SUMMARY_DTYPE = np.dtype([("n_frames", "<u8"), ("n_bytes", "<u8"), ("n_checke
                              ("n_valid", "<u8")])                                         # DemodRxSummary
 
 
+class DemodTxCfg(ctypes.Structure):
+    """demod_tx_cfg_t (include/demod.h "transmitter"): the frame format, the
+    signal and the sizes of a transmitter."""
+    _fields_ = [("sync", ctypes.c_uint8 * DEMOD_MAX_SYNC), ("sync_len", ctypes.c_uint32),
+                ("len_bytes", ctypes.c_uint32), ("crc", ctypes.c_uint32), ("fec", ctypes.c_uint32),
+                ("max_len", ctypes.c_uint32), ("gap", ctypes.c_uint32),
+                ("idle", ctypes.c_uint8 * DEMOD_MAX_SYNC), ("idle_len", ctypes.c_uint32),
+                ("amplitude", ctypes.c_int32), ("sigma", ctypes.c_int32), ("ring_symbols", ctypes.c_uint32),
+                ("seed", ctypes.c_uint64), ("max_frames", ctypes.c_uint32), ("max_samples", ctypes.c_uint32)]
+
+
+class DemodTxStreamState(ctypes.Structure):
+    """demod_tx_stream_state_t: one stream's queue and phase state, device and host."""
+    _fields_ = [("head", ctypes.c_uint64), ("tail", ctypes.c_uint64), ("accepted", ctypes.c_uint64),
+                ("refused", ctypes.c_uint64), ("offset", ctypes.c_uint32), ("phase", ctypes.c_uint32)]
+
+
+class DemodTxPlace(ctypes.Structure):
+    """demod_tx_place_t: where a frame of a send went."""
+    _fields_ = [("start", ctypes.c_uint64), ("symbols", ctypes.c_uint32), ("status", ctypes.c_uint32)]
+
+
+class DemodTxSizes(ctypes.Structure):
+    """demod_tx_sizes_t: what demod_tx_sizes reports."""
+    _fields_ = [(f, ctypes.c_uint64) for f in (
+        "max_symbols", "ring_bytes", "state_bytes", "places_bytes", "records_bytes", "bodies_bytes",
+        "pcm_bytes", "modulate_work_bytes")]
+
+
+TX_STATE_DTYPE = np.dtype([("head", "<u8"), ("tail", "<u8"), ("accepted", "<u8"), ("refused", "<u8"),
+                           ("offset", "<u4"), ("phase", "<u4")])                          # DemodTxStreamState
+TX_RECORD_DTYPE = np.dtype([("length", "<u4"), ("body", "<u4")])                         # demod_tx_record_t
+TX_PLACE_DTYPE = np.dtype([("start", "<u8"), ("symbols", "<u4"), ("status", "<u4")])     # DemodTxPlace
+DEMOD_TX_OK, DEMOD_TX_BAD_LENGTH, DEMOD_TX_NO_ROOM = 0, 1, 2
+
+
 class DemodError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -425,6 +461,24 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "demod_rx_state": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(DemodRxStreamState)]),
         "demod_rx_push": (ctypes.c_int, [_P, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_P),
                                          ctypes.POINTER(DemodRxSummary)]),
+        "demod_tx_frame_symbol_count": (ctypes.c_longlong, [ctypes.POINTER(DemodTxCfg), ctypes.c_uint32, _SZ]),
+        "demod_tx_frame_symbols": (ctypes.c_longlong, [ctypes.POINTER(DemodTxCfg), ctypes.c_uint32, _P, _SZ,
+                                                       _P, _SZ]),
+        "demod_tx_sizes": (ctypes.c_int, [ctypes.POINTER(DemodCfg), ctypes.POINTER(DemodTxCfg), _SZ,
+                                          ctypes.POINTER(DemodTxSizes)]),
+        "demod_tx_encode_async": (ctypes.c_int, [_P, ctypes.POINTER(DemodTxCfg), _P, _P, _P, _P, _P, _SZ, _SZ,
+                                                 _P, _P]),
+        "demod_tx_modulate_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), ctypes.POINTER(DemodTxCfg), _SZ]),
+        "demod_tx_modulate_async": (ctypes.c_int, [_P, ctypes.POINTER(DemodTxCfg), _P, _P, _P, _SZ, _P, _P,
+                                                   _SZ, _P]),
+        "demod_tx_create": (_P, [ctypes.POINTER(DemodCfg), ctypes.POINTER(DemodTxCfg), _SZ,
+                                 ctypes.POINTER(ctypes.c_int)]),
+        "demod_tx_destroy": (None, [_P]),
+        "demod_tx_reset": (ctypes.c_int, [_P, _SZ]),
+        "demod_tx_state": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(DemodTxStreamState)]),
+        "demod_tx_device_buffers": (ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+        "demod_tx_send": (ctypes.c_int, [_P, _P, _SZ, _P, _SZ, _P]),
+        "demod_tx_pull": (ctypes.c_longlong, [_P, _P, _P]),
         "demod_synth_fsk": (ctypes.c_int, [ctypes.POINTER(DemodCfg), ctypes.c_uint64,
                                            ctypes.c_uint64, _SZ, ctypes.c_int, ctypes.c_int,
                                            _P, _P, _P]),
@@ -653,6 +707,72 @@ def rx_sizes(cfg: DemodCfg, rxcfg: DemodRxCfg, n_streams: int) -> dict:
     if rc != DEMOD_OK:
         raise DemodError(rc, "demod_rx_sizes")
     return {f: int(getattr(out, f)) for f, _ in DemodRxSizes._fields_}
+
+
+def make_tx_cfg(sync, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE, fec: int = 0, max_len: int = 0,
+                gap: int = 0, idle=(0,), amplitude: int = 8000, sigma: int = 0, seed: int = 0,
+                ring_symbols: int = 0, max_frames: int = 1, max_samples: int = 8) -> DemodTxCfg:
+    """A demod_tx_cfg_t (include/demod.h "transmitter"). Nothing is judged here:
+    demod_tx_sizes does that."""
+    sb, ib = _sync_bytes(sync), _sync_bytes(idle)
+    if sb.size > DEMOD_MAX_SYNC or ib.size > DEMOD_MAX_SYNC:
+        raise DemodError(DEMOD_BAD_ARG, "the word and the idle pattern hold at most DEMOD_MAX_SYNC symbols")
+    x = DemodTxCfg()
+    for i, v in enumerate(sb.tolist()):
+        x.sync[i] = v
+    for i, v in enumerate(ib.tolist()):
+        x.idle[i] = v
+    x.sync_len, x.idle_len = sb.size, ib.size
+    x.len_bytes, x.crc, x.fec, x.max_len, x.gap = len_bytes, crc, fec, max_len, gap
+    x.amplitude, x.sigma, x.seed = amplitude, sigma, seed
+    x.ring_symbols, x.max_frames, x.max_samples = ring_symbols, max_frames, max_samples
+    return x
+
+
+def tx_sizes(cfg: DemodCfg, txcfg: DemodTxCfg, n_streams: int) -> dict:
+    """demod_tx_sizes: A(max_len) and every buffer's bytes (no GPU). Raises
+    DemodError(DEMOD_BAD_ARG) for a pair or a stream count the transmitter refuses."""
+    if n_streams < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_tx_sizes")
+    out = DemodTxSizes()
+    rc = load_library().demod_tx_sizes(ctypes.byref(cfg), ctypes.byref(txcfg), int(n_streams), ctypes.byref(out))
+    if rc < 0:
+        raise DemodError(rc, "demod_tx_sizes")
+    return {f: int(getattr(out, f)) for f, _ in DemodTxSizes._fields_}
+
+
+def tx_modulate_workspace_size(cfg: DemodCfg, txcfg: DemodTxCfg, n_streams: int) -> int:
+    """demod_tx_modulate_workspace_size (no GPU). Raises DemodError(DEMOD_BAD_ARG)
+    where the C function reports 0."""
+    size = int(load_library().demod_tx_modulate_workspace_size(
+        ctypes.byref(cfg), ctypes.byref(txcfg), int(n_streams))) if n_streams >= 0 else 0
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_tx_modulate_workspace_size")
+    return size
+
+
+def tx_frame_symbol_count(txcfg: DemodTxCfg, k: int, length: int) -> int:
+    """demod_tx_frame_symbol_count: A(length), the symbols of a frame on the air."""
+    if length < 0 or k < 0:
+        raise DemodError(DEMOD_BAD_ARG, "demod_tx_frame_symbol_count")
+    rc = int(load_library().demod_tx_frame_symbol_count(ctypes.byref(txcfg), int(k), int(length)))
+    if rc < 0:
+        raise DemodError(rc, "demod_tx_frame_symbol_count")
+    return rc
+
+
+def tx_frame_symbols(txcfg: DemodTxCfg, k: int, data: bytes) -> np.ndarray:
+    """demod_tx_frame_symbols: the word and the payload symbols of one frame
+    (uint8 [A(len(data))]), the reference of the transmitter's write launch."""
+    data = bytes(data)
+    A = tx_frame_symbol_count(txcfg, k, len(data))
+    out = np.zeros(A, np.uint8)
+    buf = ctypes.create_string_buffer(data, max(len(data), 1))
+    rc = int(load_library().demod_tx_frame_symbols(ctypes.byref(txcfg), int(k), ctypes.addressof(buf), len(data),
+                                                   out.ctypes.data, A))
+    if rc < 0:
+        raise DemodError(rc, "demod_tx_frame_symbols")
+    return out
 
 
 def rx_collect_workspace_size(cfg: DemodCfg, n_streams: int) -> int:
@@ -1388,6 +1508,55 @@ class Demodulator:
         if rc < 0:
             raise DemodError(rc, "demod_rx_collect_async")
 
+    def _tx_shape(self, txcfg: DemodTxCfg, n_streams: int) -> dict:
+        if n_streams < 1:
+            raise DemodError(DEMOD_BAD_ARG, "n_streams < 1")
+        return tx_sizes(self.cfg, txcfg, int(n_streams))
+
+    def tx_encode_async(self, txcfg: DemodTxCfg, d_state, d_ring, d_records, d_count, d_bytes, n_bytes: int,
+                        n_streams: int, d_place, stream: int = 0) -> None:
+        """demod_tx_encode_async (include/demod.h "transmitter", send): two
+        launches. d_state (uint8, n_streams * 40 bytes), d_ring (uint8 n_streams
+        * ring_symbols), d_records (uint8, n_streams * max_frames * 8 bytes),
+        d_count (int32 holding uint32 [n_streams]), d_bytes (uint8 n_bytes, or
+        None when n_bytes == 0) and d_place (uint8, n_streams * max_frames * 16
+        bytes) are device tensors, checked like the batch calls'."""
+        z = self._tx_shape(txcfg, n_streams)
+        S, nb = int(n_streams), int(n_bytes)
+        if nb < 0 or nb >= 2 ** 32:
+            raise DemodError(DEMOD_BAD_ARG, "n_bytes not in 0 .. 2^32 - 1")
+        dev = int(self.cfg.device)
+        _check_dev(d_state, "d_state", "uint8", z["state_bytes"], dev)
+        _check_dev(d_ring, "d_ring", "uint8", z["ring_bytes"], dev)
+        _check_dev(d_records, "d_records", "uint8", z["records_bytes"], dev)
+        _check_dev(d_count, "d_count", "int32", S, dev)
+        _check_dev(d_bytes, "d_bytes", "uint8", max(nb, 1), dev, nullable=nb == 0)
+        _check_dev(d_place, "d_place", "uint8", z["places_bytes"], dev)
+        rc = self._lib.demod_tx_encode_async(self._h, ctypes.byref(txcfg), _ptr(d_state), _ptr(d_ring),
+                                             _ptr(d_records), _ptr(d_count), _ptr(d_bytes), nb, S,
+                                             _ptr(d_place), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_tx_encode_async")
+
+    def tx_modulate_async(self, txcfg: DemodTxCfg, d_state, d_ring, d_count, n_streams: int, d_pcm, d_work,
+                          stream: int = 0) -> None:
+        """demod_tx_modulate_async (include/demod.h "transmitter", modulate):
+        three launches. d_pcm is int16 [n_streams * max_samples], d_work uint8 of
+        tx_modulate_workspace_size bytes; the rest as tx_encode_async."""
+        z = self._tx_shape(txcfg, n_streams)
+        S = int(n_streams)
+        dev = int(self.cfg.device)
+        _check_dev(d_state, "d_state", "uint8", z["state_bytes"], dev)
+        _check_dev(d_ring, "d_ring", "uint8", z["ring_bytes"], dev)
+        _check_dev(d_count, "d_count", "int32", S, dev)
+        _check_dev(d_pcm, "d_pcm", "int16", z["pcm_bytes"] // 2, dev)
+        _check_dev(d_work, "d_work", "uint8", z["modulate_work_bytes"], dev)
+        rc = self._lib.demod_tx_modulate_async(self._h, ctypes.byref(txcfg), _ptr(d_state), _ptr(d_ring),
+                                               _ptr(d_count), S, _ptr(d_pcm), _ptr(d_work),
+                                               int(d_work.numel()), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_tx_modulate_async")
+
     def frames_checked(self, pcm, sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
                        crc: int = DEMOD_CRC16_CCITT_FALSE, max_frames: Optional[int] = None,
                        n_windows: Optional[int] = None, body: bool = True):
@@ -1631,6 +1800,116 @@ class Receiver:
         raw = ctypes.string_at(bodies.value, summary["n_bytes"]) if summary["n_bytes"] else b""
         out = [raw[int(r["body"]):int(r["body"]) + int(r["length"])] for r in rec]
         return rec, out, summary
+
+
+class Transmitter:
+    """demod_tx_t: frames in, as Receiver.push hands them out, and the
+    phase-continuous signal of n_streams streams out; queues and phases are
+    kept on the device (include/demod.h "transmitter")."""
+
+    def __init__(self, n_streams: int, txcfg: DemodTxCfg, cfg: Optional[DemodCfg] = None, **kw):
+        self._lib = load_library()
+        self.cfg = cfg if cfg is not None else make_cfg(**kw)
+        self.txcfg = txcfg
+        self.n_streams = int(n_streams)
+        self.sizes = tx_sizes(self.cfg, txcfg, self.n_streams)
+        err = ctypes.c_int(0)
+        h = self._lib.demod_tx_create(ctypes.byref(self.cfg), ctypes.byref(txcfg), self.n_streams,
+                                      ctypes.byref(err))
+        if not h:
+            raise DemodError(err.value, "demod_tx_create")
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.demod_tx_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream: int) -> None:
+        rc = self._lib.demod_tx_reset(self._h, int(stream)) if stream >= 0 else DEMOD_BAD_ARG
+        if rc < 0:
+            raise DemodError(rc, "demod_tx_reset")
+
+    def state(self, stream: int) -> dict:
+        """The stream's demod_tx_stream_state_t after the last send or pull."""
+        if stream < 0:
+            raise DemodError(DEMOD_BAD_ARG, "demod_tx_state")
+        st = DemodTxStreamState()
+        rc = self._lib.demod_tx_state(self._h, int(stream), ctypes.byref(st))
+        if rc < 0:
+            raise DemodError(rc, "demod_tx_state")
+        return {f: int(getattr(st, f)) for f, _ in DemodTxStreamState._fields_}
+
+    def device_buffers(self) -> Tuple[int, int]:
+        """The device addresses of the last pull's samples [S][max_samples] and of the ring."""
+        pcm, ring = _P(), _P()
+        rc = self._lib.demod_tx_device_buffers(self._h, ctypes.byref(pcm), ctypes.byref(ring))
+        if rc < 0:
+            raise DemodError(rc, "demod_tx_device_buffers")
+        return int(pcm.value), int(ring.value)
+
+    def device_pcm(self):
+        """The last pull's samples on the device, a torch int16 tensor
+        [n_streams * max_samples] over the handle's own memory (no copy): what
+        demod_batch_async takes. Valid until the handle is closed."""
+        import torch
+
+        class _View:
+            pass
+        v = _View()
+        v.__cuda_array_interface__ = {"shape": (self.n_streams * int(self.txcfg.max_samples),), "typestr": "<i2",
+                                      "data": (self.device_buffers()[0], False), "version": 2}
+        return torch.as_tensor(v, device=f"cuda:{int(self.cfg.device)}")
+
+    def send(self, frames, bodies: bytes = b""):
+        """frames: an RX_FRAME_DTYPE array as Receiver.push returns it (stream,
+        length and body are read) with bodies the dense bytes, or a list of
+        (stream, bytes) pairs. Returns (accepted, places: a TX_PLACE_DTYPE
+        array in input order)."""
+        if not isinstance(frames, np.ndarray):
+            pairs = [(int(s), bytes(b)) for s, b in frames]
+            rec = np.zeros(len(pairs), RX_FRAME_DTYPE)
+            off = 0
+            for i, (s, b) in enumerate(pairs):
+                rec[i]["stream"], rec[i]["length"], rec[i]["body"] = s, len(b), off
+                off += len(b)
+            frames, bodies = rec, b"".join(b for _, b in pairs)
+        rec = np.ascontiguousarray(frames, dtype=RX_FRAME_DTYPE)
+        bodies = bytes(bodies)
+        buf = ctypes.create_string_buffer(bodies, max(len(bodies), 1))
+        place = np.zeros(rec.size, TX_PLACE_DTYPE)
+        rc = self._lib.demod_tx_send(self._h, rec.ctypes.data if rec.size else None, rec.size,
+                                     ctypes.addressof(buf), len(bodies), place.ctypes.data if rec.size else None)
+        if rc < 0:
+            raise DemodError(rc, "demod_tx_send")
+        return rc, place
+
+    def pull(self, n_frames) -> list:
+        """n_frames: one count for every stream, or a sequence of n_streams
+        counts. Returns the streams' int16 sample arrays."""
+        S = self.n_streams
+        counts = [int(n_frames)] * S if np.isscalar(n_frames) else [int(v) for v in n_frames]
+        if len(counts) != S or min(counts) < 0:
+            raise DemodError(DEMOD_BAD_ARG, "one non-negative count per stream")
+        out = [np.empty(c, np.int16) for c in counts]
+        nfr = np.asarray(counts, dtype=np.uintp)
+        ptrs = np.asarray([a.ctypes.data if a.size else 0 for a in out], dtype=np.uintp)
+        rc = self._lib.demod_tx_pull(self._h, nfr.ctypes.data, ptrs.ctypes.data)
+        if rc < 0:
+            raise DemodError(rc, "demod_tx_pull")
+        return out
 
 
 # demod_decode_fn: opus_decode's signature (opus.h:462)

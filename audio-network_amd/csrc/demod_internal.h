@@ -15,6 +15,9 @@ struct demod_frame_decode;
 struct demod_rx_stream_state;
 struct demod_rx_frame;
 struct demod_rx_summary;
+struct demod_tx_stream_state;
+struct demod_tx_record;
+struct demod_tx_place;
 
 namespace fskd {
 
@@ -462,5 +465,50 @@ struct RxCollectParams {
 };
 constexpr size_t rx_collect_work_bytes(size_t S) { return 16 * S + (4 * S + 7) / 8 * 8; }
 hipError_t launch_rx_collect(const RxCollectParams &p, hipStream_t s);
+
+// frames_tx.hip: the transmitter's device stages (include/demod.h
+// "transmitter"). encode = plan + write, modulate = phase + samples + state.
+// The word and the idle pattern travel as 4-bit symbols, 16 to a 64-bit word:
+// a lookup is four selects and a shift, no table in memory.
+constexpr unsigned kTxMaxWaves = 16384;   // write: waves per call (or one per group), as the check's
+constexpr unsigned tx_waves_per_group(unsigned n_streams, unsigned max_frames)
+{
+    const unsigned most = kTxMaxWaves / n_streams ? kTxMaxWaves / n_streams : 1;
+    return max_frames < most ? max_frames : most;
+}
+struct TxParams {
+    ::demod_tx_stream_state *state;       // [n_streams]
+    uint8_t *ring;                        // [n_streams][ring_symbols]
+    unsigned n_streams;
+    unsigned ring_symbols;                // C; n_streams * C < 2^31
+    unsigned n;                           // samples per symbol, a power of two
+    int log2n;
+    int bits;                             // demod_bits_per_symbol(k)
+    unsigned sync_len, idle_len;          // 1 .. 64
+    unsigned long long sync4[4], idle4[4];
+    // encode
+    const ::demod_tx_record *records;     // [n_streams][max_frames]
+    const unsigned *count;                // [n_streams]: frames (encode) or samples (modulate)
+    const uint8_t *bytes;                 // [n_bytes]
+    unsigned n_bytes;
+    unsigned max_frames;                  // n_streams * max_frames < 2^31
+    unsigned max_len, gap;
+    int len_bytes, crc_bytes, fec;        // h, c, 0 or DEMOD_FEC_CONV_K7
+    unsigned poly, init;                  // as FramesCheckParams
+    unsigned xpow8[kCrcPowBits];
+    ::demod_tx_place *place;              // [n_streams][max_frames]
+    // modulate
+    const int16_t *lut;                   // synth.hip's sine table on this device
+    uint32_t inc[kMaxTones];              // 0 at and past K
+    int amplitude, sigma;
+    uint64_t seed;
+    unsigned stride;                      // samples per stream; n_streams * stride < 2^31
+    unsigned work_stride;                 // (n - 1 + stride) / n + 2
+    int16_t *pcm;                         // [n_streams][stride]
+    uint32_t *work;                       // [n_streams][work_stride]
+};
+hipError_t launch_tx_encode(const TxParams &p, hipStream_t s);
+hipError_t launch_tx_modulate(const TxParams &p, hipStream_t s);
+const int16_t *synth_lut_device();        // synth.hip: the table's address on the current device
 
 }  // namespace fskd

@@ -38,6 +38,7 @@
 // their CRC overlap each other. No atomics; every output byte is a function of
 // the inputs alone.
 #include "acquire_scan.h"
+#include "crc_ops.h"
 
 namespace fskd {
 
@@ -46,27 +47,6 @@ constexpr int kChkWaves = kAcqThreads / kChkLanes;
 constexpr unsigned kChkMaxWaves = 16384;   // check and body: waves per call (or one per group)
 
 static_assert(kAcqThreads == 256, "one thread builds one entry of the byte table");
-
-// r(x) x mod P; the register and P in the top `width` bits
-static __device__ __forceinline__ unsigned crc_xtime(unsigned r, unsigned poly)
-{
-    return (r << 1) ^ ((r >> 31) ? poly : 0u);
-}
-
-// a(x) b(x) mod P by Horner over b's WIDTH coefficients, highest first; no
-// branches. Unrolled by 8 only, and its caller's loop not at all: a wave runs
-// this code once, and straight-line code costs more to fetch than it saves.
-template <int WIDTH>
-static __device__ __forceinline__ unsigned crc_mul(unsigned a, unsigned b, unsigned poly)
-{
-    unsigned r = 0;
-#pragma unroll 8
-    for (int i = 0; i < WIDTH; ++i) {
-        r = (r << 1) ^ (poly & (unsigned)((int)r >> 31)) ^ (a & (unsigned)((int)b >> 31));
-        b <<= 1;
-    }
-    return r;
-}
 
 static __device__ __forceinline__ unsigned group_rows(const FramesCheckParams &p, unsigned g)
 {
@@ -100,19 +80,7 @@ __global__ __launch_bounds__(kAcqThreads) void frames_check_kernel(FramesCheckPa
         unsigned crc = 0, status = DEMOD_CHECK_BAD_LENGTH;
         if (len <= p.max_len) {
             const unsigned n = (unsigned)h + len;               // <= row_bytes - crc_bytes
-            const unsigned chunk = (n + kChkLanes - 1) / kChkLanes;
-            const unsigned lo = (unsigned)lane * chunk < n ? (unsigned)lane * chunk : n;
-            const unsigned hi = lo + chunk < n ? lo + chunk : n;
-            unsigned reg = lane == 0 ? p.init : 0u;
-            for (unsigned b = lo; b < hi; ++b) reg = (reg << 8) ^ s_tab[(reg >> 24) ^ row[b]];
-            if (reg != 0 && hi < n) {
-                // times x^(8 (n - hi)): square-and-multiply, the squares x^(8 2^j) from the host
-                const unsigned after = n - hi;
-#pragma unroll 1
-                for (int j = 0; j < kCrcPowBits && (after >> j) != 0; ++j)
-                    if ((after >> j) & 1u) reg = crc_mul<WIDTH>(reg, p.xpow8[j], p.poly);
-            }
-            for (int d = kChkLanes / 2; d > 0; d >>= 1) reg ^= __shfl_xor(reg, d);
+            const unsigned reg = crc_wave<WIDTH>(row, n, lane, p.init, p.poly, p.xpow8, s_tab);
             crc = reg >> (32 - WIDTH);
             unsigned stored = 0;
             for (int b = 0; b < p.crc_bytes; ++b) stored = (stored << 8) | row[n + b];

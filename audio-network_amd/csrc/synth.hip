@@ -10,6 +10,7 @@
 
 #include "demod_internal.h"
 #include "kernel_ops.h"
+#include "synth_ops.h"
 
 namespace fskd {
 
@@ -20,31 +21,39 @@ namespace fskd {
 __device__ int16_t g_sine_lut[16384];
 __device__ unsigned g_ceiling_sink[16];
 
+static std::mutex g_lut_mu;
+static const int16_t *g_lut_ptr[kMaxDevices] = {};   // the table's address once it is filled, per device
+
 hipError_t synth_prepare()
 {
-    static std::mutex mu;
-    static bool ready[kMaxDevices] = {};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> lock(mu);
-    if (ready[dev]) return hipSuccess;
+    std::lock_guard<std::mutex> lock(g_lut_mu);
+    if (g_lut_ptr[dev]) return hipSuccess;
     // the Q15 sine table of oracle/fsk_oracle.c:oracle_sine_lut
     std::vector<int16_t> lut(16384);
     for (int i = 0; i < 16384; ++i)
         lut[i] = (int16_t)std::lrint(32767.0 * std::sin(2.0 * M_PI * (double)i / 16384.0));
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_sine_lut), lut.data(), lut.size() * sizeof(int16_t), 0,
                           hipMemcpyHostToDevice);
-    if (e == hipSuccess) ready[dev] = true;
+    if (e != hipSuccess) return e;
+    void *p = nullptr;
+    e = hipGetSymbolAddress(&p, HIP_SYMBOL(g_sine_lut));
+    if (e == hipSuccess) g_lut_ptr[dev] = static_cast<const int16_t *>(p);
     return e;
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
+// The filled table's address on the current device, for the transmitter's
+// kernels (frames_tx.hip): one table, shared. nullptr before synth_prepare. No
+// runtime call but hipGetDevice, so a captured stream is not disturbed.
+const int16_t *synth_lut_device()
 {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
+    std::lock_guard<std::mutex> lock(g_lut_mu);
+    return g_lut_ptr[dev];
 }
 
 __global__ __launch_bounds__(256) void synth_kernel(SynthParams p)

@@ -1242,6 +1242,255 @@ int demod_rx_state(const demod_rx_t *rx, size_t stream, demod_rx_stream_state_t 
 int demod_rx_push(demod_rx_t *rx, const int16_t *const *pcm, const size_t *n_frames,
                   const demod_rx_frame_t **frames, const uint8_t **bodies, demod_rx_summary_t *summary);
 
+/* ---- transmitter: frames in, the signal of many streams out ------------ */
+/*
+ * The other end of the receiver: frames are encoded (checked, or checked and
+ * convolutionally coded) into symbols and queued per stream on the device, and
+ * every pull modulates the next samples of every stream, phase-continuous,
+ * with idle symbols when a queue runs dry. Integer arithmetic alone; every
+ * output byte is a function of the inputs alone. This text is normative.
+ *
+ *   bits = demod_bits_per_symbol(K); n = cfg.n: a symbol lasts n samples (R
+ *   hops). inc[t] = llround(freqs[t] / fs 2^32) & 0xFFFFFFFF for t < K, as
+ *   demod_synth_fsk derives it, and 0 for K <= t < 16. lut is the generator's
+ *   Q15 sine table (16384 entries), mix64 the splitmix64 finaliser and gamma =
+ *   0x9E3779B97F4A7C15, all as DESIGN.md "Synthetic input" has them.
+ *
+ * A frame on the air is A(len) = L + Sp(len) symbols: the word, then
+ *   fec == 0                 Sp = ceil(8 (h + len + c) / bits): demod_unpack_symbols
+ *                            of demod_checked_frame_encode's bytes, the missing
+ *                            bits of the last symbol 0;
+ *   fec == DEMOD_FEC_CONV_K7 Sp = demod_coded_frame_symbols(..): the same of
+ *                            demod_coded_frame_encode's bytes, coded bits at or
+ *                            past 2 T(len) 0. K must be a power of two.
+ * The idle symbol of stream-absolute symbol index q is idle[q mod idle_len].
+ *
+ * State per stream (all 0 after create or reset): head is the symbol being
+ * modulated, offset < n the sample inside it, phase = PHI(head); the symbols
+ * head <= q < tail are queued in a [S][C] byte ring at q mod C (C =
+ * ring_symbols). Invariant: head + (offset > 0) <= tail <= head + C. Every
+ * launch clamps the tail it reads into that range and offset to n - 1; no
+ * content of the state, the ring or the tables moves an access outside the
+ * arrays.
+ *
+ * send. Group (stream) s has cnt = min(d_count[s], max_frames) records {length,
+ * body} at [s][i]; the data bytes of all records lie in one dense array of
+ * n_bytes bytes. body' = min(body, n_bytes - min(length, n_bytes)), and a byte
+ * at or past n_bytes reads as 0. a_i = 0 and status DEMOD_TX_BAD_LENGTH when
+ * length_i > max_len, else a_i = A(length_i) + gap; e_i is the inclusive prefix
+ * of a over the frames 0 .. i of the call, accepted or not. A frame of valid
+ * length is accepted (DEMOD_TX_OK) iff tail + e_i - head <= C, else its status
+ * is DEMOD_TX_NO_ROOM: e is monotone, so the accepted frames keep their order
+ * and everything behind the first NO_ROOM is NO_ROOM. An accepted frame starts
+ * at start_i = tail + e_i - a_i; its A symbols go to the ring at [start_i,
+ * start_i + A) and the idle symbols of those indices to the `gap` positions
+ * behind them. place[s][i] = {start_i, A, OK} or {0, 0, status}. Then tail += e
+ * of the last accepted frame, accepted += the frames accepted, refused += cnt -
+ * that.
+ *
+ * modulate. Stream s gets m = min(d_count[s], stride) samples at d_pcm[s stride
+ * + x], x < m; nothing is written at x >= m (stride = max_samples). With y =
+ * offset + x, q = head + y / n, r = y mod n:
+ *   sym(q) = ring[q mod C] & 15 when q < tail, else the idle symbol of q;
+ *   PHI(q) = phase + n sum_{head <= j < q} inc[sym(j)]  mod 2^32;
+ *   ph     = PHI(q) + r inc[sym(q)]                      mod 2^32;
+ *   tone   = (amplitude lut[ph >> 18] + 16384) >> 15;
+ *   d      = mix64(mix64(seed + (s + 1) gamma) + (head n + y + 1) gamma);
+ *   u      = the sum of d's four 16-bit fields;
+ *   noise  = ((u - 131070) sigma 113512) >> 32   (int64, arithmetic shift);
+ *   sample = tone + noise clamped to int16.
+ * Afterwards, with y_end = offset + m: head' = head + y_end / n, offset' = y_end
+ * mod n, phase' = PHI(head'), tail' = max(tail, head' + (offset' > 0)); when
+ * that raises the tail (the pull ends inside an idle symbol past the queue),
+ * the idle symbol of head' is stored at ring[head' mod C]: it is queued now,
+ * and the next pull reads it there like any other.
+ * The phase is continuous across symbols, pulls and underflow into idle, and
+ * the noise depends on the stream and the stream-absolute sample alone: the
+ * samples of a stream are the same bytes whatever the pull sizes are.
+ */
+#define DEMOD_TX_OK          0
+#define DEMOD_TX_BAD_LENGTH  1   /* length > max_len */
+#define DEMOD_TX_NO_ROOM     2   /* the ring cannot take the frame (or one before it) */
+
+typedef struct demod_tx_cfg {          /* 184 bytes, no padding */
+    uint8_t  sync[DEMOD_MAX_SYNC];     /* the word, sync_len symbols, each < K */
+    uint32_t sync_len;                 /* L, 1 .. DEMOD_MAX_SYNC */
+    uint32_t len_bytes, crc;           /* h; DEMOD_CRC16_CCITT_FALSE or DEMOD_CRC32_MPEG2 */
+    uint32_t fec;                      /* 0 or DEMOD_FEC_CONV_K7 */
+    uint32_t max_len;                  /* <= min(256^h - 1, DEMOD_MAX_FRAME_PAYLOAD) */
+    uint32_t gap;                      /* idle symbols behind each frame */
+    uint8_t  idle[DEMOD_MAX_SYNC];     /* the idle pattern, idle_len symbols, each < K */
+    uint32_t idle_len;                 /* 1 .. DEMOD_MAX_SYNC */
+    int32_t  amplitude;                /* 0 .. 32767 */
+    int32_t  sigma;                    /* 0 .. 32767, as demod_synth_fsk */
+    uint32_t ring_symbols;             /* C >= A(max_len) + gap */
+    uint64_t seed;
+    uint32_t max_frames;               /* frames per stream and send */
+    uint32_t max_samples;              /* samples per stream and pull: the stride, a multiple of 8 */
+} demod_tx_cfg_t;
+
+typedef struct demod_tx_stream_state { /* 40 bytes, one per stream, device and host */
+    uint64_t head, tail, accepted, refused;
+    uint32_t offset, phase;
+} demod_tx_stream_state_t;
+
+typedef struct demod_tx_record {       /* 8 bytes: one frame of a send, on the device */
+    uint32_t length, body;             /* data bytes; their offset in the dense byte array */
+} demod_tx_record_t;
+
+typedef struct demod_tx_place {        /* 16 bytes */
+    uint64_t start;                    /* stream-absolute symbol index of the word's first symbol */
+    uint32_t symbols, status;          /* A(length); DEMOD_TX_*. start and symbols 0 unless OK */
+} demod_tx_place_t;
+
+typedef struct demod_tx_sizes {
+    uint64_t max_symbols;              /* A(max_len) */
+    uint64_t ring_bytes;               /* S C */
+    uint64_t state_bytes;              /* S states */
+    uint64_t places_bytes;             /* S max_frames places */
+    uint64_t records_bytes;            /* S max_frames records */
+    uint64_t bodies_bytes;             /* S max_frames max_len: the most a send's accepted data takes */
+    uint64_t pcm_bytes;                /* S max_samples samples */
+    uint64_t modulate_work_bytes;      /* demod_tx_modulate_workspace_size */
+} demod_tx_sizes_t;
+
+/* A(len) for the format of txcfg and K = k tones; DEMOD_BAD_ARG for a NULL
+ * txcfg, k outside 2 .. DEMOD_MAX_TONES (with fec: not a power of two),
+ * sync_len outside 1 .. DEMOD_MAX_SYNC or an unknown len_bytes, crc or fec;
+ * DEMOD_FRAME_TOO_LARGE for len > max_len or what demod_checked_frame_size
+ * refuses. No device needed. */
+long long demod_tx_frame_symbol_count(const demod_tx_cfg_t *txcfg, uint32_t k, size_t len);
+
+/* The A(len) symbols of one frame into out[0 .. cap), built from
+ * demod_checked_frame_encode or demod_coded_frame_encode and
+ * demod_unpack_symbols: the reference demod_tx_encode_async is held to. Returns
+ * A(len), what demod_tx_frame_symbol_count refuses, DEMOD_BAD_ARG for a NULL
+ * pointer or a word symbol >= k, or DEMOD_BUFFER_TOO_SMALL. No device needed. */
+long long demod_tx_frame_symbols(const demod_tx_cfg_t *txcfg, uint32_t k, const uint8_t *data, size_t len,
+                                 uint8_t *out, size_t cap);
+
+/* Validates the pair and fills *out. No device needed. DEMOD_BAD_ARG for a
+ * NULL pointer, an invalid configuration, K < 2, a word or idle length outside
+ * 1 .. DEMOD_MAX_SYNC or a symbol of either >= K, an unknown crc, len_bytes or
+ * fec, K not a power of two with fec, max_len above min(256^h - 1,
+ * DEMOD_MAX_FRAME_PAYLOAD), C < A(max_len) + gap, n_streams == 0 or >
+ * DEMOD_MAX_SEGMENTS, max_frames == 0, n_streams * max_frames >= 2^31,
+ * n_streams * C >= 2^31, max_samples 0 or not a multiple of 8, n_streams *
+ * max_samples >= 2^31, amplitude or sigma outside 0 .. 32767. */
+int demod_tx_sizes(const demod_cfg_t *cfg, const demod_tx_cfg_t *txcfg, size_t n_streams,
+                   demod_tx_sizes_t *out);
+
+/*
+ * send on the device. Enqueued on `stream`: two launches whatever S and the
+ * counts are. Nothing is allocated or synchronised, no atomics, no
+ * floating-point operation, and the handle keeps no state of the call: it can
+ * be captured and replayed after the records, counts and bytes were rewritten
+ * in place.
+ *   plan   one wave a stream walks its records 64 at a time: the prefix e by a
+ *          wave scan with a running carry, acceptance, the places; then tail,
+ *          accepted and refused (tail and offset are stored clamped).
+ *   write  one wave a frame; wave c of a group's min(max_frames, max(16384 / S,
+ *          1)) waves takes frames c, c + wpg, ..: len || data || CRC in the
+ *          wave's LDS, the CRC by the check's lane-split scheme, then lane j
+ *          writes symbols j, j + 64, ..: the word, its bits of the checked
+ *          frame or, coded, each coded bit m from the information bits (m >> 1)
+ *          - 6 .. m >> 1 alone, and the gap's idle symbols. Consecutive bytes
+ *          per wave step; a run may wrap the ring once.
+ * d_state [S], d_ring [S][C], d_records and d_place [S][max_frames], d_count
+ * [S], d_bytes [n_bytes] (may be NULL when n_bytes == 0). Written: places i <
+ * cnt, the ring positions of the accepted frames, every byte of d_state;
+ * nothing else. Returns DEMOD_OK once enqueued; DEMOD_BAD_ARG, before any
+ * launch, for what demod_tx_sizes refuses, a NULL handle or pointer, n_bytes >=
+ * 2^32, or a misaligned d_state, d_place (8 bytes), d_records or d_count (4
+ * bytes).
+ */
+int demod_tx_encode_async(demod_t *st, const demod_tx_cfg_t *txcfg, demod_tx_stream_state_t *d_state,
+                          uint8_t *d_ring, const demod_tx_record_t *d_records, const uint32_t *d_count,
+                          const uint8_t *d_bytes, size_t n_bytes, size_t n_streams,
+                          demod_tx_place_t *d_place, void *stream);
+
+/* Bytes of demod_tx_modulate_async's d_work: one uint32_t PHI per symbol that a
+ * pull can touch, [S][(n - 1 + max_samples) / n + 2]. 0 for what demod_tx_sizes
+ * refuses. No device needed. */
+size_t demod_tx_modulate_workspace_size(const demod_cfg_t *cfg, const demod_tx_cfg_t *txcfg,
+                                        size_t n_streams);
+
+/*
+ * modulate on the device. Enqueued on `stream`: three launches whatever S and
+ * the counts are; nothing is allocated or synchronised, no atomics, no
+ * floating-point operation; d_work may hold anything on entry. The first call
+ * on a device uploads the sine table (as demod_synth_fsk's does): make one
+ * eager call before capturing.
+ *   phase    one workgroup a stream, 1 to 16 waves by the symbols a pull of
+ *            max_samples can touch, sums n inc[sym(q)] over the pull's symbols:
+ *            every thread adds up 4 consecutive symbols, a shuffle scan joins
+ *            a wave, the waves' totals meet in LDS and a running carry joins
+ *            the steps (uint32: wrap-around addition is associative, so the
+ *            grouping cannot matter); PHI is stored per symbol.
+ *   samples  one thread per 8 samples, one 16-byte store per thread; the tail
+ *            of a run whose m is not a multiple of 8 takes 2-byte stores. A
+ *            thread reads PHI from d_work and its symbols from the ring.
+ *   state    one thread a stream; last, because the other two read the state it
+ *            replaces.
+ * d_pcm is [S][max_samples], 16-byte aligned. Written: samples x < m of each
+ * stream, every byte of d_state, the one ring byte above where the tail is
+ * raised; nothing else outside d_work. Returns DEMOD_OK
+ * once enqueued; DEMOD_BAD_ARG, before any launch, for what demod_tx_sizes
+ * refuses, a NULL handle or pointer, work_bytes below
+ * demod_tx_modulate_workspace_size, or a misaligned d_pcm (16 bytes), d_state
+ * (8 bytes), d_count or d_work (4 bytes).
+ */
+int demod_tx_modulate_async(demod_t *st, const demod_tx_cfg_t *txcfg, demod_tx_stream_state_t *d_state,
+                            uint8_t *d_ring, const uint32_t *d_count, size_t n_streams,
+                            int16_t *d_pcm, void *d_work, size_t work_bytes, void *stream);
+
+/* The transmitter handle: n_streams streams of one configuration and one frame
+ * format; it owns the ring, the states, a detector handle for its stream and
+ * device, and pinned staging. NULL on failure, *error set (what demod_tx_sizes
+ * and demod_create refuse; DEMOD_NO_DEVICE, DEMOD_DEVICE_ERROR). cfg's
+ * channels, channel_mode, lead_in and method must be valid, as for any handle,
+ * but do not shape the signal: the output is mono. */
+typedef struct demod_tx demod_tx_t;
+demod_tx_t *demod_tx_create(const demod_cfg_t *cfg, const demod_tx_cfg_t *txcfg, size_t n_streams,
+                            int *error);
+void demod_tx_destroy(demod_tx_t *tx);
+
+/* Zeroes the stream's state: what it had queued is lost, other streams are
+ * untouched. */
+int demod_tx_reset(demod_tx_t *tx, size_t stream);
+
+/* The stream's state after the last send or pull (all 0 after create or reset). */
+int demod_tx_state(const demod_tx_t *tx, size_t stream, demod_tx_stream_state_t *state);
+
+/* The handle's device buffers, for callers that chain device stages behind a
+ * pull: the [S][max_samples] samples of the last pull (*d_pcm) and the ring.
+ * Either pointer may be NULL. */
+int demod_tx_device_buffers(demod_tx_t *tx, const int16_t **d_pcm, const uint8_t **d_ring);
+
+/*
+ * Queues n frames. frames[0 .. n) is a dense list of demod_rx_frame_t, exactly
+ * what demod_rx_push returns: stream, length and body (the offset of the data
+ * in bodies[0 .. n_bytes)) are read, in any stream order. The host groups the
+ * list stably by stream, one H2D copy takes counts, records and bytes in,
+ * demod_tx_encode_async runs, and one D2H copy brings the places and the
+ * states back; place[i] (when place is not NULL) is frame i's, in input order.
+ * Returns the number accepted or a negative code. DEMOD_BAD_ARG, with nothing
+ * queued, for a NULL handle or (with n > 0) frames, more than max_frames frames
+ * for one stream, a stream >= S, or body + length > n_bytes; a length above
+ * max_len is not a refusal (its place says DEMOD_TX_BAD_LENGTH).
+ */
+int demod_tx_send(demod_tx_t *tx, const demod_rx_frame_t *frames, size_t n, const uint8_t *bodies,
+                  size_t n_bytes, demod_tx_place_t *place);
+
+/*
+ * The next n_frames[s] mono samples of every stream into pcm[s] (which may be
+ * NULL where n_frames[s] == 0): the counts go in, demod_tx_modulate_async runs,
+ * one D2H copy brings the samples and the states back. Returns the total
+ * number of samples or a negative code; DEMOD_BAD_ARG, with nothing produced,
+ * for a NULL pointer or n_frames[s] > max_samples.
+ */
+long long demod_tx_pull(demod_tx_t *tx, const size_t *n_frames, int16_t *const *pcm);
+
 /* ---- many streams over many GPUs (config 5), RCCL ---------------------- */
 /*
  * A group of `world` ranks, one per GPU, demodulating n_streams streams of one
