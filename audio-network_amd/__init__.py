@@ -155,10 +155,16 @@ class DemodAcquireResult(ctypes.Structure):
     ]
 
 
+def _struct_dict(x: ctypes.Structure) -> dict:
+    """The fields of a ctypes structure by name, in the structure's order
+    (integers and doubles come out as Python's own)."""
+    return {f: getattr(x, f) for f, _ in x._fields_}
+
+
 def acquire_result_dict(r: "DemodAcquireResult") -> dict:
     """The fields of a DemodAcquireResult; `metric` as float64 [phases]."""
-    out = {f: int(getattr(r, f)) for f, _ in DemodAcquireResult._fields_ if f != "metric"}
-    out["metric"] = np.array(r.metric[:r.phases], np.float64)
+    out = _struct_dict(r)
+    out["metric"] = np.array(out.pop("metric")[:r.phases], np.float64)
     return out
 
 
@@ -180,13 +186,13 @@ class DemodFramesResult(ctypes.Structure):
     ]
 
 
-FRAME_HIT_DTYPE = np.dtype([("window", "<u8"), ("errors", "<u4"), ("reserved", "<u4")])   # DemodFrameHit
+FRAME_HIT_DTYPE = np.dtype(DemodFrameHit)
 
 
 def frames_result_dict(r: "DemodFramesResult") -> dict:
     """The fields of a DemodFramesResult; `metric` as float64 [phases]."""
-    out = {f: int(getattr(r, f)) for f, _ in DemodFramesResult._fields_ if f != "metric"}
-    out["metric"] = np.array(r.metric[:r.phases], np.float64)
+    out = _struct_dict(r)
+    out["metric"] = np.array(out.pop("metric")[:r.phases], np.float64)
     return out
 
 
@@ -211,10 +217,8 @@ class DemodFramesCheckResult(ctypes.Structure):
                 ("reserved", ctypes.c_uint64)]
 
 
-FRAME_CHECK_DTYPE = np.dtype([("length", "<u4"), ("crc", "<u4"), ("status", "<u4"),
-                              ("covered", "<u4")])                                        # DemodFrameCheck
-FRAMES_CHECK_RESULT_DTYPE = np.dtype([("n_checked", "<u8"), ("n_valid", "<u8"), ("n_kept", "<u8"),
-                                      ("reserved", "<u8")])                     # DemodFramesCheckResult
+FRAME_CHECK_DTYPE = np.dtype(DemodFrameCheck)
+FRAMES_CHECK_RESULT_DTYPE = np.dtype(DemodFramesCheckResult)
 
 
 DEMOD_FEC_CONV_K7 = 1
@@ -230,8 +234,7 @@ class DemodFrameDecode(ctypes.Structure):
                 ("steps", ctypes.c_uint32)]
 
 
-FRAME_DECODE_DTYPE = np.dtype([("length", "<u4"), ("metric", "<i4"), ("status", "<u4"),
-                               ("steps", "<u4")])                                         # DemodFrameDecode
+FRAME_DECODE_DTYPE = np.dtype(DemodFrameDecode)
 
 
 class DemodRxCfg(ctypes.Structure):
@@ -268,12 +271,9 @@ class DemodRxSizes(ctypes.Structure):
         "collect_work_bytes", "frames_bytes", "bodies_bytes")]
 
 
-RX_FRAME_DTYPE = np.dtype([("stream", "<u4"), ("length", "<u4"), ("window", "<u8"), ("body", "<u8"),
-                           ("errors", "<u4"), ("reserved", "<u4")])                       # DemodRxFrame
-RX_STATE_DTYPE = np.dtype([("base", "<u8"), ("hold", "<u8"), ("dropped", "<u8"), ("cut_hits", "<u8"),
-                           ("fill", "<u4"), ("keep", "<u4")])                             # DemodRxStreamState
-RX_SUMMARY_DTYPE = np.dtype([("n_frames", "<u8"), ("n_bytes", "<u8"), ("n_checked", "<u8"),
-                             ("n_valid", "<u8")])                                         # DemodRxSummary
+RX_FRAME_DTYPE = np.dtype(DemodRxFrame)
+RX_STATE_DTYPE = np.dtype(DemodRxStreamState)
+RX_SUMMARY_DTYPE = np.dtype(DemodRxSummary)
 
 
 class DemodTxCfg(ctypes.Structure):
@@ -305,10 +305,9 @@ class DemodTxSizes(ctypes.Structure):
         "pcm_bytes", "modulate_work_bytes")]
 
 
-TX_STATE_DTYPE = np.dtype([("head", "<u8"), ("tail", "<u8"), ("accepted", "<u8"), ("refused", "<u8"),
-                           ("offset", "<u4"), ("phase", "<u4")])                          # DemodTxStreamState
+TX_STATE_DTYPE = np.dtype(DemodTxStreamState)
 TX_RECORD_DTYPE = np.dtype([("length", "<u4"), ("body", "<u4")])                         # demod_tx_record_t
-TX_PLACE_DTYPE = np.dtype([("start", "<u8"), ("symbols", "<u4"), ("status", "<u4")])     # DemodTxPlace
+TX_PLACE_DTYPE = np.dtype(DemodTxPlace)
 DEMOD_TX_OK, DEMOD_TX_BAD_LENGTH, DEMOD_TX_NO_ROOM = 0, 1, 2
 
 
@@ -563,7 +562,7 @@ def error_model(cfg: DemodCfg) -> dict:
     rc = load_library().demod_error_model(ctypes.byref(cfg), ctypes.byref(m))
     if rc != DEMOD_OK:
         raise DemodError(rc, "demod_error_model")
-    return {f: getattr(m, f) for f, _ in DemodErrorModel._fields_}
+    return _struct_dict(m)
 
 
 def plan_info(cfg: DemodCfg) -> dict:
@@ -580,7 +579,7 @@ def plan_info(cfg: DemodCfg) -> dict:
                              _ptr(rot64), rot64.size)
     if rc != DEMOD_OK:
         raise DemodError(rc, "demod_plan_info")
-    out = {f: getattr(info, f) for f, _ in DemodPlanInfo._fields_}
+    out = _struct_dict(info)
     for f in ("slot_tone", "zcls", "fft_bins", "coef", "sgn", "rcoef"):
         out[f] = np.array(out[f][:cfg.k])
     out["coef"] = out["coef"].astype(np.float32)
@@ -590,14 +589,23 @@ def plan_info(cfg: DemodCfg) -> dict:
     return out
 
 
+def _size(name: str, cfg: DemodCfg, *counts: int, also: tuple = ()) -> int:
+    """The size_t the library's function `name` reports for cfg (then `also`:
+    further structures by reference) and the counts; a negative count or a
+    reported 0 raises DemodError(DEMOD_BAD_ARG, name)."""
+    size = 0
+    if min(counts, default=0) >= 0:
+        size = int(getattr(load_library(), name)(ctypes.byref(cfg), *also, *(int(c) for c in counts)))
+    if size == 0:
+        raise DemodError(DEMOD_BAD_ARG, name)
+    return size
+
+
 def acquire_workspace_size(cfg: DemodCfg) -> int:
     """demod_acquire_workspace_size: bytes of d_work an acquisition of cfg needs
     (no GPU). Raises DemodError(DEMOD_BAD_ARG) where the configuration has no
     acquisition (n % hop != 0, more than DEMOD_MAX_PHASES phases)."""
-    size = int(load_library().demod_acquire_workspace_size(ctypes.byref(cfg)))
-    if size == 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_acquire_workspace_size")
-    return size
+    return _size("demod_acquire_workspace_size", cfg)
 
 
 def acquire_segments_workspace_size(cfg: DemodCfg, max_segments: int, max_windows: int) -> int:
@@ -606,13 +614,7 @@ def acquire_segments_workspace_size(cfg: DemodCfg, max_segments: int, max_window
     windows needs (no GPU); monotone in both. Raises DemodError(DEMOD_BAD_ARG)
     where it is 0 (no acquisition for cfg, max_segments not in 1 ..
     DEMOD_MAX_SEGMENTS, max_windows >= 2^31)."""
-    if max_segments < 0 or max_windows < 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_acquire_segments_workspace_size")
-    size = int(load_library().demod_acquire_segments_workspace_size(ctypes.byref(cfg), int(max_segments),
-                                                                   int(max_windows)))
-    if size == 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_acquire_segments_workspace_size")
-    return size
+    return _size("demod_acquire_segments_workspace_size", cfg, max_segments, max_windows)
 
 
 def frames_workspace_size(cfg: DemodCfg, max_windows: int) -> int:
@@ -620,12 +622,7 @@ def frames_workspace_size(cfg: DemodCfg, max_windows: int) -> int:
     max_windows windows needs (no GPU); monotone in max_windows. Raises
     DemodError(DEMOD_BAD_ARG) where it is 0 (no acquisition for cfg,
     max_windows >= 2^31)."""
-    if max_windows < 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_frames_workspace_size")
-    size = int(load_library().demod_frames_workspace_size(ctypes.byref(cfg), int(max_windows)))
-    if size == 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_frames_workspace_size")
-    return size
+    return _size("demod_frames_workspace_size", cfg, max_windows)
 
 
 def frames_segments_workspace_size(cfg: DemodCfg, max_segments: int, max_windows: int) -> int:
@@ -634,13 +631,7 @@ def frames_segments_workspace_size(cfg: DemodCfg, max_segments: int, max_windows
     windows needs (no GPU); monotone in both. Raises DemodError(DEMOD_BAD_ARG)
     where it is 0 (no acquisition for cfg, max_segments not in 1 ..
     DEMOD_MAX_SEGMENTS, max_windows >= 2^31)."""
-    if max_segments < 0 or max_windows < 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_frames_segments_workspace_size")
-    size = int(load_library().demod_frames_segments_workspace_size(ctypes.byref(cfg), int(max_segments),
-                                                                  int(max_windows)))
-    if size == 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_frames_segments_workspace_size")
-    return size
+    return _size("demod_frames_segments_workspace_size", cfg, max_segments, max_windows)
 
 
 def segments_layout(cfg: DemodCfg, n_samples):
@@ -667,13 +658,7 @@ def frames_decode_workspace_size(cfg: DemodCfg, n_groups: int, max_frames: int, 
     """demod_frames_decode_workspace_size: bytes of d_work a decode of n_groups
     x max_frames rows of frame_symbols symbols needs (no GPU). Raises
     DemodError(DEMOD_BAD_ARG) where it is 0."""
-    if n_groups < 0 or max_frames < 0 or frame_symbols < 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_frames_decode_workspace_size")
-    size = int(load_library().demod_frames_decode_workspace_size(ctypes.byref(cfg), int(n_groups),
-                                                                int(max_frames), int(frame_symbols)))
-    if size == 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_frames_decode_workspace_size")
-    return size
+    return _size("demod_frames_decode_workspace_size", cfg, n_groups, max_frames, frame_symbols)
 
 
 def make_rx_cfg(sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
@@ -706,7 +691,7 @@ def rx_sizes(cfg: DemodCfg, rxcfg: DemodRxCfg, n_streams: int) -> dict:
     rc = load_library().demod_rx_sizes(ctypes.byref(cfg), ctypes.byref(rxcfg), int(n_streams), ctypes.byref(out))
     if rc != DEMOD_OK:
         raise DemodError(rc, "demod_rx_sizes")
-    return {f: int(getattr(out, f)) for f, _ in DemodRxSizes._fields_}
+    return _struct_dict(out)
 
 
 def make_tx_cfg(sync, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE, fec: int = 0, max_len: int = 0,
@@ -738,17 +723,13 @@ def tx_sizes(cfg: DemodCfg, txcfg: DemodTxCfg, n_streams: int) -> dict:
     rc = load_library().demod_tx_sizes(ctypes.byref(cfg), ctypes.byref(txcfg), int(n_streams), ctypes.byref(out))
     if rc < 0:
         raise DemodError(rc, "demod_tx_sizes")
-    return {f: int(getattr(out, f)) for f, _ in DemodTxSizes._fields_}
+    return _struct_dict(out)
 
 
 def tx_modulate_workspace_size(cfg: DemodCfg, txcfg: DemodTxCfg, n_streams: int) -> int:
     """demod_tx_modulate_workspace_size (no GPU). Raises DemodError(DEMOD_BAD_ARG)
     where the C function reports 0."""
-    size = int(load_library().demod_tx_modulate_workspace_size(
-        ctypes.byref(cfg), ctypes.byref(txcfg), int(n_streams))) if n_streams >= 0 else 0
-    if size == 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_tx_modulate_workspace_size")
-    return size
+    return _size("demod_tx_modulate_workspace_size", cfg, n_streams, also=(ctypes.byref(txcfg),))
 
 
 def tx_frame_symbol_count(txcfg: DemodTxCfg, k: int, length: int) -> int:
@@ -778,11 +759,7 @@ def tx_frame_symbols(txcfg: DemodTxCfg, k: int, data: bytes) -> np.ndarray:
 def rx_collect_workspace_size(cfg: DemodCfg, n_streams: int) -> int:
     """demod_rx_collect_workspace_size (no GPU). Raises DemodError(DEMOD_BAD_ARG)
     where it is 0."""
-    size = int(load_library().demod_rx_collect_workspace_size(ctypes.byref(cfg), int(n_streams))) \
-        if n_streams >= 0 else 0
-    if size == 0:
-        raise DemodError(DEMOD_BAD_ARG, "demod_rx_collect_workspace_size")
-    return size
+    return _size("demod_rx_collect_workspace_size", cfg, n_streams)
 
 
 def _ptr(a) -> int:
@@ -820,8 +797,64 @@ def _check_dev(t, what: str, dtype: str, min_numel: int, device: Optional[int] =
         raise DemodError(DEMOD_BAD_ARG, f"{what}: {t.numel()} elements, need >= {min_numel}")
 
 
-class Demodulator:
+class _Handle:
+    """The lifetime of a library handle: `_h` of `_lib`, given back once to the
+    function `_destroy` names. `_h` may be unset (an __init__ that raised)."""
+    _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _aligned16(flat: np.ndarray) -> np.ndarray:
+    """flat (int16, 1-D, contiguous) itself where it starts on a 16-byte
+    boundary, else a copy that does."""
+    if flat.ctypes.data % 16:
+        buf = np.empty(flat.size + 8, dtype=np.int16)
+        off = (-buf.ctypes.data % 16) // 2
+        buf = buf[off:off + flat.size]
+        buf[:] = flat
+        return buf
+    return flat
+
+
+def _segment_tables(first, count) -> Tuple[np.ndarray, np.ndarray]:
+    """A host segment table as the library reads it: first uint64 [S], count
+    uint32 [S], S >= 1."""
+    first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+    count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
+    if first.size != count.size or first.size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "first and count: one entry per segment, at least one")
+    return first, count
+
+
+def _rows_shape(n_groups: int, max_frames: int, frame_symbols: int, what: str) -> Tuple[int, int, int]:
+    """(S, cap, N) of a scan's S x cap rows of N symbols, refused as the
+    library refuses them; `what` names the group count in the message."""
+    S, cap, N = int(n_groups), int(max_frames), int(frame_symbols)
+    if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31:
+        raise DemodError(DEMOD_BAD_ARG, f"{what} not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
+                                        f"frame_symbols < 0 or {what} * max_frames >= 2^31")
+    return S, cap, N
+
+
+class Demodulator(_Handle):
     """One demod_t handle (not thread-safe within a handle, like libopus)."""
+    _destroy = "demod_destroy"
 
     def __init__(self, cfg: Optional[DemodCfg] = None, **kw):
         self._lib = load_library()
@@ -843,23 +876,6 @@ class Demodulator:
     @property
     def hop(self) -> int:
         return int(self.cfg.hop)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.demod_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self) -> None:
         rc = self._lib.demod_reset(self._h)
@@ -923,12 +939,7 @@ class Demodulator:
                 n_windows = 0 if flat.size < self.n else (flat.size - self.n) // self.hop + 1
         if n_windows and (n_windows - 1) * self.hop + self.n > flat.size:
             raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
-        buf = flat
-        if flat.ctypes.data % 16:
-            buf = np.empty(flat.size + 8, dtype=np.int16)
-            off = (-buf.ctypes.data % 16) // 2
-            buf = buf[off:off + flat.size]
-            buf[:] = flat
+        buf = _aligned16(flat)
         sym = np.empty(max(n_windows, 1), dtype=np.uint8)
         mag = np.empty((max(n_windows, 1), self.k), dtype=np.float32) if mags else None
         rc = self._lib.demod_batch(self._h, _ptr(buf), n_windows, _ptr(sym), _ptr(mag))
@@ -976,11 +987,10 @@ class Demodulator:
             raise DemodError(rc, "demod_batch_spectrum_async")
         return rc
 
-    def acquire(self, pcm, n_windows: Optional[int] = None, sync=None, max_errors: int = 0,
-                cap: Optional[int] = None):
-        """demod_acquire: the detector over the sliding windows of pcm (a host
-        int16 array or a device tensor), then symbol timing and the sync word.
-        Returns (symbols after the word at the symbol rate, result dict)."""
+    def _stage(self, pcm, n_windows: Optional[int] = None):
+        """(buf, n_windows) of a call that takes the sliding windows of pcm: a
+        host int16 array, flat and copied where it does not start on a 16-byte
+        boundary, or a device tensor, checked. n_windows None: all that fit."""
         host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
         if host:
             flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
@@ -994,15 +1004,16 @@ class Demodulator:
         if host:
             if need > size:
                 raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
-            buf = flat
-            if flat.ctypes.data % 16:
-                buf = np.empty(flat.size + 8, dtype=np.int16)
-                off = (-buf.ctypes.data % 16) // 2
-                buf = buf[off:off + flat.size]
-                buf[:] = flat
-        else:
-            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
-            buf = pcm
+            return _aligned16(flat), n_windows
+        _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
+        return pcm, n_windows
+
+    def acquire(self, pcm, n_windows: Optional[int] = None, sync=None, max_errors: int = 0,
+                cap: Optional[int] = None):
+        """demod_acquire: the detector over the sliding windows of pcm (a host
+        int16 array or a device tensor), then symbol timing and the sync word.
+        Returns (symbols after the word at the symbol rate, result dict)."""
+        buf, n_windows = self._stage(pcm, n_windows)
         sync = _sync_bytes(sync)
         if cap is None:
             cap = n_windows // max(self.n // self.hop, 1) + 1
@@ -1047,32 +1058,8 @@ class Demodulator:
         segment first[s] .. first[s] + count[s] - 1 as a batch of its own.
         Returns (out uint8 [S][cap], row s valid up to its n_written and 0xFF
         after it; [result dict per segment])."""
-        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
-        if host:
-            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
-            size = flat.size
-        else:
-            size = int(pcm.numel())
-        if n_windows is None:
-            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
-        n_windows = int(n_windows)
-        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
-        if host:
-            if need > size:
-                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
-            buf = flat
-            if flat.ctypes.data % 16:
-                buf = np.empty(flat.size + 8, dtype=np.int16)
-                off = (-buf.ctypes.data % 16) // 2
-                buf = buf[off:off + flat.size]
-                buf[:] = flat
-        else:
-            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
-            buf = pcm
-        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
-        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
-        if first.size != count.size or first.size == 0:
-            raise DemodError(DEMOD_BAD_ARG, "first and count: one entry per segment, at least one")
+        buf, n_windows = self._stage(pcm, n_windows)
+        first, count = _segment_tables(first, count)
         S = first.size
         sync = _sync_bytes(sync)
         if cap is None:
@@ -1131,28 +1118,7 @@ class Demodulator:
         FRAME_HIT_DTYPE array [n_written], payload uint8 [n_written][N] or None,
         packed uint8 [n_written][ceil(N bits / 8)] or None, result dict).
         Overlapping hits are all listed (include/demod.h "frame scan")."""
-        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
-        if host:
-            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
-            size = flat.size
-        else:
-            size = int(pcm.numel())
-        if n_windows is None:
-            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
-        n_windows = int(n_windows)
-        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
-        if host:
-            if need > size:
-                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
-            buf = flat
-            if flat.ctypes.data % 16:
-                buf = np.empty(flat.size + 8, dtype=np.int16)
-                off = (-buf.ctypes.data % 16) // 2
-                buf = buf[off:off + flat.size]
-                buf[:] = flat
-        else:
-            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
-            buf = pcm
+        buf, n_windows = self._stage(pcm, n_windows)
         sync = _sync_bytes(sync)
         N = int(frame_symbols)
         if N < 0 or (max_frames is not None and max_frames < 0):
@@ -1216,32 +1182,8 @@ class Demodulator:
         [n_written][N] or None, packed uint8 [n_written][ceil(N bits / 8)] or
         None, result dict) per segment; a hit's window is relative to its
         segment's first window."""
-        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
-        if host:
-            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
-            size = flat.size
-        else:
-            size = int(pcm.numel())
-        if n_windows is None:
-            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
-        n_windows = int(n_windows)
-        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
-        if host:
-            if need > size:
-                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
-            buf = flat
-            if flat.ctypes.data % 16:
-                buf = np.empty(flat.size + 8, dtype=np.int16)
-                off = (-buf.ctypes.data % 16) // 2
-                buf = buf[off:off + flat.size]
-                buf[:] = flat
-        else:
-            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
-            buf = pcm
-        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
-        count = np.ascontiguousarray(count, dtype=np.uint32).reshape(-1)
-        if first.size != count.size or first.size == 0:
-            raise DemodError(DEMOD_BAD_ARG, "first and count: one entry per segment, at least one")
+        buf, n_windows = self._stage(pcm, n_windows)
+        first, count = _segment_tables(first, count)
         S = first.size
         sync = _sync_bytes(sync)
         N = int(frame_symbols)
@@ -1310,16 +1252,45 @@ class Demodulator:
         if rc < 0:
             raise DemodError(rc, "demod_frames_segments_async")
 
-    def _checked_shape(self, frame_symbols: int, len_bytes: int, crc: int) -> Tuple[int, int]:
-        """(B, max_len) of a checked frame on rows of frame_symbols symbols."""
+    def _frame_shape(self, frame_symbols: int, len_bytes: int, crc: int, fec: int) -> Tuple[int, int]:
+        """(row bytes, max_len) of rows of frame_symbols symbols: B of a checked
+        frame's packed rows (fec 0), Bd of a coded frame's decoded rows
+        (DEMOD_FEC_CONV_K7, of St trellis steps)."""
         if len_bytes not in (1, 2) or crc not in CRC_BYTES:
             raise DemodError(DEMOD_BAD_ARG, "len_bytes not 1 or 2, or an unknown crc kind")
-        B = (int(frame_symbols) * bits_per_symbol(self.k) + 7) // 8
+        bits = bits_per_symbol(self.k)
+        if fec:
+            if self.k != 1 << bits:
+                raise DemodError(DEMOD_BAD_ARG, "coded frames need K = 2^bits tones")
+            St = int(frame_symbols) * bits // 2
+            if St < 8 * len_bytes + DEMOD_FEC_DEPTH:
+                raise DemodError(DEMOD_BAD_ARG, "rows shorter than the header look-ahead")
+            B, short = (St - 6) // 8, ""
+        else:
+            B, short = (int(frame_symbols) * bits + 7) // 8, "rows too short for header and CRC, or "
         max_len = B - len_bytes - CRC_BYTES[crc]
         if max_len < 0 or max_len > DEMOD_MAX_FRAME_PAYLOAD:
-            raise DemodError(DEMOD_BAD_ARG, "rows too short for header and CRC, or max_len above "
-                                            "DEMOD_MAX_FRAME_PAYLOAD")
+            raise DemodError(DEMOD_BAD_ARG, short + "max_len above DEMOD_MAX_FRAME_PAYLOAD")
         return B, max_len
+
+    def _check_scan_outputs(self, S: int, cap: int, max_len: int, d_hits, d_results, d_check, d_kept, d_body,
+                            d_summary, rows: Optional[tuple] = None, collect: bool = False) -> None:
+        """The device tensors of a scan of S x cap rows and of its check, in
+        the callers' argument order. rows: (tensor, its name, bytes a row) of
+        the rows a check reads, between d_hits and d_results. collect: the
+        collect step's view, d_body required and the check's summary named
+        d_check_summary."""
+        dev = int(self.cfg.device)
+        n = S * cap
+        _check_dev(d_hits, "d_hits", "uint8", n * ctypes.sizeof(DemodFrameHit), dev)
+        if rows is not None:
+            _check_dev(rows[0], rows[1], "uint8", n * rows[2], dev)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_check, "d_check", "uint8", n * ctypes.sizeof(DemodFrameCheck), dev)
+        _check_dev(d_kept, "d_kept", "int32", n, dev)
+        _check_dev(d_body, "d_body", "uint8", n * max_len, dev, nullable=not collect)
+        _check_dev(d_summary, "d_check_summary" if collect else "d_summary", "uint8",
+                   S * ctypes.sizeof(DemodFramesCheckResult), dev)
 
     def frames_check_async(self, d_hits, d_packed, d_results, n_groups: int, max_frames: int,
                            sync_len: int, frame_symbols: int, len_bytes: int, crc: int, d_check, d_kept,
@@ -1333,42 +1304,16 @@ class Demodulator:
         max_frames * max_len bytes, or None) and d_summary (uint8, n_groups *
         sizeof(DemodFramesCheckResult) bytes) are written. Device tensors,
         checked like the batch calls' (dtype, contiguity, device, size)."""
-        S, cap, L, N = int(n_groups), int(max_frames), int(sync_len), int(frame_symbols)
-        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31:
-            raise DemodError(DEMOD_BAD_ARG, "n_groups not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
-                                            "frame_symbols < 0 or n_groups * max_frames >= 2^31")
-        B, max_len = self._checked_shape(N, len_bytes, crc)
-        dev = int(self.cfg.device)
-        rows = S * cap
-        _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
-        _check_dev(d_packed, "d_packed", "uint8", rows * B, dev)
-        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
-        _check_dev(d_check, "d_check", "uint8", rows * ctypes.sizeof(DemodFrameCheck), dev)
-        _check_dev(d_kept, "d_kept", "int32", rows, dev)
-        _check_dev(d_body, "d_body", "uint8", rows * max_len, dev, nullable=True)
-        _check_dev(d_summary, "d_summary", "uint8", S * ctypes.sizeof(DemodFramesCheckResult), dev)
+        S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
+        B, max_len = self._frame_shape(N, len_bytes, crc, 0)
+        self._check_scan_outputs(S, cap, max_len, d_hits, d_results, d_check, d_kept, d_body, d_summary,
+                                 rows=(d_packed, "d_packed", B))
         rc = self._lib.demod_frames_check_async(
-            self._h, _ptr(d_hits), _ptr(d_packed), _ptr(d_results), S, cap, L, N, int(len_bytes), int(crc),
-            _ptr(d_check), _ptr(d_kept), _ptr(d_body) if d_body is not None else None, _ptr(d_summary),
-            stream or None)
+            self._h, _ptr(d_hits), _ptr(d_packed), _ptr(d_results), S, cap, int(sync_len), N, int(len_bytes),
+            int(crc), _ptr(d_check), _ptr(d_kept), _ptr(d_body) if d_body is not None else None,
+            _ptr(d_summary), stream or None)
         if rc < 0:
             raise DemodError(rc, "demod_frames_check_async")
-
-    def _coded_shape(self, frame_symbols: int, len_bytes: int, crc: int) -> Tuple[int, int, int]:
-        """(St, Bd, max_len) of coded rows of frame_symbols symbols."""
-        if len_bytes not in (1, 2) or crc not in CRC_BYTES:
-            raise DemodError(DEMOD_BAD_ARG, "len_bytes not 1 or 2, or an unknown crc kind")
-        bits = bits_per_symbol(self.k)
-        if self.k != 1 << bits:
-            raise DemodError(DEMOD_BAD_ARG, "coded frames need K = 2^bits tones")
-        St = int(frame_symbols) * bits // 2
-        if St < 8 * len_bytes + DEMOD_FEC_DEPTH:
-            raise DemodError(DEMOD_BAD_ARG, "rows shorter than the header look-ahead")
-        Bd = (St - 6) // 8
-        max_len = Bd - len_bytes - CRC_BYTES[crc]
-        if max_len < 0 or max_len > DEMOD_MAX_FRAME_PAYLOAD:
-            raise DemodError(DEMOD_BAD_ARG, "max_len above DEMOD_MAX_FRAME_PAYLOAD")
-        return St, Bd, max_len
 
     def frames_decode_async(self, d_hits, d_mag, n_windows: int, d_first, d_results, n_groups: int,
                             max_frames: int, sync_len: int, frame_symbols: int, len_bytes: int, crc: int,
@@ -1381,14 +1326,13 @@ class Demodulator:
         max_frames * Bd bytes) and d_decode (uint8, 16 bytes a row) are
         written; d_work (uint8, at least frames_decode_workspace_size bytes)
         may hold anything. Device tensors, checked like the batch calls'."""
-        W, S, cap, L, N = int(n_windows), int(n_groups), int(max_frames), int(sync_len), int(frame_symbols)
-        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31 or W < 0 or W >= 2 ** 31:
-            raise DemodError(DEMOD_BAD_ARG, "n_groups not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
-                                            "frame_symbols < 0, n_groups * max_frames >= 2^31 or "
-                                            "n_windows not in 0 .. 2^31 - 1")
+        S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
+        W, L = int(n_windows), int(sync_len)
+        if W < 0 or W >= 2 ** 31:
+            raise DemodError(DEMOD_BAD_ARG, "n_windows not in 0 .. 2^31 - 1")
         if fec != DEMOD_FEC_CONV_K7:
             raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
-        _, Bd, _ = self._coded_shape(N, len_bytes, crc)
+        Bd, _ = self._frame_shape(N, len_bytes, crc, fec)
         dev = int(self.cfg.device)
         rows = S * cap
         _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
@@ -1411,25 +1355,15 @@ class Demodulator:
         """demod_frames_check_coded_async: frames_check_async over the rows
         frames_decode_async wrote (uint8, n_groups * max_frames * Bd bytes),
         with max_len = Bd - len_bytes - the CRC's bytes and the coded span."""
-        S, cap, L, N = int(n_groups), int(max_frames), int(sync_len), int(frame_symbols)
-        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31:
-            raise DemodError(DEMOD_BAD_ARG, "n_groups not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
-                                            "frame_symbols < 0 or n_groups * max_frames >= 2^31")
+        S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
         if fec != DEMOD_FEC_CONV_K7:
             raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
-        _, Bd, max_len = self._coded_shape(N, len_bytes, crc)
-        dev = int(self.cfg.device)
-        rows = S * cap
-        _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
-        _check_dev(d_rows, "d_rows", "uint8", rows * Bd, dev)
-        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
-        _check_dev(d_check, "d_check", "uint8", rows * ctypes.sizeof(DemodFrameCheck), dev)
-        _check_dev(d_kept, "d_kept", "int32", rows, dev)
-        _check_dev(d_body, "d_body", "uint8", rows * max_len, dev, nullable=True)
-        _check_dev(d_summary, "d_summary", "uint8", S * ctypes.sizeof(DemodFramesCheckResult), dev)
+        Bd, max_len = self._frame_shape(N, len_bytes, crc, fec)
+        self._check_scan_outputs(S, cap, max_len, d_hits, d_results, d_check, d_kept, d_body, d_summary,
+                                 rows=(d_rows, "d_rows", Bd))
         rc = self._lib.demod_frames_check_coded_async(
-            self._h, _ptr(d_hits), _ptr(d_rows), _ptr(d_results), S, cap, L, N, int(len_bytes), int(crc),
-            int(fec), _ptr(d_check), _ptr(d_kept), _ptr(d_body) if d_body is not None else None,
+            self._h, _ptr(d_hits), _ptr(d_rows), _ptr(d_results), S, cap, int(sync_len), N, int(len_bytes),
+            int(crc), int(fec), _ptr(d_check), _ptr(d_kept), _ptr(d_body) if d_body is not None else None,
             _ptr(d_summary), stream or None)
         if rc < 0:
             raise DemodError(rc, "demod_frames_check_coded_async")
@@ -1480,22 +1414,16 @@ class Demodulator:
         d_state are written; d_work (uint8, at least rx_collect_workspace_size
         bytes) may hold anything. Device tensors, checked like the batch
         calls'."""
-        S, cap, L, N = int(n_streams), int(max_frames), int(sync_len), int(frame_symbols)
-        if S < 1 or S > DEMOD_MAX_SEGMENTS or cap < 1 or N < 0 or S * cap >= 2 ** 31:
-            raise DemodError(DEMOD_BAD_ARG, "n_streams not in 1 .. DEMOD_MAX_SEGMENTS, max_frames < 1, "
-                                            "frame_symbols < 0 or n_streams * max_frames >= 2^31")
+        S, cap, N = _rows_shape(n_streams, max_frames, frame_symbols, "n_streams")
+        L = int(sync_len)
         if fec not in (0, DEMOD_FEC_CONV_K7):
             raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
-        max_len = self._coded_shape(N, len_bytes, crc)[2] if fec else self._checked_shape(N, len_bytes, crc)[1]
+        _, max_len = self._frame_shape(N, len_bytes, crc, fec)
         dev = int(self.cfg.device)
         rows = S * cap
         _check_dev(d_state, "d_state", "uint8", S * ctypes.sizeof(DemodRxStreamState), dev)
-        _check_dev(d_hits, "d_hits", "uint8", rows * ctypes.sizeof(DemodFrameHit), dev)
-        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
-        _check_dev(d_check, "d_check", "uint8", rows * ctypes.sizeof(DemodFrameCheck), dev)
-        _check_dev(d_kept, "d_kept", "int32", rows, dev)
-        _check_dev(d_body, "d_body", "uint8", rows * max_len, dev)
-        _check_dev(d_check_summary, "d_check_summary", "uint8", S * ctypes.sizeof(DemodFramesCheckResult), dev)
+        self._check_scan_outputs(S, cap, max_len, d_hits, d_results, d_check, d_kept, d_body, d_check_summary,
+                                 collect=True)
         _check_dev(d_frames, "d_frames", "uint8", rows * ctypes.sizeof(DemodRxFrame), dev)
         _check_dev(d_bodies, "d_bodies", "uint8", rows * max_len, dev)
         _check_dev(d_summary, "d_summary", "uint8", ctypes.sizeof(DemodRxSummary), dev)
@@ -1582,33 +1510,12 @@ class Demodulator:
     def _frames_checked(self, pcm, sync, max_errors, frame_symbols, len_bytes, crc, fec, max_frames,
                         n_windows, body):
         """frames_checked (fec 0) and frames_coded."""
-        host = isinstance(pcm, np.ndarray) or not hasattr(pcm, "data_ptr")
-        if host:
-            flat = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
-            size = flat.size
-        else:
-            size = int(pcm.numel())
-        if n_windows is None:
-            n_windows = 0 if size < self.n else (size - self.n) // self.hop + 1
-        n_windows = int(n_windows)
-        need = (n_windows - 1) * self.hop + self.n if n_windows > 0 else 0
-        if host:
-            if need > size:
-                raise DemodError(DEMOD_BAD_ARG, "pcm shorter than n_windows")
-            buf = flat
-            if flat.ctypes.data % 16:
-                buf = np.empty(flat.size + 8, dtype=np.int16)
-                off = (-buf.ctypes.data % 16) // 2
-                buf = buf[off:off + flat.size]
-                buf[:] = flat
-        else:
-            _check_dev(pcm, "pcm", "int16", need, int(self.cfg.device))
-            buf = pcm
+        buf, n_windows = self._stage(pcm, n_windows)
         sync = _sync_bytes(sync)
         N = int(frame_symbols)
         if N < 0 or (max_frames is not None and max_frames < 1):
             raise DemodError(DEMOD_BAD_ARG, "frame_symbols < 0 or max_frames < 1")
-        _, max_len = self._coded_shape(N, len_bytes, crc)[1:] if fec else self._checked_shape(N, len_bytes, crc)
+        _, max_len = self._frame_shape(N, len_bytes, crc, fec)
         if max_frames is None:
             max_frames = n_windows // max(self.n // self.hop, 1) + 1
         cap = int(max_frames)
@@ -1627,7 +1534,7 @@ class Demodulator:
         if rc < 0:
             raise DemodError(rc, "demod_frames_coded" if fec else "demod_frames_checked")
         bodies = [bytes(bod[r, :int(lengths[r])]) for r in range(rc)] if bod is not None else None
-        summary = {f: int(getattr(summ, f)) for f, _ in DemodFramesCheckResult._fields_}
+        summary = _struct_dict(summ)
         return hits[:rc], lengths[:rc], bodies, frames_result_dict(res), summary
 
 
@@ -1662,9 +1569,10 @@ def _packet_tables(packets, S: int, ch: int):
     return keep, ptrs, frames
 
 
-class Streams:
+class Streams(_Handle):
     """demod_streams_t: n_streams independent streams behind one detector,
     one batch per push (include/demod.h, "many streams, one launch")."""
+    _destroy = "demod_streams_destroy"
 
     def __init__(self, n_streams: int, cfg: Optional[DemodCfg] = None, **kw):
         self._lib = load_library()
@@ -1679,23 +1587,6 @@ class Streams:
     @property
     def k(self) -> int:
         return int(self.cfg.k)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.demod_streams_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self, stream: int) -> None:
         rc = self._lib.demod_streams_reset(self._h, int(stream))
@@ -1732,10 +1623,11 @@ class Streams:
         return out_s, [mag[e[i]:e[i + 1]] for i in range(S)]
 
 
-class Receiver:
+class Receiver(_Handle):
     """demod_rx_t: n_streams live streams in, their checked (or decoded and
     checked) frames out, the carry between packets kept on the device
     (include/demod.h "receiver")."""
+    _destroy = "demod_rx_destroy"
 
     def __init__(self, n_streams: int, rxcfg: DemodRxCfg, cfg: Optional[DemodCfg] = None, **kw):
         self._lib = load_library()
@@ -1750,23 +1642,6 @@ class Receiver:
             raise DemodError(err.value, "demod_rx_create")
         self._h = h
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.demod_rx_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self, stream: int) -> None:
         rc = self._lib.demod_rx_reset(self._h, int(stream))
         if rc < 0:
@@ -1780,7 +1655,7 @@ class Receiver:
         rc = self._lib.demod_rx_state(self._h, int(stream), ctypes.byref(st))
         if rc < 0:
             raise DemodError(rc, "demod_rx_state")
-        return {f: int(getattr(st, f)) for f, _ in DemodRxStreamState._fields_}
+        return _struct_dict(st)
 
     def push(self, packets):
         """packets as Streams.push takes them. Returns (frames: an
@@ -1793,7 +1668,7 @@ class Receiver:
         del keep
         if rc < 0:
             raise DemodError(rc, "demod_rx_push")
-        summary = {f: int(getattr(summ, f)) for f, _ in DemodRxSummary._fields_}
+        summary = _struct_dict(summ)
         rec = np.zeros(rc, RX_FRAME_DTYPE)
         if rc:
             ctypes.memmove(rec.ctypes.data, frames.value, rc * RX_FRAME_DTYPE.itemsize)
@@ -1802,10 +1677,11 @@ class Receiver:
         return rec, out, summary
 
 
-class Transmitter:
+class Transmitter(_Handle):
     """demod_tx_t: frames in, as Receiver.push hands them out, and the
     phase-continuous signal of n_streams streams out; queues and phases are
     kept on the device (include/demod.h "transmitter")."""
+    _destroy = "demod_tx_destroy"
 
     def __init__(self, n_streams: int, txcfg: DemodTxCfg, cfg: Optional[DemodCfg] = None, **kw):
         self._lib = load_library()
@@ -1820,23 +1696,6 @@ class Transmitter:
             raise DemodError(err.value, "demod_tx_create")
         self._h = h
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.demod_tx_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self, stream: int) -> None:
         rc = self._lib.demod_tx_reset(self._h, int(stream)) if stream >= 0 else DEMOD_BAD_ARG
         if rc < 0:
@@ -1850,7 +1709,7 @@ class Transmitter:
         rc = self._lib.demod_tx_state(self._h, int(stream), ctypes.byref(st))
         if rc < 0:
             raise DemodError(rc, "demod_tx_state")
-        return {f: int(getattr(st, f)) for f, _ in DemodTxStreamState._fields_}
+        return _struct_dict(st)
 
     def device_buffers(self) -> Tuple[int, int]:
         """The device addresses of the last pull's samples [S][max_samples] and of the ring."""
@@ -2091,7 +1950,7 @@ def coded_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FA
                                                  int(crc), _ptr(row), int(cap), ctypes.byref(dec))
     if rc < 0:
         raise DemodError(rc, "demod_coded_frame_decode")
-    return row[:rc].tobytes(), {f: int(getattr(dec, f)) for f, _ in DemodFrameDecode._fields_}
+    return row[:rc].tobytes(), _struct_dict(dec)
 
 
 def frame_decode(buf: bytes) -> Tuple[bytes, int]:
@@ -2303,10 +2162,11 @@ def group_block_bytes(n_streams: int, world: int, steps: int, symbols_per_stream
     return int(rc)
 
 
-class Group:
+class Group(_Handle):
     """demod_group_t: n_streams streams sharded over `world` GPUs, RCCL gathers.
     Group(cfg, n, rank=r, world=w, uid=...) is one rank of a multi-process
     group; Group(cfg, n, devices=[...]) drives every rank in this process."""
+    _destroy = "demod_group_destroy"
 
     def __init__(self, cfg: DemodCfg, n_streams: int, rank: int = 0, world: int = 1,
                  uid: Optional[bytes] = None, devices: Optional[Sequence[int]] = None):
@@ -2329,20 +2189,6 @@ class Group:
         self.channels = int(cfg.channels)
         self.world = self._lib.demod_group_world(self._h)
         self.local_ranks = self._lib.demod_group_local_ranks(self._h)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.demod_group_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        self.close()
 
     def shard(self, local: int = 0) -> Tuple[int, int, int]:
         """(rank, first stream, count) of the local-th rank this process drives."""

@@ -16,6 +16,7 @@ def test_library_exports_every_header_symbol(A):
     assert len(declared) >= 20
     for name in declared:
         assert hasattr(lib, name), name
+        assert getattr(lib, name).argtypes is not None, name  # a prototype, not ctypes' int guesses
     out = subprocess.run(["nm", "-D", "--defined-only", A.LIB_PATH], capture_output=True,
                          text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
@@ -118,6 +119,79 @@ def test_device_tensor_checks(A):
     with pytest.raises(A.DemodError):
         A.frame_streams_async(torch.zeros(10, dtype=torch.uint8), 2, 5, 1,
                               torch.zeros(1, dtype=torch.uint8))
+
+
+def test_pcm_staging(A):
+    """Demodulator._stage, the one place that turns `pcm` and the optional
+    `n_windows` into what the library reads: the default window count, the
+    16-byte alignment of host samples, the length refusal and the device check."""
+    import numpy as np
+    torch = pytest.importorskip("torch")
+    d = object.__new__(A.Demodulator)
+    d._lib, d.cfg, d._h = A.load_library(), A.make_cfg(n=1024, hop=256), None
+    n, hop = 1024, 256
+    for size, want in ((n - 1, 0), (n, 1), (n + hop - 1, 1), (n + hop, 2)):
+        assert d._stage(np.zeros(size, np.int16))[1] == want, size
+    raw = np.zeros(16 + 4096 + 16, np.int8)
+    start = -raw.ctypes.data % 16
+    rng = np.random.default_rng(3)
+    for shift, same in ((0, True), (2, False)):
+        pcm = raw[start + shift:start + shift + 2 * 2048].view(np.int16)
+        pcm[:] = rng.integers(-2 ** 15, 2 ** 15, pcm.size)
+        assert pcm.ctypes.data % 16 == shift
+        buf, nw = d._stage(pcm)
+        assert buf.ctypes.data % 16 == 0 and np.array_equal(buf, pcm) and nw == 5
+        assert (buf.ctypes.data == pcm.ctypes.data) == same and np.shares_memory(buf, pcm) == same
+    assert d._stage(np.zeros(n + hop, np.int16), 2)[1] == 2
+    with pytest.raises(A.DemodError) as e:
+        d._stage(np.zeros(n + hop, np.int16), 3)
+    assert e.value.code == A.DEMOD_BAD_ARG and "shorter" in str(e.value)
+    with pytest.raises(A.DemodError) as e:
+        d._stage(torch.zeros(n, dtype=torch.int16))
+    assert e.value.code == A.DEMOD_BAD_ARG and "pcm: on cpu" in str(e.value)
+
+
+@pytest.mark.parametrize("cls,destroy", [
+    ("Demodulator", "demod_destroy"), ("Streams", "demod_streams_destroy"), ("Receiver", "demod_rx_destroy"),
+    ("Transmitter", "demod_tx_destroy"), ("Group", "demod_group_destroy")])
+def test_handle_lifetime(A, cls, destroy):
+    """close() gives the handle back once, to the class's own destroy function,
+    and is harmless without one; `with` closes; __del__ never raises."""
+    calls = []
+
+    class Lib:
+        def __getattr__(self, name):
+            return lambda h: calls.append((name, h))
+
+    class Failing:
+        def __getattr__(self, name):
+            def fn(h):
+                calls.append((name, h))
+                raise RuntimeError("at interpreter shutdown")
+            return fn
+
+    def bare(lib, h):
+        o = object.__new__(getattr(A, cls))
+        o._lib, o._h = lib, h
+        return o
+
+    o = bare(Lib(), None)
+    o.close()
+    o.close()
+    del o._h                      # an __init__ that raised before the handle was made
+    o.close()
+    assert calls == []
+    o = bare(Lib(), 0x1234)
+    o.close()
+    o.close()
+    assert calls == [(destroy, 0x1234)] and o._h is None
+    with bare(Lib(), 0x5678) as o:
+        assert len(calls) == 1
+    assert calls[1:] == [(destroy, 0x5678)] and o._h is None
+    o = bare(Failing(), 0x9ABC)
+    o.__del__()
+    assert calls[2:] == [(destroy, 0x9ABC)]
+    o._h = None                   # nothing left for the garbage collector's own __del__
 
 
 def test_batch_launches_matches_the_split_rule(A):
