@@ -25,8 +25,8 @@
 //
 // collect, three launches whatever S and the counts are:
 //  stream  one wave per stream: the largest end over the OK rows (the check's
-//          span, checked_frame_span) into hold, keep from the scan's tail,
-//          cut_hits; the stream's emitted rows and their bytes into d_work, with
+//          span, checked_frame_span) into hold, keep from the scan's tail
+//          less R - 1 windows, cut_hits; the stream's emitted rows and their bytes into d_work, with
 //          the hold the decision used.
 //  prefix  one workgroup: thread t sums a contiguous chunk of streams, the chunk
 //          totals go through LDS and each thread rewrites its chunk as the
@@ -193,8 +193,10 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_stream_kernel(RxCollec
     const unsigned long long word = (L - 1) * R;   // a start at or past fill - word: its word does not fit yet
     unsigned keep = fill > word ? (unsigned)(fill - word) : 0u;
     if (tail >= 0) keep = (unsigned long long)tail < fill ? (unsigned)tail : fill;
+    // R - 1 windows more: the same word's start on the neighbouring earlier phases, should the next push choose one
+    const unsigned back = (unsigned)(R - 1);
     st->hold = reach;
-    st->keep = keep;
+    st->keep = keep > back ? keep - back : 0u;
     const unsigned long long n_hits = res->n_hits, n_written = res->n_written;
     st->cut_hits += n_hits > n_written ? n_hits - n_written : 0ull;
 }

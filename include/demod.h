@@ -1077,10 +1077,12 @@ int demod_streams_push_packets(demod_streams_t *ms, demod_decode_fn decode, void
  *              is EMITTED when base + window_i >= hold, hold as the pushes
  *              before left it (kept rows ascend: the rows not emitted are a
  *              prefix). Then hold = max(hold, the largest end_j of this push,
- *              covered rows included); keep = tail_window when the result's
- *              tail_window >= 0, else max(0, fill - (L - 1) R): every start, on
- *              any phase, whose word does not fit yet; cut_hits += n_hits -
- *              n_written.
+ *              covered rows included); keep = max(0, t - (R - 1)), where t is
+ *              tail_window when the result's tail_window >= 0, else fill - (L -
+ *              1) R: every start, on any phase, whose word does not fit yet.
+ *              The R - 1 windows below t hold the same word's start on the
+ *              other phases, for a next push that chooses one of them;
+ *              cut_hits += n_hits - n_written.
  *   4 output   the emitted rows of stream 0, then stream 1, ..., each in
  *              ascending window order; a row's data bytes at `body`, the
  *              exclusive prefix of `length` in that order.
@@ -1089,15 +1091,29 @@ int demod_streams_push_packets(demod_streams_t *ms, demod_decode_fn decode, void
  * phase (base + phase) mod R chosen at every push, the frames a stream emits
  * over all pushes are exactly the kept frames of demod_frames_checked (or
  * demod_frames_coded) on the whole recording, in the same order, whatever the
- * packet sizes. The phase is decided per push over X alone: a stream whose
- * timing metric is weak over a short X may pick another phase for that push and
- * miss the frames that complete in it. That limitation is not solved here. (A
- * frame completes only when X holds all of it, so the pushes that matter decide
- * the phase on L + N symbols or more.)
+ * packet sizes: the R - 1 windows kept below t lie on other phases and add no
+ * hit. The phase is decided per push over X alone, and two neighbouring phases
+ * tie when a symbol boundary lies half-way between them: the choice then flips
+ * from push to push. A frame whose word is a hit (max_errors or fewer errors)
+ * on the phase of every push, from the one in which its word first fits to the
+ * one in which its row is complete, is still received, once, at a window
+ * within R - 1 of the one-shot's: each of those pushes leaves keep at or below
+ * the word's start on any phase, and `hold` is phase-blind. What remains: a
+ * push in that span that picks a phase on which the word is NOT a hit finds no
+ * tail, sets keep from fill and lets the start go; the frame is then missed
+ * even if the push in which it completes picks the one-shot's phase again.
+ * That takes noise near the code's edge (tests/test_link_cpu.py: at amplitudes
+ * 8000 and 3000 in noise of sigma 8000 every one-shot frame is received at
+ * every sample offset tried; at the edge amplitudes, 1000 to 1400, 2 to 17 % of
+ * them are missed); it is not solved here. So, per frame: a frame of the
+ * one-shot that the receiver misses has a push in that span whose absolute
+ * phase is not the one-shot's.
  *
  * C >= 2 (L + N) R, so that a frame in flight and a full packet of the same
- * length fit; a packet with more new windows than that overflows (the oldest
- * windows go and `dropped` says how many).
+ * length fit: after a push X[keep ..) is at most (L + N) R - 1 windows (a tail
+ * is not complete, so fill - t <= (L + N - 1) R, and R - 1 more are kept),
+ * which leaves room for (L + N) R + 1 new ones. A packet with more new windows
+ * than that overflows (the oldest windows go and `dropped` says how many).
  */
 typedef struct demod_rx_cfg {
     uint8_t  sync[DEMOD_MAX_SYNC];     /* the word, sync_len symbols */

@@ -13,8 +13,9 @@ being the stream's window base + i; with it keep, hold, dropped, cut_hits, all
              soft values of X, decode_rows, the coded check_group.
   3 collect  end_j = base + window_j + (L + S_j) R over the OK rows; a kept row
              is emitted when base + window >= hold (hold from the pushes
-             before); then hold = max(hold, max end_j); keep = tail_window if
-             >= 0 else max(0, fill - (L - 1) R); cut_hits += n_hits - n_written.
+             before); then hold = max(hold, max end_j); keep = max(0, t - (R -
+             1)), t = tail_window if >= 0 else fill - (L - 1) R; cut_hits +=
+             n_hits - n_written.
   4 output   stream 0's emitted rows, then stream 1's, ..; body = the exclusive
              prefix of the lengths in that order.
 
@@ -25,6 +26,7 @@ demod_frames_checked / demod_frames_coded's kept frames on a whole recording.
 """
 import numpy as np
 
+import acquire_ref
 import frames_check_ref as C
 import frames_fec_ref as FEC
 import frames_ref as F
@@ -142,7 +144,8 @@ def collect(state, hits, results, check, kept, body, chk_summary, L, R, bits, h,
             n, nb = n + 1, nb + ln
         fill, tail = int(state["fill"][s]), int(results["tail_window"][s])
         state["hold"][s] = reach
-        state["keep"][s] = min(tail, fill) if tail >= 0 else max(0, fill - (L - 1) * R)
+        t = min(tail, fill) if tail >= 0 else fill - (L - 1) * R
+        state["keep"][s] = max(0, t - (R - 1))
         cut = int(results["n_hits"][s]) - int(results["n_written"][s])
         state["cut_hits"][s] = (int(state["cut_hits"][s]) + max(cut, 0)) & M64
         checked += min(int(chk_summary["n_checked"][s]), mf)
@@ -195,6 +198,7 @@ class Rx:
         self.sym = [np.zeros(0, np.uint8) for _ in range(S)]
         self.P = [np.zeros((0, K), np.float32) for _ in range(S)]
         self.phases = [[] for _ in range(S)]      # (base + phase) mod R of each scanned push
+        self.margins = [[] for _ in range(S)]     # acquire_ref.margin of the same push's metric
 
     def reset(self, s):
         self.state[s] = 0
@@ -220,6 +224,7 @@ class Rx:
                                                            self.N, self.h, self.kind, self.fec, self.max_frames)
             if fill >= R:
                 self.phases[s].append((base + res["phase"]) % R)
+                self.margins[s].append(acquire_ref.margin(res["metric"]))
             hold = int(st["hold"])
             reach = hold
             for i in np.flatnonzero(check["status"] == C.OK):
@@ -232,7 +237,8 @@ class Rx:
                     bodies.append(bod[r])
                     nb += len(bod[r])
             st["hold"] = reach
-            st["keep"] = res["tail_window"] if res["tail_window"] >= 0 else max(0, fill - (L - 1) * R)
+            t = res["tail_window"] if res["tail_window"] >= 0 else fill - (L - 1) * R
+            st["keep"] = max(0, t - (R - 1))       # R - 1 more: the word's start on the other phases
             st["cut_hits"] = int(st["cut_hits"]) + res["n_hits"] - res["n_written"]
             checked, valid = checked + int(summ["n_checked"]), valid + int(summ["n_valid"])
         summary = dict(n_frames=len(frames), n_bytes=nb, n_checked=checked, n_valid=valid)

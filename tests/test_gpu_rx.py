@@ -19,6 +19,7 @@ import pytest
 import frames_check_ref as C
 import frames_ref as F
 import guards as G
+import link_ref as LR
 import rx_ref as X
 
 pytestmark = pytest.mark.gpu
@@ -430,13 +431,7 @@ def detector_pieces(d, pcm, sizes):
     packets of `sizes` frames sees them: [(sym, P)] per push."""
     W = (len(pcm) - N) // HOP + 1
     sym, P = d.batch(pcm[:(W - 1) * HOP + N], mags=True)
-    out, total, seen = [], 0, 0
-    for n in sizes:
-        total += n
-        w = 0 if total < N else (total - N) // HOP + 1
-        out.append((sym[seen:w], P[seen:w]))
-        seen = w
-    return out
+    return LR.pieces(sym, P, sizes, N, HOP)
 
 
 @pytest.mark.parametrize("fec", [0, 1])

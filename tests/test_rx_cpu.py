@@ -297,7 +297,7 @@ def test_hold_rule(K):
     cut = w_out + (L_WORD + N - 1) * R + 1
     rx = X.Rx(1, K, R, word, 0, N, H, KIND, fec, 16, W)
     fr, _, _ = rx.push([(sym[:cut], P[:cut])])
-    assert fr["window"].tolist() == [w_out] and rx.state["keep"][0] == w_in - rx.state["base"][0]
+    assert fr["window"].tolist() == [w_out] and rx.state["keep"][0] == w_in - (R - 1) - rx.state["base"][0]
     assert rx.state["hold"][0] == w_out + (L_WORD + X.span(len(outer), bits, H, KIND, fec)) * R > w_in
     fr, _, summ = rx.push([(sym[cut:], P[cut:])])
     assert fr["window"].tolist() == [P0 + planted[1][0] * R] and summ["n_valid"] == 2
