@@ -221,8 +221,28 @@ FRAME_CHECK_DTYPE = np.dtype(DemodFrameCheck)
 FRAMES_CHECK_RESULT_DTYPE = np.dtype(DemodFramesCheckResult)
 
 
-DEMOD_FEC_CONV_K7 = 1
+DEMOD_FEC_CONV_K7 = 1          # low nibble: the code. Alone: rate 1/2, coded bits in order
+DEMOD_FEC_RATE_2_3 = 0x10
+DEMOD_FEC_RATE_3_4 = 0x20      # both rate flags together: refused
+DEMOD_FEC_INTERLEAVE = 0x40
+DEMOD_FEC_IL_ROWS = 16
+DEMOD_FEC_IL_COLS = 16
 DEMOD_FEC_DEPTH = 64
+FEC_MODES = tuple(DEMOD_FEC_CONV_K7 | r | i for i in (0, DEMOD_FEC_INTERLEAVE)
+                  for r in (0, DEMOD_FEC_RATE_2_3, DEMOD_FEC_RATE_3_4))
+
+
+def fec_row_steps(n_soft: int, fec: int) -> int:
+    """St of a row of n_soft = C air soft values in a valid mode (include/
+    demod.h "punctured and interleaved"): the greatest T with Nt(T) <= Cu."""
+    if fec not in FEC_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
+    cu = int(n_soft) & ~255 if fec & DEMOD_FEC_INTERLEAVE else int(n_soft)
+    if fec & DEMOD_FEC_RATE_2_3:
+        return 2 * (cu // 3) + (cu % 3 == 2)
+    if fec & DEMOD_FEC_RATE_3_4:
+        return 3 * (cu // 4) + (0, 0, 1, 2)[cu % 4]
+    return cu // 2
 DEMOD_DECODE_OK = 0
 DEMOD_DECODE_BAD_LENGTH = 1   # len > max_len; metric and steps 0
 
@@ -406,6 +426,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "demod_coded_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, _P, _SZ,
                                                     ctypes.POINTER(DemodFrameDecode)]),
         "demod_frames_decode_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), _SZ, _SZ, _SZ]),
+        "demod_fec_air_index": (ctypes.c_longlong, [ctypes.c_int, _SZ]),
+        "demod_fec_frame_symbols": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_int]),
+        "demod_fec_frame_encode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _SZ]),
+        "demod_fec_row_bytes": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+        "demod_fec_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _SZ,
+                                                  ctypes.POINTER(DemodFrameDecode)]),
+        "demod_fec_decode_workspace_size": (_SZ, [ctypes.POINTER(DemodCfg), _SZ, _SZ, _SZ, ctypes.c_int]),
         "demod_frames_decode_async": (ctypes.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, _SZ,
                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P,
                                                      _SZ, _P]),
@@ -659,6 +687,15 @@ def frames_decode_workspace_size(cfg: DemodCfg, n_groups: int, max_frames: int, 
     x max_frames rows of frame_symbols symbols needs (no GPU). Raises
     DemodError(DEMOD_BAD_ARG) where it is 0."""
     return _size("demod_frames_decode_workspace_size", cfg, n_groups, max_frames, frame_symbols)
+
+
+def fec_decode_workspace_size(cfg: DemodCfg, n_groups: int, max_frames: int, frame_symbols: int,
+                              fec: int = DEMOD_FEC_CONV_K7) -> int:
+    """demod_fec_decode_workspace_size: frames_decode_workspace_size with the
+    mode's St (no GPU). Raises DemodError(DEMOD_BAD_ARG) where it is 0."""
+    if fec not in FEC_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
+    return _size("demod_fec_decode_workspace_size", cfg, n_groups, max_frames, frame_symbols, fec)
 
 
 def make_rx_cfg(sync, max_errors: int = 0, frame_symbols: int = 0, len_bytes: int = 2,
@@ -1255,14 +1292,14 @@ class Demodulator(_Handle):
     def _frame_shape(self, frame_symbols: int, len_bytes: int, crc: int, fec: int) -> Tuple[int, int]:
         """(row bytes, max_len) of rows of frame_symbols symbols: B of a checked
         frame's packed rows (fec 0), Bd of a coded frame's decoded rows
-        (DEMOD_FEC_CONV_K7, of St trellis steps)."""
+        (a coded mode, of its St trellis steps)."""
         if len_bytes not in (1, 2) or crc not in CRC_BYTES:
             raise DemodError(DEMOD_BAD_ARG, "len_bytes not 1 or 2, or an unknown crc kind")
         bits = bits_per_symbol(self.k)
         if fec:
             if self.k != 1 << bits:
                 raise DemodError(DEMOD_BAD_ARG, "coded frames need K = 2^bits tones")
-            St = int(frame_symbols) * bits // 2
+            St = fec_row_steps(int(frame_symbols) * bits, fec)
             if St < 8 * len_bytes + DEMOD_FEC_DEPTH:
                 raise DemodError(DEMOD_BAD_ARG, "rows shorter than the header look-ahead")
             B, short = (St - 6) // 8, ""
@@ -1324,14 +1361,14 @@ class Demodulator(_Handle):
         frames_segments_async). d_hits and d_results are the scan's, d_mag
         (float32, n_windows * k) the detector's; d_rows (uint8, n_groups *
         max_frames * Bd bytes) and d_decode (uint8, 16 bytes a row) are
-        written; d_work (uint8, at least frames_decode_workspace_size bytes)
-        may hold anything. Device tensors, checked like the batch calls'."""
+        written; d_work (uint8, at least fec_decode_workspace_size bytes of
+        the mode `fec`) may hold anything. Device tensors, checked like the batch calls'."""
         S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
         W, L = int(n_windows), int(sync_len)
         if W < 0 or W >= 2 ** 31:
             raise DemodError(DEMOD_BAD_ARG, "n_windows not in 0 .. 2^31 - 1")
-        if fec != DEMOD_FEC_CONV_K7:
-            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        if fec not in FEC_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
         Bd, _ = self._frame_shape(N, len_bytes, crc, fec)
         dev = int(self.cfg.device)
         rows = S * cap
@@ -1341,7 +1378,7 @@ class Demodulator(_Handle):
         _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
         _check_dev(d_rows, "d_rows", "uint8", rows * Bd, dev)
         _check_dev(d_decode, "d_decode", "uint8", rows * ctypes.sizeof(DemodFrameDecode), dev)
-        _check_dev(d_work, "d_work", "uint8", frames_decode_workspace_size(self.cfg, S, cap, N), dev)
+        _check_dev(d_work, "d_work", "uint8", fec_decode_workspace_size(self.cfg, S, cap, N, fec), dev)
         rc = self._lib.demod_frames_decode_async(
             self._h, _ptr(d_hits), _ptr(d_mag), W, _ptr(d_first) if d_first is not None else None,
             _ptr(d_results), S, cap, L, N, int(len_bytes), int(crc), int(fec), _ptr(d_rows), _ptr(d_decode),
@@ -1356,8 +1393,8 @@ class Demodulator(_Handle):
         frames_decode_async wrote (uint8, n_groups * max_frames * Bd bytes),
         with max_len = Bd - len_bytes - the CRC's bytes and the coded span."""
         S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
-        if fec != DEMOD_FEC_CONV_K7:
-            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        if fec not in FEC_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
         Bd, max_len = self._frame_shape(N, len_bytes, crc, fec)
         self._check_scan_outputs(S, cap, max_len, d_hits, d_results, d_check, d_kept, d_body, d_summary,
                                  rows=(d_rows, "d_rows", Bd))
@@ -1416,8 +1453,8 @@ class Demodulator(_Handle):
         calls'."""
         S, cap, N = _rows_shape(n_streams, max_frames, frame_symbols, "n_streams")
         L = int(sync_len)
-        if fec not in (0, DEMOD_FEC_CONV_K7):
-            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        if fec != 0 and fec not in FEC_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not 0 or one of the six coded modes")
         _, max_len = self._frame_shape(N, len_bytes, crc, fec)
         dev = int(self.cfg.device)
         rows = S * cap
@@ -1502,8 +1539,8 @@ class Demodulator(_Handle):
         """demod_frames_coded: frames_checked for coded frames (include/demod.h
         "coded frames"): detector, frame scan, soft-decision decode of its rows
         and the coded check. Returns what frames_checked returns."""
-        if fec != DEMOD_FEC_CONV_K7:
-            raise DemodError(DEMOD_BAD_ARG, "fec: unknown code")
+        if fec not in FEC_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
         return self._frames_checked(pcm, sync, max_errors, frame_symbols, len_bytes, crc, int(fec), max_frames,
                                     n_windows, body)
 
@@ -1950,6 +1987,71 @@ def coded_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FA
                                                  int(crc), _ptr(row), int(cap), ctypes.byref(dec))
     if rc < 0:
         raise DemodError(rc, "demod_coded_frame_decode")
+    return row[:rc].tobytes(), _struct_dict(dec)
+
+
+def fec_air_index(fec: int, m: int) -> int:
+    """demod_fec_air_index: the air position of mother bit m = 2 t + v in the
+    mode `fec`, or -1 where it is punctured."""
+    if fec not in FEC_MODES or not 0 <= int(m) < 2 ** 31:
+        raise DemodError(DEMOD_BAD_ARG, "demod_fec_air_index")
+    return int(load_library().demod_fec_air_index(int(fec), int(m)))
+
+
+def fec_frame_symbols(length: int, len_bytes: int, crc: int, bits: int, fec: int) -> int:
+    """demod_fec_frame_symbols: Sc of the mode, ceil(Na(len) / bits)."""
+    if fec not in FEC_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "demod_fec_frame_symbols")
+    rc = int(load_library().demod_fec_frame_symbols(int(length), int(len_bytes), int(crc), int(bits), int(fec)))
+    if rc < 0:
+        raise DemodError(rc, "demod_fec_frame_symbols")
+    return rc
+
+
+def fec_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE,
+                     fec: int = DEMOD_FEC_CONV_K7, cap: Optional[int] = None) -> bytes:
+    """demod_fec_frame_encode: the frame's bits in air order, pad bits 0. cap:
+    the output room handed to the library (default: what any mode needs)."""
+    if fec not in FEC_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "demod_fec_frame_encode")
+    lib = load_library()
+    data = bytes(data)
+    if cap is None:
+        cap = 2 * len(data) + 64
+    src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    out = (ctypes.c_uint8 * max(int(cap), 1))()
+    rc = lib.demod_fec_frame_encode(src, len(data), int(len_bytes), int(crc), int(fec), out, int(cap))
+    if rc < 0:
+        raise DemodError(rc, "demod_fec_frame_encode")
+    return bytes(out[:rc])
+
+
+def fec_row_bytes(frame_symbols: int, bits: int, len_bytes: int = 2, fec: int = DEMOD_FEC_CONV_K7) -> int:
+    """demod_fec_row_bytes: Bd of rows of frame_symbols symbols in the mode."""
+    if frame_symbols < 0 or fec not in FEC_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "demod_fec_row_bytes")
+    rc = int(load_library().demod_fec_row_bytes(int(frame_symbols), int(bits), int(len_bytes), int(fec)))
+    if rc < 0:
+        raise DemodError(rc, "demod_fec_row_bytes")
+    return rc
+
+
+def fec_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE,
+                     fec: int = DEMOD_FEC_CONV_K7, cap: Optional[int] = None) -> Tuple[bytes, dict]:
+    """demod_fec_frame_decode: the host decoder on int8 soft values in air
+    order. Returns (the row bytes written, the decode record as a dict). cap:
+    the row room handed to the library (default: Bd)."""
+    q = np.ascontiguousarray(soft, dtype=np.int8).reshape(-1)
+    if cap is None:
+        cap = max((fec_row_steps(q.size, fec) - 6) // 8, 0)
+    elif fec not in FEC_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "demod_fec_frame_decode")
+    row = np.zeros(max(int(cap), 1), dtype=np.uint8)
+    dec = DemodFrameDecode()
+    rc = load_library().demod_fec_frame_decode(_ptr(q) if q.size else None, q.size, int(len_bytes), int(crc),
+                                               int(fec), _ptr(row), int(cap), ctypes.byref(dec))
+    if rc < 0:
+        raise DemodError(rc, "demod_fec_frame_decode")
     return row[:rc].tobytes(), _struct_dict(dec)
 
 

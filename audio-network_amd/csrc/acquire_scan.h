@@ -23,6 +23,7 @@
 #pragma once
 #include "../../include/demod.h"
 #include "demod_internal.h"
+#include "fec_map.h"
 
 namespace fskd {
 
@@ -122,15 +123,17 @@ __device__ __forceinline__ uint8_t frame_packed_byte(const uint8_t *src, unsigne
 
 // the symbols a checked frame of `length` data bytes occupies behind its word
 // (include/demod.h "checked frames": S, its h + len + c bytes; with fec_depth
-// "coded frames": Sc, its 2 T(len) coded bits). The one copy of the span that
+// "coded frames": Sc, its coded bits on the air). The one copy of the span that
 // `covered` (frames_check.hip) and the receiver's `hold` (frames_carry.hip) use.
+// A mapped mode (fec_map.h: punctured, interleaved) has Sc of its Na(len) air bits.
 __device__ __forceinline__ unsigned checked_frame_span(unsigned length, unsigned len_bytes, unsigned crc_bytes,
-                                                       unsigned bits, unsigned fec_depth)
+                                                       unsigned bits, unsigned fec_depth, unsigned fec)
 {
     unsigned span = (len_bytes + crc_bytes + length) * 8;
     if (fec_depth) {
         const unsigned least = 8u * len_bytes + fec_depth;
-        span = 2u * (span + 6u > least ? span + 6u : least);
+        const unsigned T = span + 6u > least ? span + 6u : least;
+        span = fec_mode_mapped(fec) ? fec_air_bits(fec, fec_kept_bits(fec, T)) : 2u * T;
     }
     return (span + bits - 1) / bits;
 }

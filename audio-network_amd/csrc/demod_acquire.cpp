@@ -506,6 +506,13 @@ int demod_frames_segments(demod_t *st, const int16_t *pcm, size_t n_windows, con
 
 // ---- checked frames (frames_check.hip) ---------------------------------------
 
+// St of rows of C = N bits soft values in a valid mode (C < 2^33; a mapped mode's beyond 2^32 - 1: 0)
+static size_t fec_row_steps(unsigned fec, size_t C)
+{
+    if (!fec_mode_mapped(fec)) return C / 2;
+    return C > 0xFFFFFFFFu ? 0 : fec_steps_within(fec, fec_usable_bits(fec, (unsigned)C));
+}
+
 // Fills what the shape decides (row width, max_len, the CRC's constants, R,
 // bits, L); false for what demod_frames_check_async refuses about it.
 static bool frames_check_shape(const demod_cfg_t &cfg, size_t n_groups, size_t max_frames, size_t sync_len,
@@ -522,12 +529,13 @@ static bool frames_check_shape(const demod_cfg_t &cfg, size_t n_groups, size_t m
     if (frame_symbols > 0x7FFFFFFF) return false;
     size_t B = packed_row_bytes(frame_symbols, bits);
     if (fec) {
-        // coded rows: St = floor(N bits / 2) steps decode to Bd = (St - 6) / 8 bytes
-        const size_t St = frame_symbols * bits / 2;
-        if (fec != DEMOD_FEC_CONV_K7 || cfg.k != (1u << bits)) return false;
+        // coded rows: the mode's St steps (fec_map.h) decode to Bd = (St - 6) / 8 bytes
+        if (!fec_mode_valid((unsigned)fec) || cfg.k != (1u << bits)) return false;
+        const size_t St = fec_row_steps((unsigned)fec, frame_symbols * bits);
         if (St < 8 * h + DEMOD_FEC_DEPTH) return false;
         B = (St - 6) / 8;
         p.fec_depth = DEMOD_FEC_DEPTH;
+        p.fec = fec;
     }
     if (B < h + c || B - h - c > DEMOD_MAX_FRAME_PAYLOAD) return false;
     p.n_groups = (unsigned)n_groups;
@@ -605,11 +613,18 @@ int demod_frames_check_async(demod_t *st, const demod_frame_hit_t *d_hits, const
 size_t demod_frames_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
                                           size_t frame_symbols)
 {
+    return demod_fec_decode_workspace_size(cfg, n_groups, max_frames, frame_symbols, DEMOD_FEC_CONV_K7);
+}
+
+size_t demod_fec_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
+                                       size_t frame_symbols, int fec)
+{
+    if (!fec_mode_valid((unsigned)fec)) return 0;
     if (validate_cfg(cfg) != DEMOD_OK || cfg->k < 2 || (cfg->k & (cfg->k - 1)) != 0) return 0;
     if (n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames == 0 || max_frames > 0x7FFFFFFF) return 0;
     if ((unsigned long long)n_groups * max_frames > 0x7FFFFFFFull) return 0;
     if (frame_symbols == 0 || frame_symbols > 0x7FFFFFFF) return 0;
-    const size_t St = frame_symbols * (size_t)demod_bits_per_symbol(cfg->k) / 2;
+    const size_t St = fec_row_steps((unsigned)fec, frame_symbols * (size_t)demod_bits_per_symbol(cfg->k));
     return n_groups * (size_t)fec_waves_per_group((unsigned)n_groups, (unsigned)max_frames) * St * 8;
 }
 
@@ -624,13 +639,13 @@ int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, cons
     if (((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_work & 7) != 0 ||
         ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_decode & 3) != 0)
         return DEMOD_BAD_ARG;
-    if (fec != DEMOD_FEC_CONV_K7 || n_windows > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    if (!fec_mode_valid((unsigned)fec) || n_windows > 0x7FFFFFFF) return DEMOD_BAD_ARG;
     FramesCheckParams q;   // the shape the coded check will see: the same refusals
     std::memset(&q, 0, sizeof(q));
     if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, q, fec))
         return DEMOD_BAD_ARG;
     if ((sync_len + frame_symbols) * (size_t)q.phases > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const size_t need = demod_frames_decode_workspace_size(&st->cfg, n_groups, max_frames, frame_symbols);
+    const size_t need = demod_fec_decode_workspace_size(&st->cfg, n_groups, max_frames, frame_symbols, fec);
     if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
     FramesFecParams p;
     std::memset(&p, 0, sizeof(p));
@@ -642,7 +657,8 @@ int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, cons
     p.n_groups = q.n_groups;
     p.max_frames = q.max_frames;
     p.frame_symbols = (unsigned)frame_symbols;
-    p.steps = (unsigned)(frame_symbols * (size_t)q.bits / 2);
+    p.steps = (unsigned)fec_row_steps((unsigned)fec, frame_symbols * (size_t)q.bits);
+    p.fec = (unsigned)fec;
     p.row_bytes = q.row_bytes;
     p.max_len = q.max_len;
     p.len_bytes = q.len_bytes;
@@ -667,7 +683,7 @@ int demod_frames_check_coded_async(demod_t *st, const demod_frame_hit_t *d_hits,
                                    uint32_t *d_kept, uint8_t *d_body,
                                    demod_frames_check_result_t *d_summary, void *stream)
 {
-    if (fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    if (!fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     return frames_check_enqueue(st, d_hits, d_rows, d_results, n_groups, max_frames, sync_len,
                                 frame_symbols, len_bytes, crc, fec, d_check, d_kept, d_body, d_summary, stream);
 }
@@ -686,7 +702,7 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
     FramesCheckParams p;
     std::memset(&p, 0, sizeof(p));
     if (!frames_check_shape(st, 1, dcap, sync_len, frame_symbols, len_bytes, crc, p, fec)) return DEMOD_BAD_ARG;
-    const size_t fec_work = fec ? demod_frames_decode_workspace_size(&st->cfg, 1, dcap, frame_symbols) : 0;
+    const size_t fec_work = fec ? demod_fec_decode_workspace_size(&st->cfg, 1, dcap, frame_symbols, fec) : 0;
     DeviceGuard guard(st->device);
     HIP_TRY(guard.err);
     const size_t N = frame_symbols, B = p.row_bytes, M = p.max_len;
@@ -762,7 +778,7 @@ int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const 
                        size_t max_frames, demod_frames_result_t *result,
                        demod_frames_check_result_t *summary)
 {
-    if (fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    if (!fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
                               fec, hits, lengths, body, max_frames, result, summary);
 }
@@ -781,7 +797,7 @@ int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n
     for (size_t i = 0; i < L; ++i)
         if (x.sync[i] >= cfg->k) return DEMOD_BAD_ARG;
     if (N > 0x7FFFFFFF || (L + N) * R > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    if (x.fec != 0 && x.fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    if (x.fec != 0 && !fec_mode_valid(x.fec)) return DEMOD_BAD_ARG;
     // the check's (or the decode's and the coded check's): S, max_frames, the row shape
     FramesCheckParams p;
     std::memset(&p, 0, sizeof(p));
@@ -794,7 +810,7 @@ int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n
     out->ring_sym_bytes = S * C;
     out->ring_mag_bytes = S * C * cfg->k * sizeof(float);
     out->scan_work_bytes = demod_frames_segments_workspace_size(cfg, S, S * C);
-    out->decode_work_bytes = x.fec ? demod_frames_decode_workspace_size(cfg, S, x.max_frames, N) : 0;
+    out->decode_work_bytes = x.fec ? demod_fec_decode_workspace_size(cfg, S, x.max_frames, N, (int)x.fec) : 0;
     out->collect_work_bytes = demod_rx_collect_workspace_size(cfg, S);
     out->frames_bytes = rows * sizeof(demod_rx_frame_t);
     out->bodies_bytes = rows * p.max_len;
@@ -866,7 +882,7 @@ int demod_rx_collect_async(demod_t *st, demod_rx_stream_state_t *d_state, const 
         ((uintptr_t)d_summary & 7) != 0 || ((uintptr_t)d_work & 7) != 0 || ((uintptr_t)d_check & 3) != 0 ||
         ((uintptr_t)d_kept & 3) != 0)
         return DEMOD_BAD_ARG;
-    if (fec != 0 && fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    if (fec != 0 && !fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     FramesCheckParams q;   // the shape the check saw: the same refusals, the same span
     std::memset(&q, 0, sizeof(q));
     if (!frames_check_shape(st, n_streams, max_frames, sync_len, frame_symbols, len_bytes, crc, q, fec))
@@ -892,6 +908,7 @@ int demod_rx_collect_async(demod_t *st, demod_rx_stream_state_t *d_state, const 
     p.phases = q.phases;
     p.sync_len = q.sync_len;
     p.fec_depth = q.fec_depth;
+    p.fec = q.fec;
     p.frames = d_frames;
     p.bodies = d_bodies;
     p.summary = d_summary;

@@ -3,7 +3,9 @@
  * frames", DESIGN.md §4.9 "Coded frames"): the constraint-length-7, rate-1/2
  * convolutional encoder (0171/0133) over a checked frame's bytes, the soft
  * values of one window's tone powers, and the soft-decision Viterbi decoder
- * the device (frames_fec.hip) is held to, bit for bit. Integer arithmetic
+ * the device (frames_fec.hip) is held to, bit for bit; each also in the
+ * punctured and interleaved modes, through the map of fec_map.h (the
+ * demod_fec_* functions; the older ones are their fec == 1 case). Integer arithmetic
  * apart from one double expression per soft value. Pure host work, no device.
  */
 #include <math.h>
@@ -13,6 +15,7 @@
 #include <string.h>
 
 #include "../../include/demod.h"
+#include "fec_map.h"
 
 #define FEC_G0 0171u
 #define FEC_G1 0133u
@@ -40,21 +43,43 @@ long long demod_coded_frame_steps(size_t len, int len_bytes, int crc)
     return body > least ? body : least;
 }
 
-long long demod_coded_frame_symbols(size_t len, int len_bytes, int crc, int bits)
+long long demod_fec_air_index(int fec, size_t m)
 {
-    const long long T = demod_coded_frame_steps(len, len_bytes, crc);
-    if (T < 0) return T;
-    if (bits < 1 || bits > 4) return DEMOD_BAD_ARG;
-    return (2 * T + bits - 1) / bits;
+    if (!fec_mode_valid((unsigned)fec) || m > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const unsigned a = fec_air_of_mother((unsigned)fec, (unsigned)m);
+    return a == FEC_MAP_NONE ? -1 : (long long)a;
 }
 
-int demod_coded_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, uint8_t *out,
-                             size_t cap)
+/* Na(len): the frame's bits on the air, or a negative code */
+static long long fec_frame_air_bits(size_t len, int len_bytes, int crc, int fec)
 {
+    if (!fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     const long long T = demod_coded_frame_steps(len, len_bytes, crc);
-    if (T < 0) return (int)T;
+    if (T < 0) return T;
+    return (long long)fec_air_bits((unsigned)fec, fec_kept_bits((unsigned)fec, (unsigned)T));
+}
+
+long long demod_fec_frame_symbols(size_t len, int len_bytes, int crc, int bits, int fec)
+{
+    const long long Na = fec_frame_air_bits(len, len_bytes, crc, fec);
+    if (Na < 0) return Na;
+    if (bits < 1 || bits > 4) return DEMOD_BAD_ARG;
+    return (Na + bits - 1) / bits;
+}
+
+long long demod_coded_frame_symbols(size_t len, int len_bytes, int crc, int bits)
+{
+    return demod_fec_frame_symbols(len, len_bytes, crc, bits, DEMOD_FEC_CONV_K7);
+}
+
+int demod_fec_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, int fec, uint8_t *out,
+                           size_t cap)
+{
+    const long long Na = fec_frame_air_bits(len, len_bytes, crc, fec);
+    if (Na < 0) return (int)Na;
     if ((!data && len) || !out) return DEMOD_BAD_ARG;
-    const size_t need = (size_t)(2 * T + 7) / 8;
+    const long long T = demod_coded_frame_steps(len, len_bytes, crc);
+    const size_t need = (size_t)(Na + 7) / 8;
     if (need > cap) return DEMOD_BUFFER_TOO_SMALL;
     uint8_t info[2 + DEMOD_MAX_FRAME_PAYLOAD + 4];
     const int n = demod_checked_frame_encode(data, len, len_bytes, crc, info, sizeof(info));
@@ -64,20 +89,42 @@ int demod_coded_frame_encode(const uint8_t *data, size_t len, int len_bytes, int
     for (long long t = 0; t < T; ++t) {
         const unsigned u = t < 8 * (long long)n ? (info[t >> 3] >> (7 - (t & 7))) & 1u : 0u;
         reg = ((reg << 1) | u) & 0x7Fu;
-        const unsigned v0 = parity7(reg & FEC_G0), v1 = parity7(reg & FEC_G1);
-        out[(2 * t) >> 3] |= (uint8_t)(v0 << (7 - ((2 * t) & 7)));
-        out[(2 * t + 1) >> 3] |= (uint8_t)(v1 << (7 - ((2 * t + 1) & 7)));
+        for (unsigned v = 0; v < 2; ++v) {
+            const unsigned a = fec_air_of_mother((unsigned)fec, 2u * (unsigned)t + v);
+            if (a == FEC_MAP_NONE) continue;   /* punctured */
+            out[a >> 3] |= (uint8_t)(parity7(reg & (v ? FEC_G1 : FEC_G0)) << (7 - (a & 7)));
+        }
     }
     return (int)need;
 }
 
+int demod_coded_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, uint8_t *out,
+                             size_t cap)
+{
+    return demod_fec_frame_encode(data, len, len_bytes, crc, DEMOD_FEC_CONV_K7, out, cap);
+}
+
+/* St of rows of C air bits, or -1 where the row is refused */
+static long long fec_row_steps(size_t C, int len_bytes, int fec)
+{
+    if (!fec_mode_valid((unsigned)fec) || (len_bytes != 1 && len_bytes != 2)) return -1;
+    if (fec_mode_mapped((unsigned)fec) && C > 0xFFFFFFFFu) return -1;
+    const long long St = !fec_mode_mapped((unsigned)fec)
+                             ? (long long)(C / 2)
+                             : (long long)fec_steps_within((unsigned)fec, fec_usable_bits((unsigned)fec, (unsigned)C));
+    return St < 8 * len_bytes + DEMOD_FEC_DEPTH ? -1 : St;
+}
+
+long long demod_fec_row_bytes(size_t frame_symbols, int bits, int len_bytes, int fec)
+{
+    if (bits < 1 || bits > 4 || frame_symbols > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const long long St = fec_row_steps(frame_symbols * (size_t)bits, len_bytes, fec);
+    return St < 0 ? DEMOD_BAD_ARG : (St - 6) / 8;
+}
+
 long long demod_coded_row_bytes(size_t frame_symbols, int bits, int len_bytes)
 {
-    if (bits < 1 || bits > 4 || (len_bytes != 1 && len_bytes != 2) || frame_symbols > 0x7FFFFFFF)
-        return DEMOD_BAD_ARG;
-    const long long St = (long long)frame_symbols * bits / 2;
-    if (St < 8 * len_bytes + DEMOD_FEC_DEPTH) return DEMOD_BAD_ARG;
-    return (St - 6) / 8;
+    return demod_fec_row_bytes(frame_symbols, bits, len_bytes, DEMOD_FEC_CONV_K7);
 }
 
 int demod_soft_bits(const float *powers, uint32_t k, int8_t *soft)
@@ -133,14 +180,11 @@ static void forward(const int8_t *soft, size_t t_from, size_t t_to, int32_t *M, 
     }
 }
 
-int demod_coded_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, uint8_t *row,
-                             size_t cap, demod_frame_decode_t *decode)
+/* the decoder on the 2 St trellis soft values q (punctured positions 0) */
+static int trellis_decode(const int8_t *soft, size_t St, size_t h, size_t c, uint8_t *row, size_t cap,
+                          demod_frame_decode_t *decode)
 {
-    const size_t c = crc_bytes(crc), h = (size_t)len_bytes;
-    if (!soft || !row || !decode || c == 0 || (len_bytes != 1 && len_bytes != 2)) return DEMOD_BAD_ARG;
-    if (n_soft > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const size_t St = n_soft / 2, t0 = 8 * h + DEMOD_FEC_DEPTH;
-    if (St < t0) return DEMOD_BAD_ARG;
+    const size_t t0 = 8 * h + DEMOD_FEC_DEPTH;
     const size_t Bd = (St - 6) / 8;
     if (Bd < h + c || Bd - h - c > DEMOD_MAX_FRAME_PAYLOAD) return DEMOD_BAD_ARG;
     if (cap < Bd) return DEMOD_BUFFER_TOO_SMALL;
@@ -189,4 +233,30 @@ int demod_coded_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, i
     free(surv);
     free(bits);
     return written;
+}
+
+int demod_fec_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, int fec, uint8_t *row,
+                           size_t cap, demod_frame_decode_t *decode)
+{
+    const size_t c = crc_bytes(crc), h = (size_t)len_bytes;
+    if (!soft || !row || !decode || c == 0 || n_soft > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const long long St = fec_row_steps(n_soft, len_bytes, fec);
+    if (St < 0) return DEMOD_BAD_ARG;
+    if (!fec_mode_mapped((unsigned)fec)) return trellis_decode(soft, (size_t)St, h, c, row, cap, decode);
+    /* the trellis's order: q_m from air position a(m), 0 where m is punctured */
+    int8_t *q = (int8_t *)malloc(2 * (size_t)St);
+    if (!q) return DEMOD_ALLOC_FAIL;
+    for (size_t m = 0; m < 2 * (size_t)St; ++m) {
+        const unsigned a = fec_air_of_mother((unsigned)fec, (unsigned)m);   /* < Cu <= n_soft */
+        q[m] = a == FEC_MAP_NONE ? 0 : soft[a];
+    }
+    const int rc = trellis_decode(q, (size_t)St, h, c, row, cap, decode);
+    free(q);
+    return rc;
+}
+
+int demod_coded_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, uint8_t *row,
+                             size_t cap, demod_frame_decode_t *decode)
+{
+    return demod_fec_frame_decode(soft, n_soft, len_bytes, crc, DEMOD_FEC_CONV_K7, row, cap, decode);
 }

@@ -10,6 +10,7 @@
 
 #include "../../include/demod.h"
 #include "demod_internal.h"
+#include "fec_map.h"
 #include "plan.h"
 
 // Makes `dev` current for the scope of an entry point and restores the

@@ -375,6 +375,7 @@ struct FramesCheckParams {
     int phases;                           // R
     int sync_len;                         // L
     int fec_depth;                        // 0: S = ceil(8 n / bits); DEMOD_FEC_DEPTH: the coded span
+    int fec;                              // 0 or the coded mode (fec_map.h): the span's Sc
     ::demod_frame_check *check;           // [n_groups][max_frames]
     uint32_t *kept;                       // [n_groups][max_frames]
     uint8_t *body;                        // [n_groups][max_frames][max_len] or nullptr
@@ -406,7 +407,7 @@ struct FramesFecParams {
     unsigned n_groups;
     unsigned max_frames;                  // n_groups * max_frames < 2^31
     unsigned frame_symbols;               // N
-    unsigned steps;                       // St = floor(N bits / 2)
+    unsigned steps;                       // St of the mode: the greatest T with Nt(T) <= Cu
     unsigned row_bytes;                   // Bd = (St - 6) / 8
     unsigned max_len;                     // Bd - len_bytes - crc_bytes
     int len_bytes;                        // h
@@ -417,6 +418,7 @@ struct FramesFecParams {
     uint8_t *rows;                        // [n_groups][max_frames][row_bytes]
     struct ::demod_frame_decode *decode;  // [n_groups][max_frames] (struct: demod.h has a function of the name)
     unsigned long long *work;             // [waves of the launch][steps]
+    unsigned fec;                         // the mode (fec_map.h); DEMOD_FEC_CONV_K7: the map is the identity
 };
 hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s);
 
@@ -454,7 +456,7 @@ struct RxCollectParams {
     unsigned n_streams;
     unsigned max_frames;                  // n_streams * max_frames < 2^31
     unsigned max_len;
-    int len_bytes, crc_bytes, bits, phases, sync_len, fec_depth;   // as FramesCheckParams
+    int len_bytes, crc_bytes, bits, phases, sync_len, fec_depth, fec;   // as FramesCheckParams
     ::demod_rx_frame *frames;             // [n_streams max_frames]
     uint8_t *bodies;                      // [n_streams max_frames max_len]
     ::demod_rx_summary *summary;
@@ -493,7 +495,7 @@ struct TxParams {
     unsigned n_bytes;
     unsigned max_frames;                  // n_streams * max_frames < 2^31
     unsigned max_len, gap;
-    int len_bytes, crc_bytes, fec;        // h, c, 0 or DEMOD_FEC_CONV_K7
+    int len_bytes, crc_bytes, fec;        // h, c, 0 or the coded mode (fec_map.h)
     unsigned poly, init;                  // as FramesCheckParams
     unsigned xpow8[kCrcPowBits];
     ::demod_tx_place *place;              // [n_streams][max_frames]

@@ -27,7 +27,7 @@ static bool tx_shape(const demod_cfg_t *cfg, const demod_tx_cfg_t *x, size_t S, 
         if (x->idle[i] >= K) return false;
     if (x->len_bytes != 1 && x->len_bytes != 2) return false;
     if (x->crc != DEMOD_CRC16_CCITT_FALSE && x->crc != DEMOD_CRC32_MPEG2) return false;
-    if (x->fec != 0 && x->fec != DEMOD_FEC_CONV_K7) return false;
+    if (x->fec != 0 && !fec_mode_valid(x->fec)) return false;
     if (x->fec && (K & (K - 1)) != 0) return false;
     const uint32_t most = x->len_bytes == 1 ? 255u : (uint32_t)DEMOD_MAX_FRAME_PAYLOAD;
     if (x->max_len > most) return false;

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "../../include/demod.h"
+#include "fec_map.h"
 
 /* bits, or a negative code for what the format or K rules out */
 static int tx_format_bits(const demod_tx_cfg_t *x, uint32_t k)
@@ -17,7 +18,7 @@ static int tx_format_bits(const demod_tx_cfg_t *x, uint32_t k)
     if (x->sync_len < 1 || x->sync_len > DEMOD_MAX_SYNC) return DEMOD_BAD_ARG;
     if (x->len_bytes != 1 && x->len_bytes != 2) return DEMOD_BAD_ARG;
     if (x->crc != DEMOD_CRC16_CCITT_FALSE && x->crc != DEMOD_CRC32_MPEG2) return DEMOD_BAD_ARG;
-    if (x->fec != 0 && x->fec != DEMOD_FEC_CONV_K7) return DEMOD_BAD_ARG;
+    if (x->fec != 0 && !fec_mode_valid(x->fec)) return DEMOD_BAD_ARG;
     if (x->fec && (k & (k - 1)) != 0) return DEMOD_BAD_ARG;
     return demod_bits_per_symbol(k);
 }
@@ -29,7 +30,7 @@ long long demod_tx_frame_symbol_count(const demod_tx_cfg_t *x, uint32_t k, size_
     if (len > x->max_len) return DEMOD_FRAME_TOO_LARGE;
     long long sp;
     if (x->fec) {
-        sp = demod_coded_frame_symbols(len, (int)x->len_bytes, (int)x->crc, bits);
+        sp = demod_fec_frame_symbols(len, (int)x->len_bytes, (int)x->crc, bits, (int)x->fec);
     } else {
         const long long n = demod_checked_frame_size(len, (int)x->len_bytes, (int)x->crc);
         sp = n < 0 ? n : (8 * n + bits - 1) / bits;
@@ -49,10 +50,12 @@ long long demod_tx_frame_symbols(const demod_tx_cfg_t *x, uint32_t k, const uint
     if ((size_t)A > cap) return DEMOD_BUFFER_TOO_SMALL;
     const int bits = demod_bits_per_symbol(k);
     /* the frame's bytes, with a 0 byte behind them: the last symbol's missing bits */
-    uint8_t bytes[(2 * (8 * (2 + DEMOD_MAX_FRAME_PAYLOAD + 4) + 6) + 7) / 8 + 1];
+    /* (sized by rate 1/2, the most bits, and one interleaver block of rounding) */
+    uint8_t bytes[(2 * (8 * (2 + DEMOD_MAX_FRAME_PAYLOAD + 4) + 6) + 7) / 8 +
+                  DEMOD_FEC_IL_ROWS * DEMOD_FEC_IL_COLS / 8 + 1];
     memset(bytes, 0, sizeof(bytes));
-    const int nb = x->fec ? demod_coded_frame_encode(data, len, (int)x->len_bytes, (int)x->crc, bytes,
-                                                     sizeof(bytes) - 1)
+    const int nb = x->fec ? demod_fec_frame_encode(data, len, (int)x->len_bytes, (int)x->crc, (int)x->fec,
+                                                   bytes, sizeof(bytes) - 1)
                           : demod_checked_frame_encode(data, len, (int)x->len_bytes, (int)x->crc, bytes,
                                                        sizeof(bytes) - 1);
     if (nb < 0) return nb;

@@ -1,14 +1,17 @@
 // frames_fec.hip — coded frames (include/demod.h "coded frames", DESIGN.md §4.9
 // "Coded frames"): the soft values of the rows a frame scan listed, from the
 // detector's per-tone powers, and their soft-decision Viterbi decode under the
-// constraint-length-7, rate-1/2 code 0171/0133. The 64 trellis states are one
-// wave: lane = state. Groups and rows as frames_check.hip: group g owns rows
+// constraint-length-7, rate-1/2 code 0171/0133, in order or punctured to 2/3 or
+// 3/4 and interleaved (fec_map.h: the trellis does not change, a soft value's
+// place on the air does). The 64 trellis states are one wave: lane = state. Groups and rows as frames_check.hip: group g owns rows
 // g max_frames + i, i < nw_g = min(res[g].n_written, max_frames), the count
 // read and clamped here; wave c of a group's wpg waves takes rows c, c + wpg, ..
 // One launch, no atomics; every output byte is a function of the inputs alone
 // (demod_fec.c's demod_coded_frame_decode restates it on the host).
 //
-//  soft     64 values at a time, one per lane: value m = j bits + b of the row
+//  soft     64 values at a time, one per lane: trellis value m sits at air
+//           position a(m) (a = m without a map; a punctured m is 0 and reads
+//           nothing); air value a = j bits + b of the row
 //           reads the K powers of window base + window + (L + j) R and keeps
 //           the largest with bit b clear and with bit b set. A window at or
 //           past n_windows is an erasure (0) and is not read.
@@ -38,11 +41,19 @@ constexpr int kFecLanes = 64;
 constexpr int kFecWaves = kAcqThreads / kFecLanes;
 constexpr unsigned kFecPass = kFecLanes / 2;   // steps of one pass: 64 soft values
 
-// soft value m of a row whose symbol 0 of the word sits at window bw
+// trellis soft value m of a row whose symbol 0 of the word sits at window bw.
+// MAPPED (fec_map.h): m is kept or not, then its code index, then its air
+// position a < Cu <= N bits; a punctured m is 0 and loads nothing. Not MAPPED
+// (DEMOD_FEC_CONV_K7 alone): a = m, and the code is what it was without a map.
+template <bool MAPPED>
 static __device__ __forceinline__ int fec_soft(const FramesFecParams &p, bool live,
                                                unsigned long long bw, unsigned m)
 {
     if (!live || m >= 2u * p.steps) return 0;
+    if (MAPPED) {
+        m = fec_air_of_mother(p.fec, m);
+        if (m == FEC_MAP_NONE) return 0;
+    }
     const unsigned bits = (unsigned)p.bits, j = m / bits, b = m - j * bits;   // j < N
     const unsigned long long w = bw + ((unsigned long long)p.sync_len + j) * (unsigned)p.phases;
     if (w >= p.n_windows) return 0;
@@ -67,11 +78,12 @@ struct FecLane {
 };
 
 // steps t .. t + count - 1, count <= kFecPass and t + count <= St
+template <bool MAPPED>
 static __device__ __forceinline__ void fec_steps(const FramesFecParams &p, const FecLane &c, bool live,
                                                  unsigned long long bw, unsigned t, unsigned count,
                                                  int &M, unsigned long long *slot, int lane)
 {
-    const int q = fec_soft(p, live && (unsigned)lane < 2u * count, bw, 2u * t + (unsigned)lane);
+    const int q = fec_soft<MAPPED>(p, live && (unsigned)lane < 2u * count, bw, 2u * t + (unsigned)lane);
     unsigned long long mine = 0;
 #pragma unroll 4
     for (unsigned i = 0; i < count; ++i) {
@@ -113,6 +125,7 @@ static __device__ __forceinline__ unsigned long long fec_trace(const unsigned lo
     return acc;
 }
 
+template <bool MAPPED>
 __global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecParams p, unsigned wpg)
 {
     const int wave = threadIdx.x / kFecLanes, lane = threadIdx.x % kFecLanes;
@@ -141,7 +154,7 @@ __global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecPar
         const unsigned long long bw = live ? base + window : 0;
         int M = lane == 0 ? 0 : -(1 << 28);
         for (unsigned t = 0; t < t0; t += kFecPass)
-            fec_steps(p, c, live, bw, t, t0 - t < kFecPass ? t0 - t : kFecPass, M, slot, lane);
+            fec_steps<MAPPED>(p, c, live, bw, t, t0 - t < kFecPass ? t0 - t : kFecPass, M, slot, lane);
         __threadfence_block();
         int mx = M;
         for (int d = kFecLanes / 2; d > 0; d >>= 1) {
@@ -163,7 +176,7 @@ __global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecPar
             const unsigned n = h + len + (unsigned)p.crc_bytes;             // <= row_bytes
             const unsigned T = 8u * n + 6u > t0 ? 8u * n + 6u : t0;         // <= St
             for (unsigned t = t0; t < T; t += kFecPass)
-                fec_steps(p, c, live, bw, t, T - t < kFecPass ? T - t : kFecPass, M, slot, lane);
+                fec_steps<MAPPED>(p, c, live, bw, t, T - t < kFecPass ? T - t : kFecPass, M, slot, lane);
             __threadfence_block();
             fec_trace(slot, T, 0u, row, n, lane);
             out.metric = __builtin_amdgcn_readfirstlane(M);   // lane 0: state 0
@@ -178,7 +191,10 @@ hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s)
 {
     const unsigned wpg = fec_waves_per_group(p.n_groups, p.max_frames);
     const unsigned long long blocks = ((unsigned long long)p.n_groups * wpg + kFecWaves - 1) / kFecWaves;
-    hipLaunchKernelGGL(frames_decode_kernel, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
+    if (fec_mode_mapped(p.fec))
+        hipLaunchKernelGGL(frames_decode_kernel<true>, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
+    else
+        hipLaunchKernelGGL(frames_decode_kernel<false>, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
     return hipGetLastError();
 }
 

@@ -18,7 +18,8 @@
 //           c + wpg, .. (wave-uniform). len || data || CRC in the wave's LDS,
 //           the CRC by the check's lane-split scheme (crc_ops.h), then lane j
 //           writes symbols j, j + 64, ..: the word, the payload symbols, the
-//           gap's idle symbols. A coded bit m reads the information bits
+//           gap's idle symbols. An air bit goes back through the mode's map
+//           (fec_map.h) to its mother bit m, which reads the information bits
 //           (m >> 1) - 6 .. m >> 1 alone: the encoder has no serial step.
 //  phase    one workgroup per stream, 1 to 16 waves by the symbols a pull can
 //           touch: PHI of every symbol, a two-level uint32 prefix sum of n
@@ -36,6 +37,7 @@
 //           next pull reads it there.
 #include "../../include/demod.h"
 #include "crc_ops.h"
+#include "fec_map.h"
 #include "synth_ops.h"
 
 namespace fskd {
@@ -87,14 +89,15 @@ static __device__ __forceinline__ TxState tx_load(const TxParams &p, unsigned s)
 }
 
 // Sp(len): the payload symbols of a frame of len data bytes
-static __device__ __forceinline__ unsigned tx_payload_symbols(const TxParams &p, unsigned len, unsigned &steps)
+// (coded: Sc of the mode; kept: Nt(T), the frame's code bits, 0 without a code)
+static __device__ __forceinline__ unsigned tx_payload_symbols(const TxParams &p, unsigned len, unsigned &kept)
 {
     const unsigned nb = (unsigned)p.len_bytes + len + (unsigned)p.crc_bytes, bits = (unsigned)p.bits;
-    steps = 0;
+    kept = 0;
     if (!p.fec) return (8 * nb + bits - 1) / bits;
     const unsigned body = 8 * nb + 6, least = 8 * (unsigned)p.len_bytes + DEMOD_FEC_DEPTH;
-    steps = body > least ? body : least;
-    return (2 * steps + bits - 1) / bits;
+    kept = fec_kept_bits((unsigned)p.fec, body > least ? body : least);
+    return (fec_air_bits((unsigned)p.fec, kept) + bits - 1) / bits;
 }
 
 __global__ __launch_bounds__(kTxThreads) void tx_plan_kernel(TxParams p)
@@ -114,8 +117,8 @@ __global__ __launch_bounds__(kTxThreads) void tx_plan_kernel(TxParams p)
         const bool in = i < cnt;
         const unsigned len = in ? p.records[row0 + i].length : 0u;
         const bool valid = in && len <= p.max_len;
-        unsigned steps, A = 0;
-        if (valid) A = p.sync_len + tx_payload_symbols(p, len, steps);
+        unsigned kept, A = 0;
+        if (valid) A = p.sync_len + tx_payload_symbols(p, len, kept);
         const unsigned long long a = valid ? (unsigned long long)A + p.gap : 0ull;
         unsigned long long x = a;
         for (int d = 1; d < 64; d <<= 1) {
@@ -192,8 +195,8 @@ __global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsign
         if (lane < (int)cb) buf[n + lane] = (uint8_t)(crc >> (8 * (cb - 1 - (unsigned)lane)));
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        unsigned steps;
-        const unsigned A = L + tx_payload_symbols(p, len, steps);
+        unsigned kept;
+        const unsigned A = L + tx_payload_symbols(p, len, kept);
         const unsigned total = A + p.gap;            // <= C
         const unsigned sm = (unsigned)(pl.start % C);
         const unsigned long long i0 = pl.start % p.idle_len;
@@ -211,9 +214,11 @@ __global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsign
             } else {
                 sym = 0;
                 for (unsigned b = 0; b < bits; ++b) {
-                    const unsigned m = (j - L) * bits + b;
+                    // air bit a -> code index (the interleaver is its own inverse) -> mother bit
+                    const unsigned ci = fec_interleave((unsigned)p.fec, (j - L) * bits + b);
                     unsigned v = 0;
-                    if (m < 2 * steps) {
+                    if (ci < kept) {   // else a pad position of the last block or symbol
+                        const unsigned m = fec_mother_bit((unsigned)p.fec, ci);
                         // the register after step m >> 1: information bits lo .. lo + 6, the newest lowest
                         const int lo = (int)(m >> 1) - 6, B0 = lo >> 3;
                         const unsigned w = ((B0 >= 0 && (unsigned)B0 < nb ? buf[B0] : 0u) << 8) |

@@ -845,7 +845,15 @@ int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, cons
  * coded bit would otherwise ask for a tone that does not exist): every entry
  * that takes K refuses another with DEMOD_BAD_ARG.
  *
- * The code (DEMOD_FEC_CONV_K7, the only one): constraint length 7, rate 1/2,
+ * `fec` is a bit field. The low nibble names the code, DEMOD_FEC_CONV_K7; at
+ * most one of DEMOD_FEC_RATE_2_3 and DEMOD_FEC_RATE_3_4 punctures it, and
+ * DEMOD_FEC_INTERLEAVE spreads its bits over 16 x 16 blocks ("punctured and
+ * interleaved" below). Six values are valid, 1 | {0, 0x10, 0x20} | {0, 0x40};
+ * every entry that takes `fec` refuses another with DEMOD_BAD_ARG (0, no
+ * code, where it is accepted). DEMOD_FEC_CONV_K7 alone is rate 1/2 with the
+ * coded bits on the air in order, and what follows describes it.
+ *
+ * The mother code: constraint length 7, rate 1/2,
  * generators 0171 and 0133 (octal). reg_-1 = 0, reg_t = ((reg_t-1 << 1) | u_t)
  * & 0x7F, v_2t = parity(reg_t & 0171), v_2t+1 = parity(reg_t & 0133); the state
  * after step t is reg_t & 63. The information bits u_t are the checked frame
@@ -890,8 +898,33 @@ int demod_frames_checked(demod_t *st, const int16_t *pcm, size_t n_windows, cons
  *            M_T[0], steps = T.
  *
  * Row bytes at or past what is written, and rows i >= nw_g, are left alone.
+ *
+ * Punctured and interleaved. Both are one map between the trellis's coded-bit
+ * index and the position on the air; T(len), the encoder, the tail and the
+ * soft-value expression do not change. Mother bit m = 2 t + v (v = 0:
+ * generator 0171, v = 1: 0133). Puncturing is by step phase: rate 2/3 (period
+ * 2) keeps v0 v1 at phase 0 and v1 at phase 1; rate 3/4 (period 3) keeps v0 v1
+ * at phase 0, v0 at phase 1 and v1 at phase 2 (free distance 6 and 5; the
+ * mother code's is 10). T steps keep Nt(T) bits: 2 T, 3 floor(T / 2) + 2 (T
+ * mod 2) or 4 floor(T / 3) + {0, 2, 3}[T mod 3]. A kept bit's code index is i
+ * = Nt(t) + its rank among step t's kept bits. With DEMOD_FEC_INTERLEAVE, i =
+ * r 16 + c of each block of DEMOD_FEC_IL_ROWS x DEMOD_FEC_IL_COLS code bits
+ * goes to air position a = c 16 + r (the two nibbles of the low byte swapped:
+ * an involution, the same function at both ends); otherwise a = i. A frame
+ * is Na(len) = Nt(T(len)) air bits, rounded up to a multiple of 256 with the
+ * flag; positions no kept bit maps to carry 0 and are never read; Sc = ceil(Na
+ * / bits). A row of C = N bits soft values uses Cu = C (C & ~255 with the
+ * flag); St is the greatest T with Nt(T) <= Cu; Bd, max_len and the refusals
+ * follow from St as above (an interleaved row shorter than one block is
+ * refused). Trellis soft value q_m is the soft value at air position a(m), or
+ * 0 where m is punctured, which is not read.
  */
-#define DEMOD_FEC_CONV_K7       1
+#define DEMOD_FEC_CONV_K7       1      /* low nibble: the code. Alone: rate 1/2, in order */
+#define DEMOD_FEC_RATE_2_3      0x10
+#define DEMOD_FEC_RATE_3_4      0x20   /* both rate flags together: refused */
+#define DEMOD_FEC_INTERLEAVE    0x40
+#define DEMOD_FEC_IL_ROWS       16
+#define DEMOD_FEC_IL_COLS       16     /* block = 256 air bits */
 #define DEMOD_FEC_DEPTH         64
 
 #define DEMOD_DECODE_OK         0
@@ -932,6 +965,24 @@ int demod_soft_bits(const float *powers, uint32_t k, int8_t *soft);
 int demod_coded_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, uint8_t *row,
                              size_t cap, demod_frame_decode_t *decode);
 
+/* The same five with a mode ("punctured and interleaved"); the functions
+ * above equal them at fec == DEMOD_FEC_CONV_K7. Each refuses an invalid fec
+ * with DEMOD_BAD_ARG.
+ *   air_index      the air position of mother bit m < 2^31, or -1 when it is
+ *                  punctured (or fec is invalid)
+ *   frame_symbols  Sc of the mode
+ *   frame_encode   the frame in air order, ceil(Na / 8) bytes, pad bits 0
+ *   row_bytes      Bd of the mode's St
+ *   frame_decode   soft[0 .. n_soft) in air order, n_soft = C: the reference of
+ *                  demod_frames_decode_async in every mode, bit for bit */
+long long demod_fec_air_index(int fec, size_t m);
+long long demod_fec_frame_symbols(size_t len, int len_bytes, int crc, int bits, int fec);
+int demod_fec_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, int fec, uint8_t *out,
+                           size_t cap);
+long long demod_fec_row_bytes(size_t frame_symbols, int bits, int len_bytes, int fec);
+int demod_fec_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, int fec, uint8_t *row,
+                           size_t cap, demod_frame_decode_t *decode);
+
 /* Bytes of d_work: the launch's waves (min(max_frames, max(16384 / n_groups,
  * 1)) per group, as the check caps them) x St x 8, the survivor words of each
  * wave's current row. 0 when the configuration is invalid, K is not a power of
@@ -939,6 +990,12 @@ int demod_coded_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, i
  * max_frames >= 2^31, or frame_symbols is 0 or >= 2^31. No device needed. */
 size_t demod_frames_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
                                           size_t frame_symbols);
+
+/* The same with the mode's St, which a punctured row raises to as much as 3/4
+ * of C: what demod_frames_decode_async asks of work_bytes. Equals the function
+ * above at fec == DEMOD_FEC_CONV_K7; 0 also for an invalid fec. */
+size_t demod_fec_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
+                                       size_t frame_symbols, int fec);
 
 /*
  * Enqueued on `stream`: one launch whatever the counts are. Nothing is
@@ -952,9 +1009,9 @@ size_t demod_frames_decode_workspace_size(const demod_cfg_t *cfg, size_t n_group
  * [n_groups][max_frames][Bd], d_decode [n_groups][max_frames]. Returns DEMOD_OK
  * once enqueued; DEMOD_BAD_ARG, before any launch, for what
  * demod_frames_check_async refuses about its own arguments and: K not a power
- * of two, the refused row shapes above, fec not DEMOD_FEC_CONV_K7, a NULL
+ * of two, the refused row shapes above, a fec outside the six modes, a NULL
  * d_mags, d_rows, d_decode or d_work, a misaligned d_decode (4 bytes), d_work
- * or d_first (8 bytes), work_bytes below demod_frames_decode_workspace_size,
+ * or d_first (8 bytes), work_bytes below demod_fec_decode_workspace_size,
  * n_windows >= 2^31, (sync_len + frame_symbols) R >= 2^31.
  */
 int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, const float *d_mags,
@@ -1070,7 +1127,7 @@ int demod_streams_push_packets(demod_streams_t *ms, demod_decode_fn decode, void
  *              windows of Y go: base += d, dropped += d. X = Y, fill = len(Y).
  *   2 scan     X is scanned exactly as segment {first = slot, count = fill} of
  *              "segmented frame scan" (group = stream). fec == 0: packed rows,
- *              then "checked frames". fec == DEMOD_FEC_CONV_K7: no rows, then
+ *              then "checked frames". A coded mode: no rows, then
  *              the decode and the coded check of "coded frames".
  *   3 collect  For the OK rows end_j = base + window_j + (L + S_j) R, S_j the
  *              span the check's `covered` uses (plain or coded). A kept row i
@@ -1120,7 +1177,7 @@ typedef struct demod_rx_cfg {
     uint32_t sync_len, max_errors;
     uint32_t frame_symbols;            /* N */
     uint32_t len_bytes, crc;           /* h; DEMOD_CRC16_CCITT_FALSE or DEMOD_CRC32_MPEG2 */
-    uint32_t fec;                      /* 0 or DEMOD_FEC_CONV_K7 */
+    uint32_t fec;                      /* 0 or one of the six coded modes */
     uint32_t max_frames;               /* rows per stream and push */
     uint32_t ring_windows;             /* C */
 } demod_rx_cfg_t;
@@ -1149,7 +1206,7 @@ typedef struct demod_rx_sizes {
     uint64_t ring_sym_bytes;           /* one [S][C] symbol ring */
     uint64_t ring_mag_bytes;           /* one [S][C][K] power ring */
     uint64_t scan_work_bytes;          /* demod_frames_segments_workspace_size(cfg, S, S C) */
-    uint64_t decode_work_bytes;        /* demod_frames_decode_workspace_size, 0 with fec 0 */
+    uint64_t decode_work_bytes;        /* demod_fec_decode_workspace_size, 0 with fec 0 */
     uint64_t collect_work_bytes;       /* demod_rx_collect_workspace_size */
     uint64_t frames_bytes;             /* d_frames: S max_frames records */
     uint64_t bodies_bytes;             /* d_bodies: S max_frames max_len */
@@ -1276,9 +1333,9 @@ int demod_rx_push(demod_rx_t *rx, const int16_t *const *pcm, const size_t *n_fra
  *   fec == 0                 Sp = ceil(8 (h + len + c) / bits): demod_unpack_symbols
  *                            of demod_checked_frame_encode's bytes, the missing
  *                            bits of the last symbol 0;
- *   fec == DEMOD_FEC_CONV_K7 Sp = demod_coded_frame_symbols(..): the same of
- *                            demod_coded_frame_encode's bytes, coded bits at or
- *                            past 2 T(len) 0. K must be a power of two.
+ *   a coded mode             Sp = demod_fec_frame_symbols(.., fec): the same of
+ *                            demod_fec_frame_encode's bytes, air bits that no
+ *                            kept coded bit maps to 0. K must be a power of two.
  * The idle symbol of stream-absolute symbol index q is idle[q mod idle_len].
  *
  * State per stream (all 0 after create or reset): head is the symbol being
@@ -1332,7 +1389,7 @@ typedef struct demod_tx_cfg {          /* 184 bytes, no padding */
     uint8_t  sync[DEMOD_MAX_SYNC];     /* the word, sync_len symbols, each < K */
     uint32_t sync_len;                 /* L, 1 .. DEMOD_MAX_SYNC */
     uint32_t len_bytes, crc;           /* h; DEMOD_CRC16_CCITT_FALSE or DEMOD_CRC32_MPEG2 */
-    uint32_t fec;                      /* 0 or DEMOD_FEC_CONV_K7 */
+    uint32_t fec;                      /* 0 or one of the six coded modes */
     uint32_t max_len;                  /* <= min(256^h - 1, DEMOD_MAX_FRAME_PAYLOAD) */
     uint32_t gap;                      /* idle symbols behind each frame */
     uint8_t  idle[DEMOD_MAX_SYNC];     /* the idle pattern, idle_len symbols, each < K */

@@ -1,0 +1,209 @@
+"""Numpy restatement of the coded modes (include/demod.h "punctured and
+interleaved"): the reference of tests/test_fec_modes_cpu.py and
+tests/test_gpu_fec_modes.py. Nothing here calls the library.
+
+A mode is 1 | {0, 0x10 (rate 2/3), 0x20 (rate 3/4)} | {0, 0x40 (interleaved)}.
+Mother bit m = 2 t + v of the rate-1/2 code 0171/0133 is kept or punctured by
+the phase of its step; a kept bit's code index is i = Nt(t) + its rank among
+step t's kept bits; with the interleaver code index r 16 + c of each block of
+256 sits at air position c 16 + r.
+
+A mode is decoded by re-ordering the air soft values into a rate-1/2 trellis
+array of 2 St values, zeros at the punctured positions, and handing that to
+the existing tests/frames_fec_ref.py decoder: the decoder the earlier tests
+hold to a maximum-likelihood reference is the oracle here too.
+"""
+import numpy as np
+
+import frames_check_ref as C
+import frames_fec_ref as X
+
+CONV_K7, RATE_2_3, RATE_3_4, INTERLEAVE = 1, 0x10, 0x20, 0x40
+BLOCK = 256
+MODES = (0x01, 0x11, 0x21, 0x41, 0x51, 0x61)
+NEW_MODES = MODES[1:]
+BAD_MODES = (2, 0x10, 0x31, 0x81)
+# the mother bits v kept at each step phase
+KEEP = {0: ((0, 1),), RATE_2_3: ((0, 1), (1,)), RATE_3_4: ((0, 1), (0,), (1,))}
+
+
+def pattern(fec):
+    return KEEP[fec & 0x30]
+
+
+def kept_bits(fec, T):
+    """Nt(T), by counting."""
+    pat = pattern(fec)
+    return sum(len(pat[t % len(pat)]) for t in range(T))
+
+
+def steps_within(fec, Cu):
+    """St: the greatest T with Nt(T) <= Cu, by stepping."""
+    pat, T, n = pattern(fec), 0, 0
+    while n + len(pat[T % len(pat)]) <= Cu:
+        n += len(pat[T % len(pat)])
+        T += 1
+    return T
+
+
+def interleave(fec, i):
+    if not fec & INTERLEAVE:
+        return i
+    blk, r, c = i // BLOCK, (i % BLOCK) // 16, i % 16
+    return blk * BLOCK + c * 16 + r
+
+
+def air_map(fec, T):
+    """int64 [2 T]: the air position of each mother bit of T steps, -1 where punctured."""
+    pat = pattern(fec)
+    out = np.full(2 * T, -1, np.int64)
+    i = 0
+    for t in range(T):
+        for v in pat[t % len(pat)]:
+            out[2 * t + v] = interleave(fec, i)
+            i += 1
+    return out
+
+
+def air_bits(fec, T):
+    """Na: Nt(T), rounded up to whole blocks with the interleaver."""
+    n = kept_bits(fec, T)
+    return -(-n // BLOCK) * BLOCK if fec & INTERLEAVE else n
+
+
+def frame_symbols(length, h, kind, bits, fec):
+    """Sc of the mode."""
+    return -(-air_bits(fec, X.steps(length, h, kind)) // bits)
+
+
+def encode_air(info, T, fec):
+    """The Na air bits of the information bytes `info` over T steps, one per element."""
+    mother = X.encode_bits(info, T)
+    amap = air_map(fec, T)
+    out = np.zeros(air_bits(fec, T), np.uint8)
+    out[amap[amap >= 0]] = mother[amap >= 0]
+    return out
+
+
+def encode(data, h, kind, fec):
+    """The frame's bytes in air order, or None where the checked frame is refused."""
+    frame = C.encode(data, h, kind)
+    if frame is None:
+        return None
+    return np.packbits(encode_air(frame, X.steps(len(data), h, kind), fec)).tobytes()
+
+
+def row_shape(N, bits, h, kind, fec):
+    """(St, Bd, max_len) of rows of N symbols, or None where the row is refused."""
+    Cc = N * bits
+    St = steps_within(fec, Cc // BLOCK * BLOCK if fec & INTERLEAVE else Cc)
+    if St < 8 * h + X.DEPTH:
+        return None
+    Bd = (St - 6) // 8
+    max_len = Bd - h - C.CRC_BYTES[kind]
+    if max_len < 0 or max_len > 4096:
+        return None
+    return St, Bd, max_len
+
+
+def symbols_for(max_len, bits, h, kind, fec):
+    """The smallest N whose rows hold frames of max_len data bytes."""
+    N = frame_symbols(max_len, h, kind, bits, fec)
+    while row_shape(N, bits, h, kind, fec) is None or row_shape(N, bits, h, kind, fec)[2] < max_len:
+        N += 1
+    return N
+
+
+def trellis_soft(soft, fec):
+    """Air-order soft values int8 [.., C] -> the rate-1/2 trellis array int8 [.., 2 St]."""
+    soft = np.asarray(soft, np.int8)
+    Cc = soft.shape[-1]
+    St = steps_within(fec, Cc // BLOCK * BLOCK if fec & INTERLEAVE else Cc)
+    amap = air_map(fec, St)
+    out = np.zeros(soft.shape[:-1] + (2 * St,), np.int8)
+    out[..., amap >= 0] = soft[..., amap[amap >= 0]]
+    return out
+
+
+def decode_rows(soft, h, kind, fec):
+    """soft int8 [n][C] in air order: frames_fec_ref.decode_rows of the trellis array."""
+    return X.decode_rows(trellis_soft(soft, fec), h, kind)
+
+
+def decode(soft, h, kind, fec):
+    """One row: (the bytes written, its DECODE_DTYPE record)."""
+    return X.decode(trellis_soft(soft, fec), h, kind)
+
+
+def edge_lengths(max_len, h, kind, fec):
+    """0, 1, either side of 8 n + 6 = 8 h + 64, max_len, and the lengths whose
+    Nt(T) is 255, 256 and 257 mod 256: the first length up to max_len that hits
+    each residue, or where the mode's Nt never does (2 T = 16 n + 12 cannot)
+    the first that comes nearest to it."""
+    c = C.CRC_BYTES[kind]
+    out = {n for n in (0, 1, 7 - c, 8 - c, max_len) if 0 <= n <= max_len}
+    res = [kept_bits(fec, X.steps(n, h, kind)) % BLOCK for n in range(max_len + 1)]
+    for want in (255, 0, 1):
+        out.add(min(range(max_len + 1), key=lambda n: min((res[n] - want) % BLOCK, (want - res[n]) % BLOCK)))
+    return sorted(out)
+
+
+def scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames=None):
+    """rx_ref.scan_check in a coded mode: the scan of (sym, P) as one segment,
+    the mode's decode of its rows and the coded check with the mode's span."""
+    import frames_ref as F
+    import frames_segments_ref as FS
+    sym = np.asarray(sym, np.uint8).reshape(-1)
+    P = np.asarray(P, np.float32)
+    K, L = P.shape[1], len(sync)
+    bits = F.bits_per_symbol(K)
+    hits, _, _, res = FS.frames_segments(sym, P, R, [0], [sym.size], sync, max_errors, N, max_frames)[0]
+    _, Bd, _ = row_shape(N, bits, h, kind, fec)
+    rows = np.zeros((len(hits), Bd), np.uint8)
+    if len(hits):
+        soft = X.soft_bits(P)
+        q = np.stack([X.row_soft(soft, sym.size, 0, w, L, R, N) for w in hits["window"]])
+        written, _ = decode_rows(q, h, kind, fec)
+        for i, b in enumerate(written):
+            rows[i, :len(b)] = np.frombuffer(b, np.uint8)
+    return (hits,) + check_group(hits["window"], rows, L, R, bits, h, kind, fec) + (res,)
+
+
+def receiver(S, K, R, sync, max_errors, N, h, kind, fec, max_frames, ring):
+    """rx_ref.Rx in a coded mode: the same receiver, its scan-and-check and its
+    span replaced by the mode's for the length of each push."""
+    import rx_ref as RX
+
+    class ModeRx(RX.Rx):
+        def push(self, pieces):
+            old = RX.scan_check, RX.span
+            RX.scan_check = scan_check
+            RX.span = lambda length, bits, hh, kk, ff: frame_symbols(length, hh, kk, bits, ff)
+            try:
+                return super().push(pieces)
+            finally:
+                RX.scan_check, RX.span = old
+    return ModeRx(S, K, R, sync, max_errors, N, h, kind, fec, max_frames, ring)
+
+
+def check_group(windows, rows, L, R, bits, h, kind, fec):
+    """frames_fec_ref.check_group with the mode's span Sc."""
+    nw = len(windows)
+    check = np.zeros(nw, C.CHECK_DTYPE)
+    kept, bodies = [], []
+    reach = 0
+    for i in range(nw):
+        length, got, status = C.check_row(rows[i], h, kind)
+        covered = 0
+        if status == C.OK:
+            w = int(windows[i])
+            covered = int(reach > w)
+            reach = max(reach, (w + (L + frame_symbols(length, h, kind, bits, fec)) * R) & C.M64)
+            if not covered:
+                kept.append(i)
+                bodies.append(bytes(rows[i][h:h + length]))
+        check[i] = (length, got, status, covered)
+    summary = np.zeros((), C.SUMMARY_DTYPE)
+    summary["n_checked"], summary["n_valid"] = nw, int((check["status"] == C.OK).sum())
+    summary["n_kept"] = len(kept)
+    return check, np.array(kept, np.uint32), bodies, summary
