@@ -13,6 +13,8 @@ array of 2 St values, zeros at the punctured positions, and handing that to
 the existing tests/frames_fec_ref.py decoder: the decoder the earlier tests
 hold to a maximum-likelihood reference is the oracle here too.
 """
+import functools
+
 import numpy as np
 
 import frames_check_ref as C
@@ -31,8 +33,9 @@ def pattern(fec):
     return KEEP[fec & 0x30]
 
 
+@functools.lru_cache(maxsize=None)
 def kept_bits(fec, T):
-    """Nt(T), by counting."""
+    """Nt(T), by counting (each (mode, T) once: the receiver's reference asks per row)."""
     pat = pattern(fec)
     return sum(len(pat[t % len(pat)]) for t in range(T))
 
@@ -149,41 +152,16 @@ def edge_lengths(max_len, h, kind, fec):
 
 
 def scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames=None):
-    """rx_ref.scan_check in a coded mode: the scan of (sym, P) as one segment,
-    the mode's decode of its rows and the coded check with the mode's span."""
-    import frames_ref as F
-    import frames_segments_ref as FS
-    sym = np.asarray(sym, np.uint8).reshape(-1)
-    P = np.asarray(P, np.float32)
-    K, L = P.shape[1], len(sync)
-    bits = F.bits_per_symbol(K)
-    hits, _, _, res = FS.frames_segments(sym, P, R, [0], [sym.size], sync, max_errors, N, max_frames)[0]
-    _, Bd, _ = row_shape(N, bits, h, kind, fec)
-    rows = np.zeros((len(hits), Bd), np.uint8)
-    if len(hits):
-        soft = X.soft_bits(P)
-        q = np.stack([X.row_soft(soft, sym.size, 0, w, L, R, N) for w in hits["window"]])
-        written, _ = decode_rows(q, h, kind, fec)
-        for i, b in enumerate(written):
-            rows[i, :len(b)] = np.frombuffer(b, np.uint8)
-    return (hits,) + check_group(hits["window"], rows, L, R, bits, h, kind, fec) + (res,)
+    """rx_ref.scan_check, which takes a mode: the scan of (sym, P) as one
+    segment, the mode's decode of its rows and the coded check with the mode's span."""
+    import rx_ref as RX
+    return RX.scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames)
 
 
 def receiver(S, K, R, sync, max_errors, N, h, kind, fec, max_frames, ring):
-    """rx_ref.Rx in a coded mode: the same receiver, its scan-and-check and its
-    span replaced by the mode's for the length of each push."""
+    """rx_ref.Rx, which takes a mode."""
     import rx_ref as RX
-
-    class ModeRx(RX.Rx):
-        def push(self, pieces):
-            old = RX.scan_check, RX.span
-            RX.scan_check = scan_check
-            RX.span = lambda length, bits, hh, kk, ff: frame_symbols(length, hh, kk, bits, ff)
-            try:
-                return super().push(pieces)
-            finally:
-                RX.scan_check, RX.span = old
-    return ModeRx(S, K, R, sync, max_errors, N, h, kind, fec, max_frames, ring)
+    return RX.Rx(S, K, R, sync, max_errors, N, h, kind, fec, max_frames, ring)
 
 
 def check_group(windows, rows, L, R, bits, h, kind, fec):

@@ -1,7 +1,12 @@
 """Numpy restatement of the receiver (include/demod.h "receiver"): the reference
 of tests/test_rx_cpu.py and tests/test_gpu_rx.py, composed from
 frames_segments_ref (the scan of X as one segment), frames_check_ref (the plain
-check) and frames_fec_ref (soft values, decode, the coded check).
+check), frames_fec_ref (soft values) and fec_modes_ref (row shape, decode, span
+and the coded check of every coded mode; mode 1 is the rate-1/2 code).
+
+fec is 0 or a coded mode (fec_modes_ref.MODES) everywhere: span(), sizes(),
+row_symbols() and scan_check() are the one place that turns it into a span, a
+row shape or a decode, and collect(), Rx and one_shot() go through them.
 
 Per stream a run X of detector outputs, sym[i] and P[i][K], i < fill, window i
 being the stream's window base + i; with it keep, hold, dropped, cut_hits, all
@@ -27,6 +32,7 @@ demod_frames_checked / demod_frames_coded's kept frames on a whole recording.
 import numpy as np
 
 import acquire_ref
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as FEC
 import frames_ref as F
@@ -48,7 +54,7 @@ assert RESULT_DTYPE.itemsize == 560
 def span(length, bits, h, kind, fec):
     """S: the symbols a frame of `length` data bytes occupies behind its word."""
     if fec:
-        return FEC.coded_symbols(length, h, kind, bits)
+        return Z.frame_symbols(length, h, kind, bits, fec)
     return C.frame_symbols(h + length + C.CRC_BYTES[kind], bits)
 
 
@@ -67,7 +73,7 @@ def sizes(K, R, S, L, N, h, kind, fec, max_frames, ring):
     bits = F.bits_per_symbol(K)
     c = C.CRC_BYTES[kind]
     if fec:
-        St, B, max_len = FEC.row_shape(N, bits, h, kind)
+        St, B, max_len = Z.row_shape(N, bits, h, kind, fec)
         waves = min(max_frames, max(16384 // S, 1))
         decode = S * waves * St * 8
     else:
@@ -158,8 +164,8 @@ def collect(state, hits, results, check, kept, body, chk_summary, L, R, bits, h,
 # ---- scan and check of one run of windows ------------------------------------------
 
 def scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames=None):
-    """The scan of (sym, P) as one segment and the check (fec 0) or the decode
-    and the coded check of its rows. Returns (hits, check, kept, bodies, check
+    """The scan of (sym, P) as one segment and the check (fec 0) or the mode's
+    decode and coded check of its rows. Returns (hits, check, kept, bodies, check
     summary, scan result dict)."""
     sym = np.asarray(sym, np.uint8).reshape(-1)
     P = np.asarray(P, np.float32)
@@ -168,15 +174,15 @@ def scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames=None):
     hits, _, packed, res = FS.frames_segments(sym, P, R, [0], [sym.size], sync, max_errors, N, max_frames)[0]
     if not fec:
         return (hits,) + C.check_group(hits["window"], packed, L, R, bits, h, kind) + (res,)
-    _, Bd, _ = FEC.row_shape(N, bits, h, kind)
+    _, Bd, _ = Z.row_shape(N, bits, h, kind, fec)
     rows = np.zeros((len(hits), Bd), np.uint8)
     if len(hits):
         soft = FEC.soft_bits(P)
         q = np.stack([FEC.row_soft(soft, sym.size, 0, w, L, R, N) for w in hits["window"]])
-        written, _ = FEC.decode_rows(q, h, kind)
+        written, _ = Z.decode_rows(q, h, kind, fec)
         for i, b in enumerate(written):
             rows[i, :len(b)] = np.frombuffer(b, np.uint8)
-    return (hits,) + FEC.check_group(hits["window"], rows, L, R, bits, h, kind) + (res,)
+    return (hits,) + Z.check_group(hits["window"], rows, L, R, bits, h, kind, fec) + (res,)
 
 
 def one_shot(sym, P, R, sync, max_errors, N, h, kind, fec):
@@ -250,13 +256,13 @@ class Rx:
 def row_symbols(h, kind, fec, bits, max_len):
     """The smallest N whose rows hold frames of max_len data bytes."""
     if fec:
-        return FEC.symbols_for(max_len, bits, h, kind)
+        return Z.symbols_for(max_len, bits, h, kind, fec)
     return C.frame_symbols(h + max_len + C.CRC_BYTES[kind], bits)
 
 
 def frame_symbols(data, word, bits, h, kind, fec):
     """A frame on the air: the word, then the S symbols of its (coded) bytes."""
-    raw = FEC.encode(data, h, kind) if fec else C.encode(data, h, kind)
+    raw = Z.encode(data, h, kind, fec) if fec else C.encode(data, h, kind)
     return np.concatenate([np.asarray(word, np.uint8), C.unpack(raw, span(len(data), bits, h, kind, fec), bits)])
 
 

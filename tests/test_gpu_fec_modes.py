@@ -429,26 +429,29 @@ LINK_N, LINK_HOP, LINK_K, LINK_S, LINK_L, LINK_H, LINK_KIND = 1024, 256, 2, 3, 1
 LINK_LENS = (0, 24, 7)
 LINK_PACKET = 48000                  # a second of audio a push: a frame spans several pushes
 LINK_DROPS = (0, 100, 200)           # samples cut from the head of each stream: three window offsets
+LINK_SHAPE = (LINK_K, LINK_H, LINK_KIND)
+LINK_SHAPE_8 = (8, 2, C.CRC32)       # 3 bits a symbol: a 256-bit block ends inside a symbol
 
 
-def link_run(A, torch, fec, zero=None):
+def link_run(A, torch, fec, zero=None, shape=LINK_SHAPE):
     """Transmitter -> (samples on the host, `zero` = (frame, first payload
     symbol, symbols) zeroed in every stream) -> Receiver, in LINK_PACKET pushes.
-    Returns (datas, per stream (pushed samples, sizes), pushes: (records,
-    bodies), N, ring, the word)."""
-    R = LINK_N // LINK_HOP
+    shape: (K, h, CRC). Returns (datas, per stream (pushed samples, sizes),
+    pushes: (records, bodies), N, ring, the word)."""
+    K, h, kind = shape
+    bits = F.bits_per_symbol(K)
     rng = np.random.default_rng(4100 + fec)
-    word = rng.integers(0, LINK_K, LINK_L).astype(np.uint8)
+    word = rng.integers(0, K, LINK_L).astype(np.uint8)
     datas = [rng.integers(0, 256, ln).astype(np.uint8).tobytes() for ln in LINK_LENS]
     max_len, gap = max(LINK_LENS), 3
-    per = [LINK_L + Z.frame_symbols(len(dd), LINK_H, LINK_KIND, 1, fec) + gap for dd in datas]
-    N = Z.symbols_for(max_len, 1, LINK_H, LINK_KIND, fec)
+    per = [LINK_L + Z.frame_symbols(len(dd), h, kind, bits, fec) + gap for dd in datas]
+    N = Z.symbols_for(max_len, bits, h, kind, fec)
     symbols = 3 + sum(per) + N + 8
     total = -(-symbols * LINK_N // LINK_PACKET) * LINK_PACKET
     ring = total // LINK_HOP + 64
-    x = A.make_tx_cfg(word, LINK_H, LINK_KIND, fec, max_len, gap, (0, 1), 8000, 400, 77, sum(per) + 5, len(datas),
+    x = A.make_tx_cfg(word, h, kind, fec, max_len, gap, (0, 1), 8000, 400, 77, sum(per) + 5, len(datas),
                       LINK_PACKET)
-    freqs = T.loop_tones(LINK_K)
+    freqs = T.loop_tones(K)
     pcm = [[] for _ in range(LINK_S)]
     with A.Transmitter(LINK_S, x, n=LINK_N, hop=LINK_HOP, freqs=freqs) as tx:
         for at in range(0, total, LINK_PACKET):
@@ -465,7 +468,7 @@ def link_run(A, torch, fec, zero=None):
         for s in range(LINK_S):
             pcm[s][a:a + cnt * LINK_N] = 0
     pcm = [p[drop:] for p, drop in zip(pcm, LINK_DROPS)]
-    rxcfg = A.make_rx_cfg(word, 2, N, LINK_H, LINK_KIND, fec, 8, ring)
+    rxcfg = A.make_rx_cfg(word, 2, N, h, kind, fec, 8, ring)
     pushes, sizes = [], [[] for _ in range(LINK_S)]
     with A.Receiver(LINK_S, rxcfg, n=LINK_N, hop=LINK_HOP, freqs=freqs) as rx:
         for at in range(0, total, LINK_PACKET):
@@ -478,17 +481,18 @@ def link_run(A, torch, fec, zero=None):
     return datas, list(zip(pcm, sizes)), pushes, N, ring, word
 
 
-def link_reference(A, fec, streams, N, ring, word):
+def link_reference(A, fec, streams, N, ring, word, shape=LINK_SHAPE):
     """fec_modes_ref.receiver on the device detector's own outputs, push by push."""
     import link_ref as LR
+    K, h, kind = shape
     R = LINK_N // LINK_HOP
     cuts = []
-    with A.Demodulator(n=LINK_N, hop=LINK_HOP, freqs=T.loop_tones(LINK_K)) as d:
+    with A.Demodulator(n=LINK_N, hop=LINK_HOP, freqs=T.loop_tones(K)) as d:
         for pcm, sizes in streams:
             W = (len(pcm) - LINK_N) // LINK_HOP + 1
             sym, P = d.batch(pcm[:(W - 1) * LINK_HOP + LINK_N], mags=True)
             cuts.append(LR.pieces(sym, P, sizes, LINK_N, LINK_HOP))
-    ref = Z.receiver(LINK_S, LINK_K, R, word, 2, N, LINK_H, LINK_KIND, fec, 8, ring)
+    ref = Z.receiver(LINK_S, K, R, word, 2, N, h, kind, fec, 8, ring)
     return [ref.push([cuts[s][i] for s in range(LINK_S)]) for i in range(len(cuts[0]))]
 
 
@@ -496,16 +500,27 @@ def delivered(pushes, s):
     return [b for fr, bodies in pushes for f, b in zip(fr, bodies) if int(f["stream"]) == s]
 
 
-@pytest.mark.parametrize("fec", [0x11, 0x41, 0x61])
-def test_link(A, torch, fec):
-    """Transmitter -> Receiver, 3 streams at three sample offsets: every push
-    equals the host reference on the same detector outputs, and every frame of
-    every stream comes back."""
-    datas, streams, pushes, N, ring, word = link_run(A, torch, fec)
-    for i, ((fr, bodies), (w_fr, w_bodies, _)) in enumerate(zip(pushes, link_reference(A, fec, streams, N, ring, word))):
+def link_holds(A, torch, fec, shape):
+    datas, streams, pushes, N, ring, word = link_run(A, torch, fec, shape=shape)
+    want = link_reference(A, fec, streams, N, ring, word, shape)
+    for i, ((fr, bodies), (w_fr, w_bodies, _)) in enumerate(zip(pushes, want)):
         assert fr.tobytes() == w_fr.tobytes() and bodies == w_bodies, ("push", i, fr, w_fr)
     for s in range(LINK_S):
         assert delivered(pushes, s) == datas, (hex(fec), s)
+
+
+@pytest.mark.parametrize("fec", [0x11, 0x41, 0x61, 0x21, 0x51])
+def test_link(A, torch, fec):
+    """Transmitter -> Receiver, 3 streams at three sample offsets, in every
+    mapped mode: every push equals the host reference on the same detector
+    outputs, and every frame of every stream comes back."""
+    link_holds(A, torch, fec, LINK_SHAPE)
+
+
+def test_link_8_tones(A, torch):
+    """The same in mode 0x51 at 8 tones, h 2, CRC-32: punctured and
+    interleaved, the 256-bit blocks ending inside a symbol."""
+    link_holds(A, torch, 0x51, LINK_SHAPE_8)
 
 
 @pytest.mark.parametrize("fec", [0x41, 0x01])

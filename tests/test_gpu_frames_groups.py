@@ -9,7 +9,9 @@ body kernel min(ceil(max_frames max_len / 64), most)). The cases here reach
 what the neighbouring files do not: most below max_frames, most = 1 and the
 16384 / S == 0 fallback, a last block with waves that leave beside live ones,
 the body kernel's stride loop running more than once, workspace slots above
-16383, and the chain segmented scan -> decode -> coded check behind 20000
+16383, the decode of a punctured and interleaved mode (tests/fec_modes_ref.py),
+whose workspace goes by the mode's step count, at two of these counts, and the
+chain segmented scan -> decode -> coded check behind 20000
 segments, nearly all of them empty.
 
 A group's outputs depend on its own content alone (test_groups and
@@ -29,11 +31,13 @@ import functools
 import numpy as np
 import pytest
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as X
 import frames_ref as F
 import frames_segments_ref as FS
 import guards as G
+import test_gpu_fec_modes as TM
 import test_gpu_frames_check as TC
 import test_gpu_frames_fec as TF
 import test_gpu_frames_segments as TS
@@ -409,6 +413,98 @@ def test_decode_fallback_tables(A, torch, handle):
         got = run_decode(A, torch, d, case, case["idx"], poison=poison, guard=True)
         TF.same(got, want, poison)
     print(f"decode S={S} max_frames={max_frames} K={K} R={Rn} with first[]: {stats}")
+
+
+# ---- Part 2: the mapped decode (fec_modes_ref) at the same group counts ---------------------------
+
+@functools.lru_cache(maxsize=2)
+def mapped_decode_case(S, max_frames, fec, Rn, tables):
+    """decode_case in a mapped mode at 2 tones: h 1, CRC-16, rows of one
+    interleaver block (N = 256 symbols at 1 bit, the least the mode accepts),
+    a pool of 40 rows (test_gpu_fec_modes.pool) and POOL distinct groups."""
+    K, h, kind, N = 2, 1, C.CRC16, Z.BLOCK
+    assert Z.row_shape(N, 1, h, kind, fec) is not None and Z.row_shape(N - 1, 1, h, kind, fec) is None
+    rng = np.random.default_rng(S * 10 + max_frames + fec)
+    P, starts = TM.pool(rng, K, Rn, h, kind, fec, N, 40)
+    W = len(P)
+    counts = stored_counts(rng, max_frames)
+    hits = np.zeros((POOL, max_frames), C.HIT_DTYPE)
+    hits["window"] = starts[rng.integers(0, len(starts), hits.shape)]
+    hits["errors"] = rng.integers(0, 3, hits.shape)
+    first = None
+    if tables:
+        shift = int(starts[3])
+        choices = [0, shift, W - (TM.L0 + 20) * Rn, 0, W, shift, W + 9, 2 ** 64 - 1]
+        first = [choices[p % len(choices)] for p in range(POOL)]
+        for p, f in enumerate(first):
+            if f == shift:
+                hits["window"][p] = starts[rng.integers(3, len(starts), max_frames)] - np.uint64(shift)
+            elif f:
+                hits["window"][p] = rng.integers(0, 3 * Rn + 1, max_frames).astype(np.uint64)
+    return dict(K=K, Rn=Rn, h=h, kind=kind, N=N, fec=fec, P=P, W=W, hits=hits, counts=counts, first=first,
+                idx=draw_slots(rng, S))
+
+
+def mapped_decode_expected(A, case, S, max_frames, most, waves, poison=TM.POISON):
+    """rows and decode of the S groups whole, from the pool's reference (the
+    host decoder on the reference's soft values, which tests/test_fec_modes_cpu.py
+    holds to fec_modes_ref.decode); the fixture's conditions; the tally."""
+    c = case
+    rows, dec, by_key = TM.reference(A, c["P"], c["W"], c["first"], c["hits"], c["counts"], TM.L0, c["Rn"], c["N"],
+                                     c["h"], c["kind"], c["fec"], poison)
+    idx = c["idx"]
+    wpg = waves_per_group(S, max_frames)
+    assert (MAX_WAVES // S if MAX_WAVES // S else 1) == most and S * wpg == waves
+    assert_last_block_holds_rows(S, wpg, idx, c["counts"], max_frames, LIVE.get(S, WAVES_PER_BLOCK))
+    assert {int(v[1]["status"][0]) for v in by_key.values()} == {X.OK, X.BAD_LENGTH}
+    assert len(by_key) >= 20                              # distinct rows decoded: a handful, not S max_frames
+    statuses = [dec[p, :min(c["counts"][p], max_frames)].copy().view(X.DECODE_DTYPE)["status"].reshape(-1)
+                for p in range(POOL)]
+    return (rows[idx], dec[idx]), tally(S, max_frames, idx, c["counts"], statuses)
+
+
+def run_mapped_decode(A, torch, d, case, idx, **kw):
+    """One call; the workspace has exactly demod_fec_decode_workspace_size bytes."""
+    c = case
+    first = None if c["first"] is None else [c["first"][p] for p in idx]
+    run = TM.Run(A, torch, c["P"], c["hits"][idx], [c["counts"][p] for p in idx], first=first, **kw)
+    got = run(d, TM.L0, c["N"], c["h"], c["kind"], c["fec"])
+    St = Z.row_shape(c["N"], 1, c["h"], c["kind"], c["fec"])[0]
+    assert run.d_work.numel() == len(idx) * waves_per_group(len(idx), c["hits"].shape[1]) * St * 8
+    return got
+
+
+def test_decode_geometry_mapped(A, torch, handle):
+    """Mode 0x61 (rate 3/4, interleaved: 192 steps, 23 bytes a row) at S = 5461
+    x 4 rows: 3 waves a group take 4 rows, the last block has a wave that
+    leaves; the workspace under two poisons."""
+    S, max_frames, most, waves = GEOMETRY[1]
+    fec, Rn = 0x61, 1
+    assert Z.row_shape(Z.BLOCK, 1, 1, C.CRC16, fec) == (192, 23, 20)
+    case = mapped_decode_case(S, max_frames, fec, Rn, False)
+    want, stats = mapped_decode_expected(A, case, S, max_frames, most, waves)
+    print(f"decode fec={fec:#x} S={S} max_frames={max_frames}: {stats}")
+    d = handle(Rn, case["K"])
+    for work_poison in (0xFF, 0x00):
+        TM.same(run_mapped_decode(A, torch, d, case, case["idx"], work_poison=work_poison), want, (S, work_poison))
+
+
+def test_decode_fallback_mapped(A, torch, handle):
+    """Mode 0x51 (rate 2/3, interleaved: 170 steps, 20 bytes a row) at S =
+    16385 x 3 rows, 2 tones, R 4, with a first[] table (entries at n_windows
+    and above it among them): one wave a group, workspace slots above 16383;
+    two output poisons, two workspace poisons."""
+    S, max_frames, most, waves = GEOMETRY[4]
+    fec, Rn = 0x51, 4
+    assert Z.row_shape(Z.BLOCK, 1, 1, C.CRC16, fec) == (170, 20, 17)
+    case = mapped_decode_case(S, max_frames, fec, Rn, True)
+    assert case["W"] in case["first"] and max(case["first"]) > case["W"]
+    d = handle(Rn, case["K"])
+    for poison, work_poison in ((0xFF, 0x00), (0x5A, 0xFF)):
+        want, stats = mapped_decode_expected(A, case, S, max_frames, most, waves, poison)
+        got = run_mapped_decode(A, torch, d, case, case["idx"], poison=poison, work_poison=work_poison)
+        TM.same(got, want, (poison, work_poison))
+    print(f"decode fec={fec:#x} S={S} max_frames={max_frames} R={Rn} with first[]: {stats}")
 
 
 # ---- Part 3: the chain behind a sparse segmented scan -----------------------------------------

@@ -165,12 +165,25 @@ def test_advance(A, torch, handle, S, Cw, K):
 
 # ---- collect ---------------------------------------------------------------------------
 
-def collect_case(S, mf, K, fec, seed):
-    """Hand-made outputs of a scan and a check for S groups of up to mf rows."""
+MODE_LEN = 40                    # the mapped modes' rows hold frames of 40 bytes: 43 bytes wide, 47 or 63 interleaved
+COLLECT_MODE_CASES = [(1, 5, 2), (65, 130, 2), (1025, 4, 2), (65, 130, 8)]       # (S, mf, K)
+
+
+def collect_seed(S, mf, K, fec):
+    return 77 * S + mf + fec + K
+
+
+def collect_case(S, mf, K, fec, seed, mode_len=None):
+    """Hand-made outputs of a scan and a check for S groups of up to mf rows.
+    mode_len: rows of the smallest N that holds frames of that many bytes in
+    mode fec (the mode's N, max_len and span)."""
     rng = np.random.default_rng(seed)
     bits = F.bits_per_symbol(K)
     h, kind = (2, C.CRC16) if fec else (1, C.CRC32)
-    Nsym = 400 // bits if fec else X.row_symbols(h, kind, 0, bits, 7)
+    if mode_len is not None:
+        Nsym = X.row_symbols(h, kind, fec, bits, mode_len)
+    else:
+        Nsym = 400 // bits if fec else X.row_symbols(h, kind, 0, bits, 7)
     max_len = X.sizes(K, R, S, L_WORD, Nsym, h, kind, fec, mf, 10 ** 6)["max_len"]
     state = np.zeros(S, X.STATE_DTYPE)
     state["base"] = rng.integers(0, 2 ** 40, S)
@@ -185,6 +198,8 @@ def collect_case(S, mf, K, fec, seed):
     check["crc"] = rng.integers(0, 2 ** 32, (S, mf))
     check["status"] = rng.choice([C.OK, C.OK, C.BAD_CRC, C.BAD_LENGTH], (S, mf))
     check["covered"] = rng.integers(0, 2, (S, mf))
+    if mode_len is not None:      # stream 0 (hold 0, mf rows) emits a row whose stored length is above max_len
+        check["length"][0, 0], check["status"][0, 0], check["covered"][0, 0] = max_len + 9, C.OK, 0
     res = np.zeros(S, X.RESULT_DTYPE)
     nw = rng.integers(0, mf + 1, S)
     nw[::5] = mf
@@ -214,12 +229,36 @@ def collect_case(S, mf, K, fec, seed):
                 N=Nsym, max_len=max_len, bits=bits)
 
 
+def collect_reference(c, fec, poison=0xFF):
+    """rx_ref.collect of a case over poisoned outputs: (state, frames, bodies, summary)."""
+    S, mf = c["hits"].shape
+    rows = S * mf
+    return X.collect(c["state"], c["hits"], c["res"], c["check"], c["kept"], c["body"], c["summ"], L_WORD, R,
+                     c["bits"], c["h"], c["kind"], fec, np.frombuffer(bytes([poison]) * (rows * 32), X.FRAME_DTYPE),
+                     np.full(rows * c["max_len"], poison, np.uint8))
+
+
 @pytest.mark.parametrize("fec", [0, 1])
 @pytest.mark.parametrize("S,mf", [(1, 5), (63, 5), (64, 1), (65, 130), (1025, 4), (20000, 3)])
 def test_collect(A, torch, handle, S, mf, fec):
     K = 2
-    d = handle(K)
-    c = collect_case(S, mf, K, fec, 77 * S + mf + fec)
+    run_collect(A, torch, handle(K), collect_case(S, mf, K, fec, 77 * S + mf + fec), S, mf, fec)
+
+
+@pytest.mark.parametrize("S,mf,K", COLLECT_MODE_CASES)
+@pytest.mark.parametrize("fec", [0x11, 0x21, 0x41, 0x51, 0x61])
+def test_collect_modes(A, torch, handle, fec, S, mf, K):
+    """The same in the five mapped modes, with the mode's N, max_len and span:
+    hold comes from the mode's span and a stored length above max_len is
+    clamped at the mode's max_len. tests/test_fec_stages_cpu.py asserts on the
+    reference alone that hold differs from the rate-1/2 one and that a clamped
+    record is emitted."""
+    run_collect(A, torch, handle(K), collect_case(S, mf, K, fec, collect_seed(S, mf, K, fec), MODE_LEN), S, mf, fec)
+
+
+def run_collect(A, torch, d, c, S, mf, fec):
+    """State, summary, records and bytes whole over two poisons, the guards
+    intact, the inputs unwritten."""
     ins = [c["hits"], c["res"], c["check"], c["kept"], c["body"], c["summ"]]
     d_in = [torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda() for a in ins]
     rows, max_len = S * mf, c["max_len"]
@@ -233,10 +272,7 @@ def test_collect(A, torch, handle, S, mf, fec):
         d.rx_collect_async(d_state, d_in[0], d_in[1], d_in[2], d_in[3].view(torch.int32), d_in[4], d_in[5], S, mf,
                            L_WORD, c["N"], c["h"], c["kind"], fec, d_frames, d_bodies, d_summary, d_work)
         o.guards_intact()
-        w_state, w_frames, w_bodies, w_summary = X.collect(
-            c["state"], c["hits"], c["res"], c["check"], c["kept"], c["body"], c["summ"], L_WORD, R, c["bits"],
-            c["h"], c["kind"], fec, np.frombuffer(bytes([poison]) * (rows * 32), X.FRAME_DTYPE),
-            np.full(rows * max_len, poison, np.uint8))
+        w_state, w_frames, w_bodies, w_summary = collect_reference(c, fec, poison)
         same(d_state.cpu().numpy(), w_state.view(np.uint8), "state")
         same(d_summary.cpu().numpy(), w_summary.reshape(1).view(np.uint8), "summary")
         same(d_frames.cpu().numpy(), w_frames.view(np.uint8), "records")
@@ -340,8 +376,10 @@ def rx_setup(A, K, fec, max_frames=8, ring=None, n_frames=5, seed=0):
 
 def one_shot(d, pcm, word, Nsym, fec):
     """[(window, errors, body)] of demod_frames_checked / demod_frames_coded."""
-    run = d.frames_coded if fec else d.frames_checked
-    hits, lengths, bodies, _, _ = run(pcm, word, 0, Nsym, H, KIND)
+    if fec:
+        hits, lengths, bodies, _, _ = d.frames_coded(pcm, word, 0, Nsym, H, KIND, fec=fec)
+    else:
+        hits, lengths, bodies, _, _ = d.frames_checked(pcm, word, 0, Nsym, H, KIND)
     return [(int(hh["window"]), int(hh["errors"]), b) for hh, b in zip(hits, bodies)]
 
 
@@ -388,7 +426,20 @@ def test_push_gives_the_one_shot_frames(A, torch, handle, S, K, fec):
     """Five frames per stream, each stream delayed by its own number of samples:
     2880-frame packets, ragged packets (0, 100 and 997 frames among them) and one
     single push all return each stream's one-shot frames under its own index."""
-    d = handle(K)
+    push_against_one_shot(A, handle(K), S, K, fec)
+
+
+@pytest.mark.parametrize("fec", [0x21, 0x51, 0x61])
+@pytest.mark.parametrize("K", [2, 8])
+@pytest.mark.parametrize("S", [1, 3])
+def test_push_gives_the_one_shot_frames_modes(A, torch, handle, S, K, fec):
+    """The same in modes 0x21, 0x51 and 0x61: with tests/test_gpu_fec_modes.py's
+    link every flag (rate 2/3, rate 3/4, interleaved) reaches a receiver at 1
+    and at 3 bits a symbol, where a 256-bit block ends inside a symbol."""
+    push_against_one_shot(A, handle(K), S, K, fec)
+
+
+def push_against_one_shot(A, d, S, K, fec):
     pcm, word, Nsym, rxcfg, datas = rx_setup(A, K, fec)
     rng = np.random.default_rng(S)
     delays = [0 if S == 1 else HOP * ((3 * s) % 7) + 20 * (s % 5) for s in range(S)]
