@@ -257,6 +257,35 @@ class DemodFrameDecode(ctypes.Structure):
 FRAME_DECODE_DTYPE = np.dtype(DemodFrameDecode)
 
 
+DEMOD_FEC_RS16 = 0x100         # 16 parity bytes a codeword of the outer code, t = 8
+DEMOD_FEC_RS32 = 0x200         # 32, t = 16; both parity flags together: refused
+DEMOD_RS_OK = 0
+DEMOD_RS_BAD_LENGTH = 1        # len > max_len; the other fields 0
+DEMOD_RS_FAILED = 2            # at least one codeword failed
+RS_PARITY = {0: 0, DEMOD_FEC_RS16: 16, DEMOD_FEC_RS32: 32}
+# the 20 modes: none or one of the six coded modes with none or one parity flag; 0 is no mode
+RS_MODES = tuple(m | r for r in (0, DEMOD_FEC_RS16, DEMOD_FEC_RS32) for m in (0,) + FEC_MODES if m | r)
+RS_PARITY_MODES = tuple(m for m in RS_MODES if m & (DEMOD_FEC_RS16 | DEMOD_FEC_RS32))
+RS_CONV_MODES = tuple(m for m in RS_MODES if m & 0xFF)   # with the convolutional code: what the trellis functions take
+
+
+class DemodFrameRs(ctypes.Structure):
+    """demod_frame_rs_t (include/demod.h "Reed-Solomon outer code"): one row's
+    status, codewords, corrected bytes and failed codewords."""
+    _fields_ = [("status", ctypes.c_uint32), ("codewords", ctypes.c_uint32), ("corrected", ctypes.c_uint32),
+                ("failed", ctypes.c_uint32)]
+
+
+FRAME_RS_DTYPE = np.dtype(DemodFrameRs)
+
+
+def rs_mode_parts(fec: int) -> Tuple[int, int]:
+    """(the coded mode or 0, P) of one of the 20 modes."""
+    if fec not in RS_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "fec: not one of the 20 modes")
+    return fec & 0xFF, RS_PARITY[fec & (DEMOD_FEC_RS16 | DEMOD_FEC_RS32)]
+
+
 class DemodRxCfg(ctypes.Structure):
     """demod_rx_cfg_t (include/demod.h "receiver"): the frame format and the
     sizes of a receiver."""
@@ -443,6 +472,15 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                               ctypes.c_int, ctypes.c_int, _P, _P, _P, _SZ,
                                               ctypes.POINTER(DemodFramesResult),
                                               ctypes.POINTER(DemodFramesCheckResult)]),
+        "demod_rs_generator": (ctypes.c_int, [ctypes.c_int, _P]),
+        "demod_rs_encode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, _P]),
+        "demod_rs_frame_size": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+        "demod_rs_max_len": (ctypes.c_longlong, [_SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+        "demod_rs_frame_encode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _SZ]),
+        "demod_rs_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(DemodFrameRs)]),
+        "demod_frames_rs_async": (ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, _P, _P]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -693,8 +731,8 @@ def fec_decode_workspace_size(cfg: DemodCfg, n_groups: int, max_frames: int, fra
                               fec: int = DEMOD_FEC_CONV_K7) -> int:
     """demod_fec_decode_workspace_size: frames_decode_workspace_size with the
     mode's St (no GPU). Raises DemodError(DEMOD_BAD_ARG) where it is 0."""
-    if fec not in FEC_MODES:
-        raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
+    if fec not in RS_CONV_MODES:
+        raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes, with or without a parity flag")
     return _size("demod_fec_decode_workspace_size", cfg, n_groups, max_frames, frame_symbols, fec)
 
 
@@ -1296,6 +1334,7 @@ class Demodulator(_Handle):
         if len_bytes not in (1, 2) or crc not in CRC_BYTES:
             raise DemodError(DEMOD_BAD_ARG, "len_bytes not 1 or 2, or an unknown crc kind")
         bits = bits_per_symbol(self.k)
+        fec, parity = rs_mode_parts(fec) if fec else (0, 0)
         if fec:
             if self.k != 1 << bits:
                 raise DemodError(DEMOD_BAD_ARG, "coded frames need K = 2^bits tones")
@@ -1305,7 +1344,11 @@ class Demodulator(_Handle):
             B, short = (St - 6) // 8, ""
         else:
             B, short = (int(frame_symbols) * bits + 7) // 8, "rows too short for header and CRC, or "
-        max_len = B - len_bytes - CRC_BYTES[crc]
+        if parity:
+            max_len = rs_max_len(B, len_bytes, crc, DEMOD_FEC_RS16 if parity == 16 else DEMOD_FEC_RS32) \
+                if 0 <= B < 2 ** 31 else -1
+        else:
+            max_len = B - len_bytes - CRC_BYTES[crc]
         if max_len < 0 or max_len > DEMOD_MAX_FRAME_PAYLOAD:
             raise DemodError(DEMOD_BAD_ARG, short + "max_len above DEMOD_MAX_FRAME_PAYLOAD")
         return B, max_len
@@ -1367,8 +1410,8 @@ class Demodulator(_Handle):
         W, L = int(n_windows), int(sync_len)
         if W < 0 or W >= 2 ** 31:
             raise DemodError(DEMOD_BAD_ARG, "n_windows not in 0 .. 2^31 - 1")
-        if fec not in FEC_MODES:
-            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
+        if fec not in RS_MODES or not fec & 0xFF:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes, with or without a parity flag")
         Bd, _ = self._frame_shape(N, len_bytes, crc, fec)
         dev = int(self.cfg.device)
         rows = S * cap
@@ -1393,8 +1436,8 @@ class Demodulator(_Handle):
         frames_decode_async wrote (uint8, n_groups * max_frames * Bd bytes),
         with max_len = Bd - len_bytes - the CRC's bytes and the coded span."""
         S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
-        if fec not in FEC_MODES:
-            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
+        if fec not in RS_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the 20 modes")
         Bd, max_len = self._frame_shape(N, len_bytes, crc, fec)
         self._check_scan_outputs(S, cap, max_len, d_hits, d_results, d_check, d_kept, d_body, d_summary,
                                  rows=(d_rows, "d_rows", Bd))
@@ -1404,6 +1447,27 @@ class Demodulator(_Handle):
             _ptr(d_summary), stream or None)
         if rc < 0:
             raise DemodError(rc, "demod_frames_check_coded_async")
+
+    def frames_rs_async(self, d_rows, d_results, n_groups: int, max_frames: int, frame_symbols: int,
+                        len_bytes: int, crc: int, fec: int, d_rs, stream: int = 0) -> None:
+        """demod_frames_rs_async: the Reed-Solomon outer code over the rows of
+        a frame scan (fec & 0xFF == 0: its d_packed, B bytes a row) or of
+        frames_decode_async (Bd bytes a row), corrected in place before
+        frames_check_coded_async reads them. d_rs (uint8, 16 bytes a row:
+        FRAME_RS_DTYPE) is written. Device tensors, checked like the batch
+        calls'."""
+        S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
+        if fec not in RS_PARITY_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the modes with a parity flag")
+        W, _ = self._frame_shape(N, len_bytes, crc, fec)
+        dev = int(self.cfg.device)
+        _check_dev(d_rows, "d_rows", "uint8", S * cap * W, dev)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_rs, "d_rs", "uint8", S * cap * ctypes.sizeof(DemodFrameRs), dev)
+        rc = self._lib.demod_frames_rs_async(self._h, _ptr(d_rows), _ptr(d_results), S, cap, N, int(len_bytes),
+                                             int(crc), int(fec), _ptr(d_rs), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_rs_async")
 
     def rx_advance_async(self, d_state, d_ring_sym_in, d_ring_mag_in, d_new_sym, d_new_mag,
                          n_new_windows: int, d_new_first, d_new_count, n_streams: int, ring_windows: int,
@@ -1453,8 +1517,8 @@ class Demodulator(_Handle):
         calls'."""
         S, cap, N = _rows_shape(n_streams, max_frames, frame_symbols, "n_streams")
         L = int(sync_len)
-        if fec != 0 and fec not in FEC_MODES:
-            raise DemodError(DEMOD_BAD_ARG, "fec: not 0 or one of the six coded modes")
+        if fec != 0 and fec not in RS_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not 0 or one of the 20 modes")
         _, max_len = self._frame_shape(N, len_bytes, crc, fec)
         dev = int(self.cfg.device)
         rows = S * cap
@@ -1538,9 +1602,11 @@ class Demodulator(_Handle):
                      max_frames: Optional[int] = None, n_windows: Optional[int] = None, body: bool = True):
         """demod_frames_coded: frames_checked for coded frames (include/demod.h
         "coded frames"): detector, frame scan, soft-decision decode of its rows
-        and the coded check. Returns what frames_checked returns."""
-        if fec not in FEC_MODES:
-            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the six coded modes")
+        and the coded check; with a parity flag the Reed-Solomon stage before
+        the check, and with fec & 0xFF == 0 over the scan's packed rows.
+        Returns what frames_checked returns."""
+        if fec not in RS_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the 20 modes")
         return self._frames_checked(pcm, sync, max_errors, frame_symbols, len_bytes, crc, int(fec), max_frames,
                                     n_windows, body)
 
@@ -1993,14 +2059,14 @@ def coded_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FA
 def fec_air_index(fec: int, m: int) -> int:
     """demod_fec_air_index: the air position of mother bit m = 2 t + v in the
     mode `fec`, or -1 where it is punctured."""
-    if fec not in FEC_MODES or not 0 <= int(m) < 2 ** 31:
+    if fec not in RS_CONV_MODES or not 0 <= int(m) < 2 ** 31:
         raise DemodError(DEMOD_BAD_ARG, "demod_fec_air_index")
     return int(load_library().demod_fec_air_index(int(fec), int(m)))
 
 
 def fec_frame_symbols(length: int, len_bytes: int, crc: int, bits: int, fec: int) -> int:
     """demod_fec_frame_symbols: Sc of the mode, ceil(Na(len) / bits)."""
-    if fec not in FEC_MODES:
+    if fec not in RS_CONV_MODES:
         raise DemodError(DEMOD_BAD_ARG, "demod_fec_frame_symbols")
     rc = int(load_library().demod_fec_frame_symbols(int(length), int(len_bytes), int(crc), int(bits), int(fec)))
     if rc < 0:
@@ -2012,12 +2078,14 @@ def fec_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCI
                      fec: int = DEMOD_FEC_CONV_K7, cap: Optional[int] = None) -> bytes:
     """demod_fec_frame_encode: the frame's bits in air order, pad bits 0. cap:
     the output room handed to the library (default: what any mode needs)."""
-    if fec not in FEC_MODES:
+    if fec not in RS_CONV_MODES:
         raise DemodError(DEMOD_BAD_ARG, "demod_fec_frame_encode")
     lib = load_library()
     data = bytes(data)
     if cap is None:
         cap = 2 * len(data) + 64
+        if fec & (DEMOD_FEC_RS16 | DEMOD_FEC_RS32):   # twice the n' bytes, and the same slack
+            cap = 2 * rs_frame_size(len(data), len_bytes, crc, fec) + 64
     src = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
     out = (ctypes.c_uint8 * max(int(cap), 1))()
     rc = lib.demod_fec_frame_encode(src, len(data), int(len_bytes), int(crc), int(fec), out, int(cap))
@@ -2028,7 +2096,7 @@ def fec_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCI
 
 def fec_row_bytes(frame_symbols: int, bits: int, len_bytes: int = 2, fec: int = DEMOD_FEC_CONV_K7) -> int:
     """demod_fec_row_bytes: Bd of rows of frame_symbols symbols in the mode."""
-    if frame_symbols < 0 or fec not in FEC_MODES:
+    if frame_symbols < 0 or fec not in RS_CONV_MODES:
         raise DemodError(DEMOD_BAD_ARG, "demod_fec_row_bytes")
     rc = int(load_library().demod_fec_row_bytes(int(frame_symbols), int(bits), int(len_bytes), int(fec)))
     if rc < 0:
@@ -2043,8 +2111,10 @@ def fec_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALS
     the row room handed to the library (default: Bd)."""
     q = np.ascontiguousarray(soft, dtype=np.int8).reshape(-1)
     if cap is None:
-        cap = max((fec_row_steps(q.size, fec) - 6) // 8, 0)
-    elif fec not in FEC_MODES:
+        if fec not in RS_CONV_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "demod_fec_frame_decode")
+        cap = max((fec_row_steps(q.size, fec & 0xFF) - 6) // 8, 0)
+    elif fec not in RS_CONV_MODES:
         raise DemodError(DEMOD_BAD_ARG, "demod_fec_frame_decode")
     row = np.zeros(max(int(cap), 1), dtype=np.uint8)
     dec = DemodFrameDecode()
@@ -2053,6 +2123,71 @@ def fec_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALS
     if rc < 0:
         raise DemodError(rc, "demod_fec_frame_decode")
     return row[:rc].tobytes(), _struct_dict(dec)
+
+
+def rs_generator(parity_bytes: int) -> bytes:
+    """demod_rs_generator: g(x) of parity_bytes roots, highest coefficient first."""
+    out = (ctypes.c_uint8 * 33)()
+    n = load_library().demod_rs_generator(int(parity_bytes), out)
+    if n < 0:
+        raise DemodError(n, "demod_rs_generator")
+    return bytes(out[:n])
+
+
+def rs_encode(msg: bytes, parity_bytes: int) -> bytes:
+    """demod_rs_encode: the parity of one codeword's message."""
+    msg = bytes(msg)
+    out = (ctypes.c_uint8 * 32)()
+    n = load_library().demod_rs_encode(msg, len(msg), int(parity_bytes), out)
+    if n < 0:
+        raise DemodError(n, "demod_rs_encode")
+    return bytes(out[:n])
+
+
+def rs_frame_size(length: int, len_bytes: int, crc: int, fec: int) -> int:
+    """demod_rs_frame_size: n'(len) of the mode."""
+    n = load_library().demod_rs_frame_size(int(length), int(len_bytes), int(crc), int(fec))
+    if n < 0:
+        raise DemodError(int(n), "demod_rs_frame_size")
+    return int(n)
+
+
+def rs_max_len(row_bytes: int, len_bytes: int, crc: int, fec: int) -> int:
+    """demod_rs_max_len: the greatest len whose protected frame fits a row."""
+    if row_bytes < 0:
+        raise DemodError(DEMOD_BAD_ARG, "row_bytes < 0")
+    n = load_library().demod_rs_max_len(int(row_bytes), int(len_bytes), int(crc), int(fec))
+    if n < 0:
+        raise DemodError(int(n), "demod_rs_max_len")
+    return int(n)
+
+
+def rs_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE,
+                    fec: int = DEMOD_FEC_RS16) -> bytes:
+    """demod_rs_frame_encode: len || data || CRC || parity, n' bytes."""
+    data = bytes(data)
+    cap = rs_frame_size(len(data), len_bytes, crc, fec)
+    out = (ctypes.c_uint8 * max(cap, 1))()
+    n = load_library().demod_rs_frame_encode(data, len(data), int(len_bytes), int(crc), int(fec), out, cap)
+    if n < 0:
+        raise DemodError(n, "demod_rs_frame_encode")
+    return bytes(out[:n])
+
+
+def rs_frame_decode(row, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE, fec: int = DEMOD_FEC_RS16):
+    """demod_rs_frame_decode on a copy of `row` (bytes or uint8 array; its
+    length is the row width): (the corrected row, the record as a dict, the
+    bytes covered)."""
+    buf = np.array(np.frombuffer(bytes(row), np.uint8) if isinstance(row, (bytes, bytearray)) else row,
+                   dtype=np.uint8).reshape(-1).copy()
+    if buf.size == 0:
+        raise DemodError(DEMOD_BAD_ARG, "row: empty")
+    rec = DemodFrameRs()
+    n = load_library().demod_rs_frame_decode(buf.ctypes.data, buf.size, int(len_bytes), int(crc), int(fec),
+                                             ctypes.byref(rec))
+    if n < 0:
+        raise DemodError(n, "demod_rs_frame_decode")
+    return buf, _struct_dict(rec), n
 
 
 def frame_decode(buf: bytes) -> Tuple[bytes, int]:

@@ -24,6 +24,7 @@
 #include "../../include/demod.h"
 #include "demod_internal.h"
 #include "fec_map.h"
+#include "rs_ops.h"
 
 namespace fskd {
 
@@ -126,10 +127,12 @@ __device__ __forceinline__ uint8_t frame_packed_byte(const uint8_t *src, unsigne
 // "coded frames": Sc, its coded bits on the air). The one copy of the span that
 // `covered` (frames_check.hip) and the receiver's `hold` (frames_carry.hip) use.
 // A mapped mode (fec_map.h: punctured, interleaved) has Sc of its Na(len) air bits.
+// With an outer code of `parity` bytes a codeword (rs_ops.h) the bytes are n'.
 __device__ __forceinline__ unsigned checked_frame_span(unsigned length, unsigned len_bytes, unsigned crc_bytes,
-                                                       unsigned bits, unsigned fec_depth, unsigned fec)
+                                                       unsigned bits, unsigned fec_depth, unsigned fec,
+                                                       unsigned parity)
 {
-    unsigned span = (len_bytes + crc_bytes + length) * 8;
+    unsigned span = rs_frame_bytes(len_bytes + crc_bytes + length, parity) * 8;
     if (fec_depth) {
         const unsigned least = 8u * len_bytes + fec_depth;
         const unsigned T = span + 6u > least ? span + 6u : least;

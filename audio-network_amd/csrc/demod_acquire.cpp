@@ -528,20 +528,25 @@ static bool frames_check_shape(const demod_cfg_t &cfg, size_t n_groups, size_t m
     const size_t c = crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4, h = (size_t)len_bytes;
     if (frame_symbols > 0x7FFFFFFF) return false;
     size_t B = packed_row_bytes(frame_symbols, bits);
-    if (fec) {
+    if (fec && !rs_mode_valid((unsigned)fec)) return false;
+    const unsigned conv = rs_mode_conv((unsigned)fec), P = rs_parity((unsigned)fec);
+    if (conv) {
         // coded rows: the mode's St steps (fec_map.h) decode to Bd = (St - 6) / 8 bytes
-        if (!fec_mode_valid((unsigned)fec) || cfg.k != (1u << bits)) return false;
-        const size_t St = fec_row_steps((unsigned)fec, frame_symbols * bits);
+        if (cfg.k != (1u << bits)) return false;
+        const size_t St = fec_row_steps(conv, frame_symbols * bits);
         if (St < 8 * h + DEMOD_FEC_DEPTH) return false;
         B = (St - 6) / 8;
         p.fec_depth = DEMOD_FEC_DEPTH;
-        p.fec = fec;
+        p.fec = (int)conv;
     }
-    if (B < h + c || B - h - c > DEMOD_MAX_FRAME_PAYLOAD) return false;
+    // max_len: the greatest len whose frame fits the row; with an outer code its n' bytes (rs_ops.h)
+    const long long M = P ? rs_max_len((unsigned)B, (unsigned)h, (unsigned)c, P) : (long long)B - (long long)(h + c);
+    if (M < 0 || M > DEMOD_MAX_FRAME_PAYLOAD) return false;
+    p.parity = (int)P;
     p.n_groups = (unsigned)n_groups;
     p.max_frames = (unsigned)max_frames;
     p.row_bytes = (unsigned)B;
-    p.max_len = (unsigned)(B - h - c);
+    p.max_len = (unsigned)M;
     p.len_bytes = len_bytes;
     p.crc_bytes = (int)c;
     p.poly = c == 2 ? 0x1021u << 16 : 0x04C11DB7u;
@@ -619,7 +624,8 @@ size_t demod_frames_decode_workspace_size(const demod_cfg_t *cfg, size_t n_group
 size_t demod_fec_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, size_t max_frames,
                                        size_t frame_symbols, int fec)
 {
-    if (!fec_mode_valid((unsigned)fec)) return 0;
+    if (!rs_mode_valid((unsigned)fec) || !rs_mode_conv((unsigned)fec)) return 0;
+    fec = (int)rs_mode_conv((unsigned)fec);   // a parity flag does not change the trellis's workspace
     if (validate_cfg(cfg) != DEMOD_OK || cfg->k < 2 || (cfg->k & (cfg->k - 1)) != 0) return 0;
     if (n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames == 0 || max_frames > 0x7FFFFFFF) return 0;
     if ((unsigned long long)n_groups * max_frames > 0x7FFFFFFFull) return 0;
@@ -639,13 +645,15 @@ int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, cons
     if (((uintptr_t)d_hits & 7) != 0 || ((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_work & 7) != 0 ||
         ((uintptr_t)d_first & 7) != 0 || ((uintptr_t)d_decode & 3) != 0)
         return DEMOD_BAD_ARG;
-    if (!fec_mode_valid((unsigned)fec) || n_windows > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    if (!rs_mode_valid((unsigned)fec) || !rs_mode_conv((unsigned)fec) || n_windows > 0x7FFFFFFF)
+        return DEMOD_BAD_ARG;
+    const int conv = (int)rs_mode_conv((unsigned)fec);   // the trellis's mode; the parity flag sizes the frame
     FramesCheckParams q;   // the shape the coded check will see: the same refusals
     std::memset(&q, 0, sizeof(q));
     if (!frames_check_shape(st, n_groups, max_frames, sync_len, frame_symbols, len_bytes, crc, q, fec))
         return DEMOD_BAD_ARG;
     if ((sync_len + frame_symbols) * (size_t)q.phases > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const size_t need = demod_fec_decode_workspace_size(&st->cfg, n_groups, max_frames, frame_symbols, fec);
+    const size_t need = demod_fec_decode_workspace_size(&st->cfg, n_groups, max_frames, frame_symbols, conv);
     if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
     FramesFecParams p;
     std::memset(&p, 0, sizeof(p));
@@ -657,8 +665,9 @@ int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, cons
     p.n_groups = q.n_groups;
     p.max_frames = q.max_frames;
     p.frame_symbols = (unsigned)frame_symbols;
-    p.steps = (unsigned)fec_row_steps((unsigned)fec, frame_symbols * (size_t)q.bits);
-    p.fec = (unsigned)fec;
+    p.steps = (unsigned)fec_row_steps((unsigned)conv, frame_symbols * (size_t)q.bits);
+    p.fec = (unsigned)conv;
+    p.parity = (unsigned)q.parity;
     p.row_bytes = q.row_bytes;
     p.max_len = q.max_len;
     p.len_bytes = q.len_bytes;
@@ -683,9 +692,38 @@ int demod_frames_check_coded_async(demod_t *st, const demod_frame_hit_t *d_hits,
                                    uint32_t *d_kept, uint8_t *d_body,
                                    demod_frames_check_result_t *d_summary, void *stream)
 {
-    if (!fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
+    if (!rs_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     return frames_check_enqueue(st, d_hits, d_rows, d_results, n_groups, max_frames, sync_len,
                                 frame_symbols, len_bytes, crc, fec, d_check, d_kept, d_body, d_summary, stream);
+}
+
+int demod_frames_rs_async(demod_t *st, uint8_t *d_rows, const demod_frames_result_t *d_results,
+                          size_t n_groups, size_t max_frames, size_t frame_symbols, int len_bytes, int crc,
+                          int fec, demod_frame_rs_t *d_rs, void *stream)
+{
+    if (!st || !d_rows || !d_results || !d_rs) return DEMOD_BAD_ARG;
+    if (((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_rs & 3) != 0) return DEMOD_BAD_ARG;
+    if (!rs_mode_valid((unsigned)fec) || !rs_parity((unsigned)fec)) return DEMOD_BAD_ARG;
+    FramesCheckParams q;   // the shape the coded check will see: the same refusals (it has no word here)
+    std::memset(&q, 0, sizeof(q));
+    if (!frames_check_shape(st, n_groups, max_frames, 1, frame_symbols, len_bytes, crc, q, fec))
+        return DEMOD_BAD_ARG;
+    FramesRsParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.rows = d_rows;
+    p.res = d_results;
+    p.n_groups = q.n_groups;
+    p.max_frames = q.max_frames;
+    p.row_bytes = q.row_bytes;
+    p.max_len = q.max_len;
+    p.len_bytes = q.len_bytes;
+    p.crc_bytes = q.crc_bytes;
+    p.parity = q.parity;
+    p.rs = d_rs;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_frames_rs(p, (hipStream_t)stream));
+    return DEMOD_OK;
 }
 
 // demod_frames_checked (fec 0: the scan's packed rows) and demod_frames_coded
@@ -702,7 +740,9 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
     FramesCheckParams p;
     std::memset(&p, 0, sizeof(p));
     if (!frames_check_shape(st, 1, dcap, sync_len, frame_symbols, len_bytes, crc, p, fec)) return DEMOD_BAD_ARG;
-    const size_t fec_work = fec ? demod_fec_decode_workspace_size(&st->cfg, 1, dcap, frame_symbols, fec) : 0;
+    // conv: the trellis's mode or 0 (the scan's packed rows); p.parity: the outer code's stage before the check
+    const int conv = (int)rs_mode_conv((unsigned)fec);
+    const size_t fec_work = conv ? demod_fec_decode_workspace_size(&st->cfg, 1, dcap, frame_symbols, conv) : 0;
     DeviceGuard guard(st->device);
     HIP_TRY(guard.err);
     const size_t N = frame_symbols, B = p.row_bytes, M = p.max_len;
@@ -711,13 +751,14 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
     HIP_TRY(st->d_frm_work.reserve(work));  // bytes
     HIP_TRY(st->d_frm_res.reserve(1));
     HIP_TRY(st->d_frm_hits.reserve(dcap));
-    if (fec) {
+    if (conv) {
         HIP_TRY(st->d_fec_rows.reserve(dcap * B));
         HIP_TRY(st->d_fec_decode.reserve(dcap));
         HIP_TRY(st->d_fec_work.reserve(fec_work));  // bytes
     } else {
         HIP_TRY(st->d_frm_packed.reserve(dcap * B));
     }
+    if (p.parity) HIP_TRY(st->d_rs.reserve(dcap));
     HIP_TRY(st->d_chk_check.reserve(dcap));
     HIP_TRY(st->d_chk_kept.reserve(dcap));
     HIP_TRY(st->d_chk_sum.reserve(1));
@@ -727,16 +768,22 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
     int rc;
     if ((rc = stage_and_detect(st, pcm, n_windows)) != DEMOD_OK) return rc;
     rc = demod_frames_async(st, st->d_sym.p, st->d_mag.p, n_windows, sync, sync_len, max_errors, N,
-                            st->d_frm_hits.p, nullptr, fec ? nullptr : st->d_frm_packed.p, dcap,
+                            st->d_frm_hits.p, nullptr, conv ? nullptr : st->d_frm_packed.p, dcap,
                             st->d_frm_res.p, st->d_frm_work.p, work, st->stream);
     if (rc < 0) return rc;
-    if (fec) {
+    uint8_t *rows = conv ? st->d_fec_rows.p : st->d_frm_packed.p;
+    if (conv) {
         rc = demod_frames_decode_async(st, st->d_frm_hits.p, st->d_mag.p, n_windows, nullptr, st->d_frm_res.p,
                                        1, dcap, sync_len, N, len_bytes, crc, fec, st->d_fec_rows.p,
                                        st->d_fec_decode.p, st->d_fec_work.p, fec_work, st->stream);
         if (rc < 0) return rc;
     }
-    rc = frames_check_enqueue(st, st->d_frm_hits.p, fec ? st->d_fec_rows.p : st->d_frm_packed.p,
+    if (p.parity) {
+        rc = demod_frames_rs_async(st, rows, st->d_frm_res.p, 1, dcap, N, len_bytes, crc, fec, st->d_rs.p,
+                                   st->stream);
+        if (rc < 0) return rc;
+    }
+    rc = frames_check_enqueue(st, st->d_frm_hits.p, rows,
                               st->d_frm_res.p, 1, dcap, sync_len, N, len_bytes, crc, fec, st->d_chk_check.p,
                               st->d_chk_kept.p, want_body ? st->d_chk_body.p : nullptr, st->d_chk_sum.p,
                               st->stream);
@@ -778,7 +825,7 @@ int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const 
                        size_t max_frames, demod_frames_result_t *result,
                        demod_frames_check_result_t *summary)
 {
-    if (!fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
+    if (!rs_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
                               fec, hits, lengths, body, max_frames, result, summary);
 }
@@ -797,7 +844,8 @@ int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n
     for (size_t i = 0; i < L; ++i)
         if (x.sync[i] >= cfg->k) return DEMOD_BAD_ARG;
     if (N > 0x7FFFFFFF || (L + N) * R > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    if (x.fec != 0 && !fec_mode_valid(x.fec)) return DEMOD_BAD_ARG;
+    if (x.fec != 0 && !rs_mode_valid(x.fec)) return DEMOD_BAD_ARG;
+    const int conv = (int)rs_mode_conv(x.fec);   // the trellis's mode, or 0
     // the check's (or the decode's and the coded check's): S, max_frames, the row shape
     FramesCheckParams p;
     std::memset(&p, 0, sizeof(p));
@@ -810,11 +858,11 @@ int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n
     out->ring_sym_bytes = S * C;
     out->ring_mag_bytes = S * C * cfg->k * sizeof(float);
     out->scan_work_bytes = demod_frames_segments_workspace_size(cfg, S, S * C);
-    out->decode_work_bytes = x.fec ? demod_fec_decode_workspace_size(cfg, S, x.max_frames, N, (int)x.fec) : 0;
+    out->decode_work_bytes = conv ? demod_fec_decode_workspace_size(cfg, S, x.max_frames, N, conv) : 0;
     out->collect_work_bytes = demod_rx_collect_workspace_size(cfg, S);
     out->frames_bytes = rows * sizeof(demod_rx_frame_t);
     out->bodies_bytes = rows * p.max_len;
-    if (out->scan_work_bytes == 0 || (x.fec && out->decode_work_bytes == 0)) return DEMOD_BAD_ARG;
+    if (out->scan_work_bytes == 0 || (conv && out->decode_work_bytes == 0)) return DEMOD_BAD_ARG;
     return DEMOD_OK;
 }
 
@@ -882,7 +930,7 @@ int demod_rx_collect_async(demod_t *st, demod_rx_stream_state_t *d_state, const 
         ((uintptr_t)d_summary & 7) != 0 || ((uintptr_t)d_work & 7) != 0 || ((uintptr_t)d_check & 3) != 0 ||
         ((uintptr_t)d_kept & 3) != 0)
         return DEMOD_BAD_ARG;
-    if (fec != 0 && !fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
+    if (fec != 0 && !rs_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     FramesCheckParams q;   // the shape the check saw: the same refusals, the same span
     std::memset(&q, 0, sizeof(q));
     if (!frames_check_shape(st, n_streams, max_frames, sync_len, frame_symbols, len_bytes, crc, q, fec))
@@ -909,6 +957,7 @@ int demod_rx_collect_async(demod_t *st, demod_rx_stream_state_t *d_state, const 
     p.sync_len = q.sync_len;
     p.fec_depth = q.fec_depth;
     p.fec = q.fec;
+    p.parity = q.parity;
     p.frames = d_frames;
     p.bodies = d_bodies;
     p.summary = d_summary;

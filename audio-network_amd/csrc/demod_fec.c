@@ -16,6 +16,7 @@
 
 #include "../../include/demod.h"
 #include "fec_map.h"
+#include "rs_ops.h"
 
 #define FEC_G0 0171u
 #define FEC_G1 0133u
@@ -35,28 +36,42 @@ static size_t crc_bytes(int crc)
     return crc == DEMOD_CRC16_CCITT_FALSE ? 2 : crc == DEMOD_CRC32_MPEG2 ? 4 : 0;
 }
 
-long long demod_coded_frame_steps(size_t len, int len_bytes, int crc)
+/* T(len) of the frame's n bytes, or with an outer code of P parity bytes its n' */
+static long long frame_steps(size_t len, int len_bytes, int crc, unsigned P)
 {
-    const long long n = demod_checked_frame_size(len, len_bytes, crc);
+    long long n = demod_checked_frame_size(len, len_bytes, crc);
     if (n < 0) return n;
+    n = (long long)rs_frame_bytes((unsigned)n, P);
     const long long body = 8 * n + 6, least = 8 * (long long)len_bytes + DEMOD_FEC_DEPTH;
     return body > least ? body : least;
 }
 
+long long demod_coded_frame_steps(size_t len, int len_bytes, int crc)
+{
+    return frame_steps(len, len_bytes, crc, 0);
+}
+
+/* a mode with the convolutional code: one of the six, with or without a parity flag */
+static int conv_mode_valid(int fec)
+{
+    return rs_mode_valid((unsigned)fec) && rs_mode_conv((unsigned)fec) != 0u;
+}
+
 long long demod_fec_air_index(int fec, size_t m)
 {
-    if (!fec_mode_valid((unsigned)fec) || m > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const unsigned a = fec_air_of_mother((unsigned)fec, (unsigned)m);
+    if (!conv_mode_valid(fec) || m > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const unsigned a = fec_air_of_mother(rs_mode_conv((unsigned)fec), (unsigned)m);
     return a == FEC_MAP_NONE ? -1 : (long long)a;
 }
 
 /* Na(len): the frame's bits on the air, or a negative code */
 static long long fec_frame_air_bits(size_t len, int len_bytes, int crc, int fec)
 {
-    if (!fec_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
-    const long long T = demod_coded_frame_steps(len, len_bytes, crc);
+    if (!conv_mode_valid(fec)) return DEMOD_BAD_ARG;
+    const unsigned conv = rs_mode_conv((unsigned)fec);
+    const long long T = frame_steps(len, len_bytes, crc, rs_parity((unsigned)fec));
     if (T < 0) return T;
-    return (long long)fec_air_bits((unsigned)fec, fec_kept_bits((unsigned)fec, (unsigned)T));
+    return (long long)fec_air_bits(conv, fec_kept_bits(conv, (unsigned)T));
 }
 
 long long demod_fec_frame_symbols(size_t len, int len_bytes, int crc, int bits, int fec)
@@ -78,19 +93,22 @@ int demod_fec_frame_encode(const uint8_t *data, size_t len, int len_bytes, int c
     const long long Na = fec_frame_air_bits(len, len_bytes, crc, fec);
     if (Na < 0) return (int)Na;
     if ((!data && len) || !out) return DEMOD_BAD_ARG;
-    const long long T = demod_coded_frame_steps(len, len_bytes, crc);
+    const unsigned P = rs_parity((unsigned)fec), conv = rs_mode_conv((unsigned)fec);
+    const long long T = frame_steps(len, len_bytes, crc, P);
     const size_t need = (size_t)(Na + 7) / 8;
     if (need > cap) return DEMOD_BUFFER_TOO_SMALL;
-    uint8_t info[2 + DEMOD_MAX_FRAME_PAYLOAD + 4];
-    const int n = demod_checked_frame_encode(data, len, len_bytes, crc, info, sizeof(info));
+    uint8_t info[2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 19 * RS_MAX_PARITY];   /* the longest n' */
+    int n = demod_checked_frame_encode(data, len, len_bytes, crc, info, sizeof(info));
     if (n < 0) return n;
+    rs_frame_protect(info, (unsigned)n, P);
+    n = (int)rs_frame_bytes((unsigned)n, P);
     memset(out, 0, need);
     unsigned reg = 0;
     for (long long t = 0; t < T; ++t) {
         const unsigned u = t < 8 * (long long)n ? (info[t >> 3] >> (7 - (t & 7))) & 1u : 0u;
         reg = ((reg << 1) | u) & 0x7Fu;
         for (unsigned v = 0; v < 2; ++v) {
-            const unsigned a = fec_air_of_mother((unsigned)fec, 2u * (unsigned)t + v);
+            const unsigned a = fec_air_of_mother(conv, 2u * (unsigned)t + v);
             if (a == FEC_MAP_NONE) continue;   /* punctured */
             out[a >> 3] |= (uint8_t)(parity7(reg & (v ? FEC_G1 : FEC_G0)) << (7 - (a & 7)));
         }
@@ -107,11 +125,12 @@ int demod_coded_frame_encode(const uint8_t *data, size_t len, int len_bytes, int
 /* St of rows of C air bits, or -1 where the row is refused */
 static long long fec_row_steps(size_t C, int len_bytes, int fec)
 {
-    if (!fec_mode_valid((unsigned)fec) || (len_bytes != 1 && len_bytes != 2)) return -1;
-    if (fec_mode_mapped((unsigned)fec) && C > 0xFFFFFFFFu) return -1;
-    const long long St = !fec_mode_mapped((unsigned)fec)
+    if (!conv_mode_valid(fec) || (len_bytes != 1 && len_bytes != 2)) return -1;
+    const unsigned conv = rs_mode_conv((unsigned)fec);
+    if (fec_mode_mapped(conv) && C > 0xFFFFFFFFu) return -1;
+    const long long St = !fec_mode_mapped(conv)
                              ? (long long)(C / 2)
-                             : (long long)fec_steps_within((unsigned)fec, fec_usable_bits((unsigned)fec, (unsigned)C));
+                             : (long long)fec_steps_within(conv, fec_usable_bits(conv, (unsigned)C));
     return St < 8 * len_bytes + DEMOD_FEC_DEPTH ? -1 : St;
 }
 
@@ -181,14 +200,17 @@ static void forward(const int8_t *soft, size_t t_from, size_t t_to, int32_t *M, 
 }
 
 /* the decoder on the 2 St trellis soft values q (punctured positions 0) */
-static int trellis_decode(const int8_t *soft, size_t St, size_t h, size_t c, uint8_t *row, size_t cap,
-                          demod_frame_decode_t *decode)
+static int trellis_decode(const int8_t *soft, size_t St, size_t h, size_t c, unsigned P, uint8_t *row,
+                          size_t cap, demod_frame_decode_t *decode)
 {
     const size_t t0 = 8 * h + DEMOD_FEC_DEPTH;
     const size_t Bd = (St - 6) / 8;
-    if (Bd < h + c || Bd - h - c > DEMOD_MAX_FRAME_PAYLOAD) return DEMOD_BAD_ARG;
+    /* the greatest len whose frame fits the row: n bytes, or with an outer code n' */
+    const long long most = P ? rs_max_len((unsigned)Bd, (unsigned)h, (unsigned)c, P)
+                             : (long long)Bd - (long long)(h + c);
+    if (most < 0 || most > DEMOD_MAX_FRAME_PAYLOAD) return DEMOD_BAD_ARG;
     if (cap < Bd) return DEMOD_BUFFER_TOO_SMALL;
-    const size_t max_len = Bd - h - c;
+    const size_t max_len = (size_t)most;
     uint64_t *surv = (uint64_t *)malloc(St * sizeof(uint64_t));
     uint8_t *bits = (uint8_t *)malloc(St);
     if (!surv || !bits) {
@@ -215,7 +237,7 @@ static int trellis_decode(const int8_t *soft, size_t St, size_t h, size_t c, uin
         for (size_t b = 0; b < h; ++b) row[b] = (uint8_t)(len >> (8 * (h - 1 - b)));
         written = (int)h;
     } else {
-        const size_t n = h + len + c;
+        const size_t n = rs_frame_bytes((unsigned)(h + len + c), P);
         const size_t T = 8 * n + 6 > t0 ? 8 * n + 6 : t0;   /* <= St: n <= Bd */
         forward(soft, t0, T, M, surv);
         trace_back(surv, T, 0, bits);
@@ -242,15 +264,16 @@ int demod_fec_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int
     if (!soft || !row || !decode || c == 0 || n_soft > 0x7FFFFFFF) return DEMOD_BAD_ARG;
     const long long St = fec_row_steps(n_soft, len_bytes, fec);
     if (St < 0) return DEMOD_BAD_ARG;
-    if (!fec_mode_mapped((unsigned)fec)) return trellis_decode(soft, (size_t)St, h, c, row, cap, decode);
+    const unsigned P = rs_parity((unsigned)fec), conv = rs_mode_conv((unsigned)fec);
+    if (!fec_mode_mapped(conv)) return trellis_decode(soft, (size_t)St, h, c, P, row, cap, decode);
     /* the trellis's order: q_m from air position a(m), 0 where m is punctured */
     int8_t *q = (int8_t *)malloc(2 * (size_t)St);
     if (!q) return DEMOD_ALLOC_FAIL;
     for (size_t m = 0; m < 2 * (size_t)St; ++m) {
-        const unsigned a = fec_air_of_mother((unsigned)fec, (unsigned)m);   /* < Cu <= n_soft */
+        const unsigned a = fec_air_of_mother(conv, (unsigned)m);   /* < Cu <= n_soft */
         q[m] = a == FEC_MAP_NONE ? 0 : soft[a];
     }
-    const int rc = trellis_decode(q, (size_t)St, h, c, row, cap, decode);
+    const int rc = trellis_decode(q, (size_t)St, h, c, P, row, cap, decode);
     free(q);
     return rc;
 }

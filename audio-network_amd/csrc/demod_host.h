@@ -11,6 +11,7 @@
 #include "../../include/demod.h"
 #include "demod_internal.h"
 #include "fec_map.h"
+#include "rs_ops.h"
 #include "plan.h"
 
 // Makes `dev` current for the scope of an entry point and restores the
@@ -179,6 +180,7 @@ struct demod {
     fskd::DevBuf<uint8_t> d_fec_rows;
     fskd::DevBuf<demod_frame_decode_t> d_fec_decode;
     fskd::DevBuf<unsigned char> d_fec_work;
+    fskd::DevBuf<demod_frame_rs_t> d_rs;
     fskd::PinnedBuf<int16_t> h_in;      // pinned staging for small host calls
     fskd::PinnedBuf<uint8_t> h_sym;
     fskd::PinnedBuf<float> h_mag;       // [h_sym.cap][k]

@@ -12,6 +12,7 @@ struct demod_frame_hit;
 struct demod_frame_check;
 struct demod_frames_check_result;
 struct demod_frame_decode;
+struct demod_frame_rs;
 struct demod_rx_stream_state;
 struct demod_rx_frame;
 struct demod_rx_summary;
@@ -376,6 +377,7 @@ struct FramesCheckParams {
     int sync_len;                         // L
     int fec_depth;                        // 0: S = ceil(8 n / bits); DEMOD_FEC_DEPTH: the coded span
     int fec;                              // 0 or the coded mode (fec_map.h): the span's Sc
+    int parity;                           // P of the outer code (rs_ops.h) or 0: the span is of n' bytes
     ::demod_frame_check *check;           // [n_groups][max_frames]
     uint32_t *kept;                       // [n_groups][max_frames]
     uint8_t *body;                        // [n_groups][max_frames][max_len] or nullptr
@@ -418,9 +420,27 @@ struct FramesFecParams {
     uint8_t *rows;                        // [n_groups][max_frames][row_bytes]
     struct ::demod_frame_decode *decode;  // [n_groups][max_frames] (struct: demod.h has a function of the name)
     unsigned long long *work;             // [waves of the launch][steps]
-    unsigned fec;                         // the mode (fec_map.h); DEMOD_FEC_CONV_K7: the map is the identity
+    unsigned fec;                         // the coded mode (fec_map.h); DEMOD_FEC_CONV_K7: the map is the identity
+    unsigned parity;                      // P of the outer code (rs_ops.h) or 0: the row holds n' bytes
 };
 hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s);
+
+// frames_rs.hip: the Reed-Solomon outer code over the rows a frame scan or the
+// decode above wrote, in place (groups and rows as frames_check.hip). One wave
+// per row, no workspace.
+struct FramesRsParams {
+    uint8_t *rows;                        // [n_groups][max_frames][row_bytes]
+    const ::demod_frames_result *res;     // [n_groups]
+    unsigned n_groups;
+    unsigned max_frames;                  // n_groups * max_frames < 2^31
+    unsigned row_bytes;                   // W: B, or Bd in a coded mode
+    unsigned max_len;                     // the greatest len with n'(len) <= W; <= DEMOD_MAX_FRAME_PAYLOAD
+    int len_bytes;                        // h
+    int crc_bytes;                        // c
+    int parity;                           // P: 16 or 32
+    ::demod_frame_rs *rs;                 // [n_groups][max_frames]
+};
+hipError_t launch_frames_rs(const FramesRsParams &p, hipStream_t s);
 
 // frames_carry.hip: the receiver's device-resident carry (include/demod.h
 // "receiver"). advance moves each stream's kept windows and its new ones from
@@ -456,7 +476,7 @@ struct RxCollectParams {
     unsigned n_streams;
     unsigned max_frames;                  // n_streams * max_frames < 2^31
     unsigned max_len;
-    int len_bytes, crc_bytes, bits, phases, sync_len, fec_depth, fec;   // as FramesCheckParams
+    int len_bytes, crc_bytes, bits, phases, sync_len, fec_depth, fec, parity;   // as FramesCheckParams
     ::demod_rx_frame *frames;             // [n_streams max_frames]
     uint8_t *bodies;                      // [n_streams max_frames max_len]
     ::demod_rx_summary *summary;
@@ -496,6 +516,8 @@ struct TxParams {
     unsigned max_frames;                  // n_streams * max_frames < 2^31
     unsigned max_len, gap;
     int len_bytes, crc_bytes, fec;        // h, c, 0 or the coded mode (fec_map.h)
+    int parity;                           // P of the outer code (rs_ops.h) or 0
+    unsigned long long rs_g8[4];          // its generator's coefficients g[1 .. 32], eight to a word
     unsigned poly, init;                  // as FramesCheckParams
     unsigned xpow8[kCrcPowBits];
     ::demod_tx_place *place;              // [n_streams][max_frames]

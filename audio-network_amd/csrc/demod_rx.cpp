@@ -29,6 +29,7 @@ struct demod_rx {
     DevBuf<demod_frames_result_t> d_res;  // [S]
     DevBuf<uint8_t> d_rows;               // [S][max_frames][row_bytes]: packed, or decoded
     DevBuf<demod_frame_decode_t> d_decode;
+    DevBuf<demod_frame_rs_t> d_rs;        // with a parity flag: the outer code's records
     DevBuf<demod_frame_check_t> d_check;
     DevBuf<uint32_t> d_kept;
     DevBuf<uint8_t> d_body;
@@ -61,10 +62,11 @@ static int rx_allocate(demod_rx_t *rx)
     HIP_TRY(rx->d_first.reserve(S));
     HIP_TRY(rx->d_count.reserve(S));
     HIP_TRY(rx->d_scan_work.reserve(z.scan_work_bytes));
-    if (rx->rx.fec) {
+    if (rs_mode_conv(rx->rx.fec)) {
         HIP_TRY(rx->d_fec_work.reserve(z.decode_work_bytes));
         HIP_TRY(rx->d_decode.reserve(rows));
     }
+    if (rs_parity(rx->rx.fec)) HIP_TRY(rx->d_rs.reserve(rows));
     HIP_TRY(rx->d_col_work.reserve(z.collect_work_bytes));
     HIP_TRY(rx->d_hits.reserve(rows));
     HIP_TRY(rx->d_res.reserve(S));
@@ -148,6 +150,7 @@ int demod_rx_state(const demod_rx_t *rx, size_t stream, demod_rx_stream_state_t 
 static int rx_run(demod_rx_t *rx, demod_t *st, const StreamsStage &sg)
 {
     const demod_rx_cfg_t &x = rx->rx;
+    const unsigned conv = rs_mode_conv(x.fec);   // the trellis's mode, or 0: the scan writes packed rows
     const size_t S = rx->S, C = x.ring_windows, Wb = sg.Wb, mf = x.max_frames;
     const size_t L = x.sync_len, N = x.frame_symbols;
     // the tables of demod_segments_layout's layout, 16-byte aligned behind the samples
@@ -176,15 +179,22 @@ static int rx_run(demod_rx_t *rx, demod_t *st, const StreamsStage &sg)
     if (rc < 0) return rc;
     rc = demod_frames_segments_async(st, rx->ring_sym[out].p, rx->ring_mag[out].p, S * C, rx->d_first.p,
                                      rx->d_count.p, S, x.sync, L, x.max_errors, N, rx->d_hits.p, nullptr,
-                                     x.fec ? nullptr : rx->d_rows.p, mf, rx->d_res.p, rx->d_scan_work.p,
+                                     conv ? nullptr : rx->d_rows.p, mf, rx->d_res.p, rx->d_scan_work.p,
                                      rx->sz.scan_work_bytes, st->stream);
     if (rc < 0) return rc;
     uint8_t *d_body = rx->sz.max_len ? rx->d_body.p : nullptr;
-    if (x.fec) {
+    if (conv) {
         rc = demod_frames_decode_async(st, rx->d_hits.p, rx->ring_mag[out].p, S * C, rx->d_first.p, rx->d_res.p,
                                        S, mf, L, N, (int)x.len_bytes, (int)x.crc, (int)x.fec, rx->d_rows.p,
                                        rx->d_decode.p, rx->d_fec_work.p, rx->sz.decode_work_bytes, st->stream);
         if (rc < 0) return rc;
+    }
+    if (rs_parity(x.fec)) {   // the outer code over the packed or the decoded rows, before the check reads them
+        rc = demod_frames_rs_async(st, rx->d_rows.p, rx->d_res.p, S, mf, N, (int)x.len_bytes, (int)x.crc,
+                                   (int)x.fec, rx->d_rs.p, st->stream);
+        if (rc < 0) return rc;
+    }
+    if (x.fec) {
         rc = demod_frames_check_coded_async(st, rx->d_hits.p, rx->d_rows.p, rx->d_res.p, S, mf, L, N,
                                             (int)x.len_bytes, (int)x.crc, (int)x.fec, rx->d_check.p,
                                             rx->d_kept.p, d_body, rx->d_chk_sum.p, st->stream);

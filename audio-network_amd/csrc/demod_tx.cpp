@@ -27,8 +27,8 @@ static bool tx_shape(const demod_cfg_t *cfg, const demod_tx_cfg_t *x, size_t S, 
         if (x->idle[i] >= K) return false;
     if (x->len_bytes != 1 && x->len_bytes != 2) return false;
     if (x->crc != DEMOD_CRC16_CCITT_FALSE && x->crc != DEMOD_CRC32_MPEG2) return false;
-    if (x->fec != 0 && !fec_mode_valid(x->fec)) return false;
-    if (x->fec && (K & (K - 1)) != 0) return false;
+    if (x->fec != 0 && !rs_mode_valid(x->fec)) return false;
+    if (rs_mode_conv(x->fec) && (K & (K - 1)) != 0) return false;
     const uint32_t most = x->len_bytes == 1 ? 255u : (uint32_t)DEMOD_MAX_FRAME_PAYLOAD;
     if (x->max_len > most) return false;
     const long long A = demod_tx_frame_symbol_count(x, K, x->max_len);
@@ -58,7 +58,13 @@ static bool tx_shape(const demod_cfg_t *cfg, const demod_tx_cfg_t *x, size_t S, 
     p.gap = x->gap;
     p.len_bytes = (int)x->len_bytes;
     p.crc_bytes = x->crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4;
-    p.fec = (int)x->fec;
+    p.fec = (int)rs_mode_conv(x->fec);
+    p.parity = (int)rs_parity(x->fec);
+    if (p.parity) {
+        uint8_t g[RS_MAX_PARITY + 1];
+        rs_generator((unsigned)p.parity, g);
+        for (int i = 0; i < p.parity; ++i) p.rs_g8[i >> 3] |= (unsigned long long)g[i + 1] << ((i & 7) * 8);
+    }
     p.poly = p.crc_bytes == 2 ? 0x1021u << 16 : 0x04C11DB7u;
     p.init = p.crc_bytes == 2 ? 0xFFFFu << 16 : 0xFFFFFFFFu;
     // x^8, then its squares mod P, as the check passes them (demod_acquire.cpp frames_check_shape)

@@ -10,6 +10,7 @@
 
 #include "../../include/demod.h"
 #include "fec_map.h"
+#include "rs_ops.h"
 
 /* bits, or a negative code for what the format or K rules out */
 static int tx_format_bits(const demod_tx_cfg_t *x, uint32_t k)
@@ -18,8 +19,8 @@ static int tx_format_bits(const demod_tx_cfg_t *x, uint32_t k)
     if (x->sync_len < 1 || x->sync_len > DEMOD_MAX_SYNC) return DEMOD_BAD_ARG;
     if (x->len_bytes != 1 && x->len_bytes != 2) return DEMOD_BAD_ARG;
     if (x->crc != DEMOD_CRC16_CCITT_FALSE && x->crc != DEMOD_CRC32_MPEG2) return DEMOD_BAD_ARG;
-    if (x->fec != 0 && !fec_mode_valid(x->fec)) return DEMOD_BAD_ARG;
-    if (x->fec && (k & (k - 1)) != 0) return DEMOD_BAD_ARG;
+    if (x->fec != 0 && !rs_mode_valid(x->fec)) return DEMOD_BAD_ARG;
+    if (rs_mode_conv(x->fec) && (k & (k - 1)) != 0) return DEMOD_BAD_ARG;
     return demod_bits_per_symbol(k);
 }
 
@@ -29,11 +30,12 @@ long long demod_tx_frame_symbol_count(const demod_tx_cfg_t *x, uint32_t k, size_
     if (bits < 0) return bits;
     if (len > x->max_len) return DEMOD_FRAME_TOO_LARGE;
     long long sp;
-    if (x->fec) {
+    if (rs_mode_conv(x->fec)) {
         sp = demod_fec_frame_symbols(len, (int)x->len_bytes, (int)x->crc, bits, (int)x->fec);
     } else {
+        /* the frame's n bytes, or with an outer code its n' */
         const long long n = demod_checked_frame_size(len, (int)x->len_bytes, (int)x->crc);
-        sp = n < 0 ? n : (8 * n + bits - 1) / bits;
+        sp = n < 0 ? n : (8 * (long long)rs_frame_bytes((unsigned)n, rs_parity(x->fec)) + bits - 1) / bits;
     }
     return sp < 0 ? sp : (long long)x->sync_len + sp;
 }
@@ -51,13 +53,18 @@ long long demod_tx_frame_symbols(const demod_tx_cfg_t *x, uint32_t k, const uint
     const int bits = demod_bits_per_symbol(k);
     /* the frame's bytes, with a 0 byte behind them: the last symbol's missing bits */
     /* (sized by rate 1/2, the most bits, and one interleaver block of rounding) */
-    uint8_t bytes[(2 * (8 * (2 + DEMOD_MAX_FRAME_PAYLOAD + 4) + 6) + 7) / 8 +
+    /* (the frame with the outer code's most parity: 19 codewords of 32 bytes) */
+    uint8_t bytes[(2 * (8 * (2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 19 * RS_MAX_PARITY) + 6) + 7) / 8 +
                   DEMOD_FEC_IL_ROWS * DEMOD_FEC_IL_COLS / 8 + 1];
     memset(bytes, 0, sizeof(bytes));
-    const int nb = x->fec ? demod_fec_frame_encode(data, len, (int)x->len_bytes, (int)x->crc, (int)x->fec,
-                                                   bytes, sizeof(bytes) - 1)
-                          : demod_checked_frame_encode(data, len, (int)x->len_bytes, (int)x->crc, bytes,
-                                                       sizeof(bytes) - 1);
+    int nb;
+    if (rs_mode_conv(x->fec)) {
+        nb = demod_fec_frame_encode(data, len, (int)x->len_bytes, (int)x->crc, (int)x->fec, bytes,
+                                    sizeof(bytes) - 1);
+    } else {
+        nb = demod_checked_frame_encode(data, len, (int)x->len_bytes, (int)x->crc, bytes, sizeof(bytes) - 1);
+        if (nb >= 0) rs_frame_protect(bytes, (unsigned)nb, rs_parity(x->fec));
+    }
     if (nb < 0) return nb;
     memcpy(out, x->sync, L);
     const int rc = demod_unpack_symbols(bytes, (size_t)A - L, bits, out + L, cap - L);

@@ -164,7 +164,8 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_stream_kernel(RxCollec
     for (unsigned i = lane; i < nw; i += kRxLanes) {
         if (p.check[row0 + i].status != DEMOD_CHECK_OK) continue;
         const unsigned S = checked_frame_span(rx_length(p, row0 + i), (unsigned)p.len_bytes,
-                                              (unsigned)p.crc_bytes, (unsigned)p.bits, (unsigned)p.fec_depth, (unsigned)p.fec);
+                                              (unsigned)p.crc_bytes, (unsigned)p.bits, (unsigned)p.fec_depth, (unsigned)p.fec,
+                                              (unsigned)p.parity);
         const unsigned long long end = base + p.hits[row0 + i].window + (L + S) * R;
         if (end > reach) reach = end;
     }

@@ -118,7 +118,8 @@ __global__ __launch_bounds__(kAcqThreads) void frames_select_kernel(FramesCheckP
                 window = p.hits[row0 + i].window;
                 // the frame's symbols on the air: its bytes, or coded 2 T(len) bits
                 const unsigned S = checked_frame_span(p.check[row0 + i].length, (unsigned)p.len_bytes,
-                                                      (unsigned)p.crc_bytes, bits, (unsigned)p.fec_depth, (unsigned)p.fec);
+                                                      (unsigned)p.crc_bytes, bits, (unsigned)p.fec_depth, (unsigned)p.fec,
+                                                      (unsigned)p.parity);
                 end = window + (L + S) * R;
             }
             // inclusive maximum over the lanes up to this one, then over the waves before

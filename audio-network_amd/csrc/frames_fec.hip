@@ -173,7 +173,8 @@ __global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecPar
             out.status = DEMOD_DECODE_BAD_LENGTH;
             out.steps = 0;
         } else {
-            const unsigned n = h + len + (unsigned)p.crc_bytes;             // <= row_bytes
+            // the row's bytes: n, or n' with an outer code (rs_ops.h); <= row_bytes
+            const unsigned n = rs_frame_bytes(h + len + (unsigned)p.crc_bytes, p.parity);
             const unsigned T = 8u * n + 6u > t0 ? 8u * n + 6u : t0;         // <= St
             for (unsigned t = t0; t < T; t += kFecPass)
                 fec_steps<MAPPED>(p, c, live, bw, t, T - t < kFecPass ? T - t : kFecPass, M, slot, lane);

@@ -16,7 +16,12 @@
 //           the places; then tail, accepted, refused.
 //  write    one wave per frame, wave c of a group's wpg waves taking frames c,
 //           c + wpg, .. (wave-uniform). len || data || CRC in the wave's LDS,
-//           the CRC by the check's lane-split scheme (crc_ops.h), then lane j
+//           the CRC by the check's lane-split scheme (crc_ops.h); with an outer
+//           code (rs_ops.h) its parity behind them, 64 / P codewords at a time:
+//           lane (slot, i) holds byte i of the slot's parity register, a step
+//           takes the register's top byte and the neighbour's by shuffle, and
+//           the product with the lane's generator coefficient is a GF(2)-linear
+//           map in eight registers. Then lane j
 //           writes symbols j, j + 64, ..: the word, the payload symbols, the
 //           gap's idle symbols. An air bit goes back through the mode's map
 //           (fec_map.h) to its mother bit m, which reads the information bits
@@ -38,6 +43,7 @@
 #include "../../include/demod.h"
 #include "crc_ops.h"
 #include "fec_map.h"
+#include "rs_ops.h"
 #include "synth_ops.h"
 
 namespace fskd {
@@ -46,8 +52,9 @@ constexpr int kTxThreads = 256;
 constexpr int kTxWaves = kTxThreads / 64;
 constexpr int kTxPhaseRun = 4;        // phase: consecutive symbols a thread sums per step
 constexpr int kTxPhaseMaxWaves = 16;  // phase: waves a stream at most (one workgroup)
-// len || data || CRC of the longest frame, rounded up to a multiple of 8
-constexpr int kTxFrameBytes = (2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 7) / 8 * 8;
+// len || data || CRC || parity of the longest frame (19 codewords of 32 parity
+// bytes), rounded up to a multiple of 8
+constexpr int kTxFrameBytes = (2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 19 * RS_MAX_PARITY + 7) / 8 * 8;
 
 // symbol i < 64 of a pattern packed 16 symbols to a word
 static __device__ __forceinline__ unsigned tx_sym4(const unsigned long long (&w)[4], unsigned i)
@@ -92,7 +99,8 @@ static __device__ __forceinline__ TxState tx_load(const TxParams &p, unsigned s)
 // (coded: Sc of the mode; kept: Nt(T), the frame's code bits, 0 without a code)
 static __device__ __forceinline__ unsigned tx_payload_symbols(const TxParams &p, unsigned len, unsigned &kept)
 {
-    const unsigned nb = (unsigned)p.len_bytes + len + (unsigned)p.crc_bytes, bits = (unsigned)p.bits;
+    const unsigned nb = rs_frame_bytes((unsigned)p.len_bytes + len + (unsigned)p.crc_bytes, (unsigned)p.parity);
+    const unsigned bits = (unsigned)p.bits;
     kept = 0;
     if (!p.fec) return (8 * nb + bits - 1) / bits;
     const unsigned body = 8 * nb + 6, least = 8 * (unsigned)p.len_bytes + DEMOD_FEC_DEPTH;
@@ -172,6 +180,23 @@ __global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsign
     const unsigned C = p.ring_symbols, L = p.sync_len;
     uint8_t *buf = s_frame[wave];
     uint8_t *ring = p.ring + (size_t)g * C;
+    // the outer code: lane (slot, si) of 64 / P slots; times the lane's generator
+    // coefficient g[si + 1] as a GF(2)-linear map, col[b] = g[si + 1] alpha^b
+    const unsigned P = (unsigned)p.parity;   // 0, 16 or 32
+    const unsigned slot = P == 16 ? (unsigned)lane >> 4 : (unsigned)lane >> 5, si = P ? (unsigned)lane & (P - 1u) : 0u;
+    unsigned col[8];
+    {
+        unsigned long long w = p.rs_g8[0];
+        if ((si >> 3) == 1) w = p.rs_g8[1];
+        if ((si >> 3) == 2) w = p.rs_g8[2];
+        if ((si >> 3) == 3) w = p.rs_g8[3];
+        unsigned a = (unsigned)(w >> ((si & 7u) * 8u)) & 0xFFu;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            col[b] = a;
+            a = rs_xtime(a);
+        }
+    }
     for (unsigned i = c; i < cnt; i += wpg) {   // the same for every lane of the wave
         const size_t r = (size_t)g * p.max_frames + i;
         const demod_tx_place_t pl = p.place[r];   // plan's, of this call
@@ -190,11 +215,39 @@ __global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsign
             buf[h + b] = b < lenc ? p.bytes[off + b] : (uint8_t)0;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        const unsigned n = h + len, nb = n + cb;
+        const unsigned n = h + len;
+        unsigned nb = n + cb;
         const unsigned crc = crc_wave<WIDTH>(buf, n, lane, p.init, p.poly, p.xpow8, s_tab) >> (32 - WIDTH);
         if (lane < (int)cb) buf[n + lane] = (uint8_t)(crc >> (8 * (cb - 1 - (unsigned)lane)));
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
+        if (P) {
+            const unsigned n0 = nb, D = rs_codewords(n0, P);
+            for (unsigned j0 = 0; j0 < D; j0 += 64u / P) {   // the same for every lane of the wave
+                const unsigned j = j0 + slot;
+                const bool have = j < D;
+                const unsigned kj = have ? rs_message_bytes(n0, D, j) : 0u;
+                const unsigned kmost = rs_message_bytes(n0, D, j0);   // k_j does not grow with j
+                unsigned par = 0, at = j;
+                for (unsigned x = 0; x < kmost; ++x) {
+                    // the register's top byte (the slot's lane 0) and the byte below this lane's
+                    const unsigned top = (unsigned)__shfl((int)par, (int)(slot * P));
+                    const unsigned below = (unsigned)__shfl((int)par, lane < 63 ? lane + 1 : lane);
+                    if (have && x < kj) {
+                        const unsigned f = buf[at] ^ top;
+                        unsigned v = si + 1u < P ? below : 0u;
+#pragma unroll
+                        for (int b = 0; b < 8; ++b) v ^= ((f >> b) & 1u) ? col[b] : 0u;
+                        par = v;
+                        at += D;
+                    }
+                }
+                if (have) buf[n0 + si * D + j] = (uint8_t)par;   // parity byte si D + j
+            }
+            nb = n0 + D * P;   // n' <= kTxFrameBytes: len <= max_len <= DEMOD_MAX_FRAME_PAYLOAD
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
         unsigned kept;
         const unsigned A = L + tx_payload_symbols(p, len, kept);
         const unsigned total = A + p.gap;            // <= C

@@ -1009,7 +1009,8 @@ size_t demod_fec_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, 
  * [n_groups][max_frames][Bd], d_decode [n_groups][max_frames]. Returns DEMOD_OK
  * once enqueued; DEMOD_BAD_ARG, before any launch, for what
  * demod_frames_check_async refuses about its own arguments and: K not a power
- * of two, the refused row shapes above, a fec outside the six modes, a NULL
+ * of two, the refused row shapes above, a fec that is not one of the six modes
+ * (each with or without a parity flag of "Reed-Solomon outer code"), a NULL
  * d_mags, d_rows, d_decode or d_work, a misaligned d_decode (4 bytes), d_work
  * or d_first (8 bytes), work_bytes below demod_fec_decode_workspace_size,
  * n_windows >= 2^31, (sync_len + frame_symbols) R >= 2^31.
@@ -1023,9 +1024,13 @@ int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, cons
 
 /*
  * demod_frames_check_async over decoded rows: the same launches and outputs
- * with the row width Bd (max_len = Bd - h - c) and, for `covered`, the coded
- * span S = ceil(2 T(len) / bits). Refuses what demod_frames_check_async and
- * demod_frames_decode_async refuse about the same arguments.
+ * with the row width Bd and, for `covered`, the coded span S = ceil(2 T(len) /
+ * bits); max_len = Bd - h - c in the six coded modes. Refuses what
+ * demod_frames_check_async and demod_frames_decode_async refuse about the same
+ * arguments. Takes the 20 modes of "Reed-Solomon outer code": with a parity
+ * flag max_len is the greatest len with n'(len) <= the row width and the span
+ * follows n'; with the low nibble 0 the rows are the scan's packed rows of B
+ * bytes and the span is ceil(8 n' / bits).
  */
 int demod_frames_check_coded_async(demod_t *st, const demod_frame_hit_t *d_hits, const uint8_t *d_rows,
                                    const demod_frames_result_t *d_results, size_t n_groups,
@@ -1037,13 +1042,137 @@ int demod_frames_check_coded_async(demod_t *st, const demod_frame_hit_t *d_hits,
 /*
  * demod_frames_checked for coded frames: detector, frame scan (no packed rows),
  * decode, coded check and the kept rows, on handle-owned buffers. Arguments,
- * outputs and return value as demod_frames_checked, with max_len = Bd - h - c.
+ * outputs and return value as demod_frames_checked, with the mode's max_len:
+ * Bd - h - c in the six coded modes. Takes the 20 modes of "Reed-Solomon outer
+ * code": with a parity flag max_len is the greatest len with n'(len) <= the
+ * row width and demod_frames_rs_async runs before the check; with the low
+ * nibble 0 the scan writes packed rows (the row width is B) and nothing is
+ * decoded.
  */
 int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const uint8_t *sync,
                        size_t sync_len, uint32_t max_errors, size_t frame_symbols, int len_bytes,
                        int crc, int fec, demod_frame_hit_t *hits, uint32_t *lengths, uint8_t *body,
                        size_t max_frames, demod_frames_result_t *result,
                        demod_frames_check_result_t *summary);
+
+/* ---- Reed-Solomon outer code: a few wrong bytes, wherever they sit -------- */
+/*
+ * The CRC only detects. At fec == 0 one wrongly decided symbol loses the
+ * frame; in a coded mode the frame is lost whenever the Viterbi decoder leaves
+ * the correct path, and its errors then come as a short burst of wrong bytes.
+ * A byte-oriented outer code corrects both. Two more flags of `fec` name it:
+ *
+ *   DEMOD_FEC_RS16  P = 16 parity bytes a codeword, t = 8 wrong bytes corrected
+ *   DEMOD_FEC_RS32  P = 32, t = 16                  (both together: refused)
+ *
+ * Each of the six coded modes takes none or one of them, and each flag stands
+ * alone (low nibble 0: no convolutional code): 20 non-zero values in all.
+ *
+ * The field is GF(2^8) with the reduction polynomial 0x11D and alpha = 2; the
+ * generator is g(x) = prod_{i < P} (x - alpha^i). A codeword of the message
+ * m[0 .. k) is systematic: m[0] is the highest coefficient, the parity is the
+ * remainder of m(x) x^P by g, highest degree first, and the codeword is m ||
+ * parity, shortened (the missing leading symbols are 0 and are never sent).
+ *
+ * The protected frame. With F = len || data || CRC, the n = h + len + c bytes
+ * of "checked frames", and k_max = 255 - P: D = ceil(n / k_max) codewords,
+ * byte-interleaved. Codeword j < D has the message bytes F[j], F[j + D], ..
+ * (k_j = ceil((n - j) / D) of them); the frame is F followed by D P parity
+ * bytes, parity byte i D + j being byte i of codeword j's parity. n'(len) = n +
+ * D P, which increases strictly with len. With the low nibble 0 the n' bytes go
+ * on the air as a plain frame does, S = ceil(8 n' / bits) symbols; with
+ * DEMOD_FEC_CONV_K7 they are the information bits of the unchanged trellis,
+ * T(len) = max(8 n' + 6, 8 h + DEMOD_FEC_DEPTH).
+ *
+ * Rows of W bytes (B, or Bd in a coded mode) hold max_len = the greatest len
+ * with n'(len) <= W; W < n'(0) and max_len > DEMOD_MAX_FRAME_PAYLOAD are
+ * refused.
+ *
+ * The length header is read as it is: from the row, or by the Viterbi header
+ * look-ahead. It is covered by codeword 0 (and codeword 1 when h = 2 and D >=
+ * 2), so a wrong header is detected (the codewords it lays out do not decode,
+ * or the CRC fails), not repaired: a frame whose header bytes are wrong is
+ * lost.
+ *
+ * The decoder is defined by its result. For each codeword, with the received
+ * word r of k_j + P symbols: if a codeword c of the shortened code has d(r, c)
+ * <= t it is unique, r is replaced by c and e_j = d; otherwise the codeword's
+ * bytes stay as they are and it counts as failed (a locator with a root outside
+ * the k_j + P positions, or with fewer roots than its degree, is a failure).
+ * The record of a row:
+ *
+ *   status     DEMOD_RS_OK every codeword decoded; DEMOD_RS_BAD_LENGTH len >
+ *              max_len (nothing past the header is read, the other fields 0);
+ *              DEMOD_RS_FAILED at least one codeword failed (the others are
+ *              still corrected)
+ *   codewords  D;  corrected  sum of e_j;  failed  the codewords that failed
+ *
+ * The CRC stays the arbiter of a frame: the check does not read this record.
+ *
+ * Not here: erasure decoding, passing the Viterbi decoder's reliability to the
+ * outer code, protecting the length header, the multi-GPU group, fskrx options.
+ *
+ * Every entry that takes `fec` takes the 20 modes where the frame alone is
+ * concerned (the check, the one-shot call, the receiver, the transmitter, the
+ * demod_rs_* codec); the trellis's own functions (demod_fec_*,
+ * demod_frames_decode_async) refuse a mode without the convolutional code and
+ * size the frame by n', and demod_fec_frame_decode is the Viterbi part alone,
+ * writing n' bytes.
+ */
+#define DEMOD_FEC_RS16          0x100
+#define DEMOD_FEC_RS32          0x200  /* both parity flags together: refused */
+
+#define DEMOD_RS_OK             0
+#define DEMOD_RS_BAD_LENGTH     1   /* len > max_len; the other fields 0 */
+#define DEMOD_RS_FAILED         2   /* at least one codeword failed */
+
+typedef struct demod_frame_rs {
+    uint32_t status, codewords, corrected, failed;
+} demod_frame_rs_t;
+
+/* The host codec; no device needed. `fec` is any of the 20 modes (without a
+ * parity flag n' = n and there is nothing to decode); another value is refused
+ * with DEMOD_BAD_ARG.
+ *   generator     g of 1 <= parity_bytes <= 32 roots into g[0 .. parity_bytes],
+ *                 highest coefficient first; returns parity_bytes + 1
+ *   encode        the parity of one codeword's message msg[0 .. k), k +
+ *                 parity_bytes <= 255; returns parity_bytes
+ *   frame_size    n'(len), or what demod_checked_frame_size refuses
+ *   max_len       of rows of row_bytes bytes; DEMOD_BAD_ARG when none fits
+ *   frame_encode  the n' bytes into out[0 .. cap); returns n', what
+ *                 demod_checked_frame_encode refuses or DEMOD_BUFFER_TOO_SMALL
+ *   frame_decode  the decoder above on row[0 .. cap), in place: the reference
+ *                 of demod_frames_rs_async, bit for bit. cap is the row width
+ *                 W that decides max_len. Returns the bytes it covered (n', or h
+ *                 with DEMOD_RS_BAD_LENGTH), or DEMOD_BAD_ARG for a NULL
+ *                 pointer, a bad len_bytes, crc or fec or a refused row width. */
+int demod_rs_generator(int parity_bytes, uint8_t *g);
+int demod_rs_encode(const uint8_t *msg, size_t k, int parity_bytes, uint8_t *parity);
+long long demod_rs_frame_size(size_t len, int len_bytes, int crc, int fec);
+long long demod_rs_max_len(size_t row_bytes, int len_bytes, int crc, int fec);
+int demod_rs_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, int fec, uint8_t *out,
+                          size_t cap);
+int demod_rs_frame_decode(uint8_t *row, size_t cap, int len_bytes, int crc, int fec, demod_frame_rs_t *out);
+
+/*
+ * The device stage, between the scan (low nibble 0: over its d_packed) or
+ * demod_frames_decode_async (a coded mode: over its d_rows) and
+ * demod_frames_check_coded_async. Enqueued on `stream`: one launch whatever the
+ * counts are. No workspace, no atomics, no floating point; nothing is allocated
+ * or synchronised and the handle keeps no state of the call, so it can be
+ * captured behind the scan and replayed. Groups and rows as "checked frames";
+ * the counts are read and clamped on the device, and no content of a row or a
+ * result moves a read or a write outside the rows. It corrects the rows in
+ * place. Written: bytes among the first n'(len) of rows i < nw_g that a decoded
+ * codeword changes; every byte of their d_rs records ([n_groups][max_frames]);
+ * nothing else. Returns DEMOD_OK once enqueued; DEMOD_BAD_ARG, before the
+ * launch, for what demod_frames_check_coded_async refuses about the same
+ * arguments, a fec without a parity flag, a NULL d_rs or one misaligned (4
+ * bytes).
+ */
+int demod_frames_rs_async(demod_t *st, uint8_t *d_rows, const demod_frames_result_t *d_results,
+                          size_t n_groups, size_t max_frames, size_t frame_symbols, int len_bytes, int crc,
+                          int fec, demod_frame_rs_t *d_rs, void *stream);
 
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
@@ -1177,7 +1306,7 @@ typedef struct demod_rx_cfg {
     uint32_t sync_len, max_errors;
     uint32_t frame_symbols;            /* N */
     uint32_t len_bytes, crc;           /* h; DEMOD_CRC16_CCITT_FALSE or DEMOD_CRC32_MPEG2 */
-    uint32_t fec;                      /* 0 or one of the six coded modes */
+    uint32_t fec;                      /* 0 or one of the 20 modes ("Reed-Solomon outer code") */
     uint32_t max_frames;               /* rows per stream and push */
     uint32_t ring_windows;             /* C */
 } demod_rx_cfg_t;
@@ -1389,7 +1518,7 @@ typedef struct demod_tx_cfg {          /* 184 bytes, no padding */
     uint8_t  sync[DEMOD_MAX_SYNC];     /* the word, sync_len symbols, each < K */
     uint32_t sync_len;                 /* L, 1 .. DEMOD_MAX_SYNC */
     uint32_t len_bytes, crc;           /* h; DEMOD_CRC16_CCITT_FALSE or DEMOD_CRC32_MPEG2 */
-    uint32_t fec;                      /* 0 or one of the six coded modes */
+    uint32_t fec;                      /* 0 or one of the 20 modes ("Reed-Solomon outer code") */
     uint32_t max_len;                  /* <= min(256^h - 1, DEMOD_MAX_FRAME_PAYLOAD) */
     uint32_t gap;                      /* idle symbols behind each frame */
     uint8_t  idle[DEMOD_MAX_SYNC];     /* the idle pattern, idle_len symbols, each < K */
