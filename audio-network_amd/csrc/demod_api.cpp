@@ -1,7 +1,8 @@
 // demod_api.cpp — C ABI host layer of libfskdemod.so (include/demod.h): the
 // handle, the batch and streaming entry points, the segment layout, synth,
-// framing, strerror and version. What runs on the detector's outputs
-// (acquisition, frames) is demod_acquire.cpp; many streams, demod_streams.cpp.
+// framing, strerror and version. What runs on the detector's outputs is
+// demod_acquire.cpp (acquisition, frame scans) and demod_frames.cpp (the stages
+// over a scan's rows); many streams, demod_streams.cpp.
 //
 // Handle lifecycle mirrors the Opus decoder the reference receiver drives
 // (opus_decoder_create/destroy, hardware/src/playback.cpp:67-74); streaming

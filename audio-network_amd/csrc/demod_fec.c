@@ -14,9 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../include/demod.h"
-#include "fec_map.h"
-#include "rs_ops.h"
+#include "frame_shape.h"
 
 #define FEC_G0 0171u
 #define FEC_G1 0133u
@@ -28,12 +26,6 @@ static unsigned parity7(unsigned v)
     v ^= v >> 2;
     v ^= v >> 1;
     return v & 1u;
-}
-
-/* c: the CRC's bytes, or 0 for an unknown kind */
-static size_t crc_bytes(int crc)
-{
-    return crc == DEMOD_CRC16_CCITT_FALSE ? 2 : crc == DEMOD_CRC32_MPEG2 ? 4 : 0;
 }
 
 /* T(len) of the frame's n bytes, or with an outer code of P parity bytes its n' */
@@ -122,23 +114,12 @@ int demod_coded_frame_encode(const uint8_t *data, size_t len, int len_bytes, int
     return demod_fec_frame_encode(data, len, len_bytes, crc, DEMOD_FEC_CONV_K7, out, cap);
 }
 
-/* St of rows of C air bits, or -1 where the row is refused */
-static long long fec_row_steps(size_t C, int len_bytes, int fec)
-{
-    if (!conv_mode_valid(fec) || (len_bytes != 1 && len_bytes != 2)) return -1;
-    const unsigned conv = rs_mode_conv((unsigned)fec);
-    if (fec_mode_mapped(conv) && C > 0xFFFFFFFFu) return -1;
-    const long long St = !fec_mode_mapped(conv)
-                             ? (long long)(C / 2)
-                             : (long long)fec_steps_within(conv, fec_usable_bits(conv, (unsigned)C));
-    return St < 8 * len_bytes + DEMOD_FEC_DEPTH ? -1 : St;
-}
-
 long long demod_fec_row_bytes(size_t frame_symbols, int bits, int len_bytes, int fec)
 {
     if (bits < 1 || bits > 4 || frame_symbols > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const long long St = fec_row_steps(frame_symbols * (size_t)bits, len_bytes, fec);
-    return St < 0 ? DEMOD_BAD_ARG : (St - 6) / 8;
+    if (!conv_mode_valid(fec) || (len_bytes != 1 && len_bytes != 2)) return DEMOD_BAD_ARG;
+    const long long St = (long long)frame_row_steps(rs_mode_conv((unsigned)fec), frame_symbols * (size_t)bits);
+    return St < 8 * len_bytes + DEMOD_FEC_DEPTH ? DEMOD_BAD_ARG : (St - 6) / 8;
 }
 
 long long demod_coded_row_bytes(size_t frame_symbols, int bits, int len_bytes)
@@ -199,18 +180,13 @@ static void forward(const int8_t *soft, size_t t_from, size_t t_to, int32_t *M, 
     }
 }
 
-/* the decoder on the 2 St trellis soft values q (punctured positions 0) */
-static int trellis_decode(const int8_t *soft, size_t St, size_t h, size_t c, unsigned P, uint8_t *row,
-                          size_t cap, demod_frame_decode_t *decode)
+/* the decoder on the 2 St trellis soft values q (punctured positions 0) of a row of shape z, into its Bd bytes */
+static int trellis_decode(const int8_t *soft, const struct frame_shape *z, uint8_t *row,
+                          demod_frame_decode_t *decode)
 {
+    const size_t St = z->steps, h = (size_t)z->len_bytes, c = (size_t)z->crc_bytes, max_len = z->max_len;
+    const unsigned P = (unsigned)z->parity;
     const size_t t0 = 8 * h + DEMOD_FEC_DEPTH;
-    const size_t Bd = (St - 6) / 8;
-    /* the greatest len whose frame fits the row: n bytes, or with an outer code n' */
-    const long long most = P ? rs_max_len((unsigned)Bd, (unsigned)h, (unsigned)c, P)
-                             : (long long)Bd - (long long)(h + c);
-    if (most < 0 || most > DEMOD_MAX_FRAME_PAYLOAD) return DEMOD_BAD_ARG;
-    if (cap < Bd) return DEMOD_BUFFER_TOO_SMALL;
-    const size_t max_len = (size_t)most;
     uint64_t *surv = (uint64_t *)malloc(St * sizeof(uint64_t));
     uint8_t *bits = (uint8_t *)malloc(St);
     if (!surv || !bits) {
@@ -260,20 +236,21 @@ static int trellis_decode(const int8_t *soft, size_t St, size_t h, size_t c, uns
 int demod_fec_frame_decode(const int8_t *soft, size_t n_soft, int len_bytes, int crc, int fec, uint8_t *row,
                            size_t cap, demod_frame_decode_t *decode)
 {
-    const size_t c = crc_bytes(crc), h = (size_t)len_bytes;
-    if (!soft || !row || !decode || c == 0 || n_soft > 0x7FFFFFFF) return DEMOD_BAD_ARG;
-    const long long St = fec_row_steps(n_soft, len_bytes, fec);
-    if (St < 0) return DEMOD_BAD_ARG;
-    const unsigned P = rs_parity((unsigned)fec), conv = rs_mode_conv((unsigned)fec);
-    if (!fec_mode_mapped(conv)) return trellis_decode(soft, (size_t)St, h, c, P, row, cap, decode);
+    struct frame_shape z;   /* of a row of n_soft one-bit symbols */
+    if (!soft || !row || !decode || !conv_mode_valid(fec)) return DEMOD_BAD_ARG;
+    if (frame_shape_fill(&z, 1, 1, n_soft, len_bytes, crc, fec)) return DEMOD_BAD_ARG;
+    if (cap < z.row_bytes) return DEMOD_BUFFER_TOO_SMALL;
+    const unsigned conv = (unsigned)z.fec;
+    const size_t St = z.steps;
+    if (!fec_mode_mapped(conv)) return trellis_decode(soft, &z, row, decode);
     /* the trellis's order: q_m from air position a(m), 0 where m is punctured */
-    int8_t *q = (int8_t *)malloc(2 * (size_t)St);
+    int8_t *q = (int8_t *)malloc(2 * St);
     if (!q) return DEMOD_ALLOC_FAIL;
-    for (size_t m = 0; m < 2 * (size_t)St; ++m) {
+    for (size_t m = 0; m < 2 * St; ++m) {
         const unsigned a = fec_air_of_mother(conv, (unsigned)m);   /* < Cu <= n_soft */
         q[m] = a == FEC_MAP_NONE ? 0 : soft[a];
     }
-    const int rc = trellis_decode(q, (size_t)St, h, c, P, row, cap, decode);
+    const int rc = trellis_decode(q, &z, row, decode);
     free(q);
     return rc;
 }

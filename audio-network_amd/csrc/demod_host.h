@@ -1,17 +1,18 @@
 // demod_host.h — what the host layer's files share (private): demod_api.cpp
 // (handle, batch and streaming entry points), demod_acquire.cpp (acquisition
-// and frame entry points on the detector's outputs), demod_streams.cpp (many
-// streams behind one handle) and demod_rx.cpp (the receiver handle).
+// and the frame scans on the detector's outputs), demod_frames.cpp (the stages
+// over a scan's rows), demod_streams.cpp (many streams behind one handle),
+// demod_rx.cpp and demod_tx.cpp (receiver and transmitter: stages and handle).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 
 #include "../../include/demod.h"
 #include "demod_internal.h"
-#include "fec_map.h"
-#include "rs_ops.h"
+#include "frame_shape.h"
 #include "plan.h"
 
 // Makes `dev` current for the scope of an entry point and restores the
@@ -217,6 +218,128 @@ int ensure_host(demod_t *st, size_t samples, size_t windows);
 int ensure_dev(demod_t *st, size_t samples, size_t windows, bool mags);
 // Device or managed memory (a host pointer, or one the runtime does not know: false).
 bool is_device_ptr(const void *p);
+
+// ---- what the entry points on the detector's outputs share (demod_acquire.cpp and on) ----
+
+// Every pointer on an 8-byte (4-byte) boundary; a null pointer is.
+template <class... T> static inline bool aligned8(const T *...p) { return (((uintptr_t)p | ...) & 7) == 0; }
+template <class... T> static inline bool aligned4(const T *...p) { return (((uintptr_t)p | ...) & 3) == 0; }
+
+// R = n / hop when it divides and is at most DEMOD_MAX_PHASES, else 0 (n and
+// hop are powers of two for every valid configuration, so R is one)
+static inline uint32_t acquire_phases(const demod_cfg_t &c)
+{
+    if (c.hop == 0 || c.n % c.hop != 0) return 0;
+    const uint32_t r = c.n / c.hop;
+    return (r >= 1 && r <= DEMOD_MAX_PHASES && (r & (r - 1)) == 0) ? r : 0;
+}
+
+// Bytes of a packed row: N symbols of `bits` bits, MSB first, the last byte padded
+static inline size_t packed_row_bytes(size_t N, size_t bits) { return (N * bits + 7) / 8; }
+
+// Rows a synchronous wrapper keeps on the device for `windows` windows: the
+// caller's cap, or every row there can be. Acquisition writes one symbol per R
+// windows (n_out <= ceil(W / R)); complete hits are starts on one phase whose
+// frame fits, so W / R + 1 bounds them too.
+static inline size_t hit_cap(size_t cap, size_t windows, uint32_t R) { return std::min(cap, windows / R + 1); }
+
+// Groups (segments, streams) of max_frames rows each: 1 .. DEMOD_MAX_SEGMENTS groups and fewer than 2^31
+// rows in all. The frame scans take max_frames == 0 (they only count); the stages over rows do not.
+static inline bool group_rows_ok(size_t n_groups, size_t max_frames, bool rows_may_be_zero)
+{
+    if (n_groups == 0 || n_groups > DEMOD_MAX_SEGMENTS || max_frames > 0x7FFFFFFF) return false;
+    return max_frames ? (unsigned long long)n_groups * max_frames <= 0x7FFFFFFFull : rows_may_be_zero;
+}
+
+// The configuration's R when the shape and the sync word are acceptable, else
+// 0. whole: the batch is acquired as one stream and needs R windows (a segment
+// with fewer is an outcome of the segmented call, not a refusal).
+static inline uint32_t acquire_args(const demod_cfg_t &cfg, size_t n_windows, const uint8_t *sync,
+                                    size_t sync_len, uint32_t max_errors, bool whole)
+{
+    const uint32_t R = acquire_phases(cfg);
+    if (R == 0 || (whole && n_windows < R) || n_windows > 0x7FFFFFFF) return 0;
+    if (sync_len > DEMOD_MAX_SYNC || (sync_len && (!sync || max_errors >= sync_len))) return 0;
+    for (size_t i = 0; i < sync_len; ++i)
+        if (sync[i] >= cfg.k) return 0;
+    return R;
+}
+
+// R when a frame scan of these arguments is acceptable, else 0: what
+// acquire_args refuses, no word, or a frame of 2^31 windows or more.
+static inline uint32_t frames_args(const demod_cfg_t &cfg, size_t n_windows, const uint8_t *sync,
+                                        size_t sync_len, uint32_t max_errors, size_t frame_symbols,
+                                        size_t max_frames, bool whole)
+{
+    const uint32_t R = acquire_args(cfg, n_windows, sync, sync_len, max_errors, whole);
+    if (R == 0 || sync_len == 0 || max_frames > 0x7FFFFFFF) return 0;
+    if (frame_symbols > 0x7FFFFFFF || (sync_len + frame_symbols) * R > 0x7FFFFFFF) return 0;
+    return R;
+}
+
+// The synchronous wrappers' first half, on st->stream: the batch's samples on
+// the device (host samples are copied to st->d_in, a device pointer is read in
+// place), then the detector into st->d_sym and st->d_mag.
+static inline int stage_and_detect(demod_t *st, const int16_t *pcm, size_t n_windows)
+{
+    const size_t n_samples = (n_windows - 1) * st->cfg.hop + st->cfg.n;
+    const bool din = is_device_ptr(pcm);
+    int rc;
+    if ((rc = ensure_dev(st, din ? 0 : n_samples, n_windows, true)) != DEMOD_OK) return rc;
+    if (!din)
+        HIP_TRY(hipMemcpyAsync(st->d_in.p, pcm, n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
+                               st->stream));
+    rc = enqueue_batch(st, din ? pcm : st->d_in.p, n_windows, st->d_sym.p, st->d_mag.p, st->stream);
+    return rc < 0 ? rc : DEMOD_OK;
+}
+
+// What every stage over a scan's rows asks of its call: the configuration's R, the groups and rows, the word's
+// length and the row's shape (fec 0: the scan's packed rows). R with the shape filled, or 0 for what they refuse.
+static inline uint32_t stage_shape(const demod_cfg_t &cfg, size_t n_groups, size_t max_frames, size_t sync_len,
+                                   size_t frame_symbols, int len_bytes, int crc, int fec, frame_shape &s)
+{
+    const uint32_t R = acquire_phases(cfg);
+    if (R == 0 || !group_rows_ok(n_groups, max_frames, false) || sync_len == 0 || sync_len > DEMOD_MAX_SYNC)
+        return 0;
+    const int bits = demod_bits_per_symbol(cfg.k);
+    return frame_shape_fill(&s, bits, cfg.k == (1u << bits), frame_symbols, len_bytes, crc, fec) ? 0 : R;
+}
+
+// The shape fields FramesCheckParams, FramesFecParams and RxCollectParams name alike, from the row's shape
+// (frame_shape.h) and the call's rows, R and L. What a block calls its own (its groups, row_bytes, steps,
+// fec_depth) its entry point sets; FramesRsParams, with no span on the air, is filled there whole.
+template <class P>
+static inline void fill_shape_fields(P &p, const frame_shape &s, size_t max_frames, uint32_t R, size_t sync_len)
+{
+    p.max_frames = (unsigned)max_frames;
+    p.max_len = s.max_len;
+    p.len_bytes = s.len_bytes;
+    p.crc_bytes = s.crc_bytes;
+    p.bits = s.bits;
+    p.phases = (int)R;
+    p.sync_len = (int)sync_len;
+    p.fec = s.fec;
+    p.parity = s.parity;
+}
+
+// poly, init and xpow8[] of the CRC of crc_bytes bytes (FramesCheckParams, TxParams): the register in the top
+// 8 c bits of the word; x^8, then its squares mod P (Horner over the square's own coefficients, highest first).
+template <class P>
+static inline void fill_crc_fields(P &p, int crc_bytes)
+{
+    static_assert(DEMOD_MAX_FRAME_PAYLOAD + 2 < (1 << kCrcPowBits), "bytes after a lane's chunk");
+    p.poly = crc_bytes == 2 ? 0x1021u << 16 : 0x04C11DB7u;
+    p.init = crc_bytes == 2 ? 0xFFFFu << 16 : 0xFFFFFFFFu;
+    const int width = 8 * crc_bytes;
+    p.xpow8[0] = 1u << (32 - width + 8);
+    for (int j = 1; j < kCrcPowBits; ++j) {
+        const uint32_t a = p.xpow8[j - 1];
+        uint32_t r = 0, b = a;
+        for (int i = 0; i < width; ++i, b <<= 1)
+            r = (r << 1) ^ ((r >> 31) ? p.poly : 0u) ^ ((b >> 31) ? a : 0u);
+        p.xpow8[j] = r;
+    }
+}
 
 // demod_streams.cpp: the staging half of a push, shared by demod_streams_push
 // and demod_rx_push (demod_rx.cpp). After streams_check (plan.h) has admitted

@@ -18,13 +18,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "../../include/demod.h"
-#include "rs_ops.h"
-
-static size_t crc_bytes(int crc)
-{
-    return crc == DEMOD_CRC16_CCITT_FALSE ? 2 : crc == DEMOD_CRC32_MPEG2 ? 4 : 0;
-}
+#include "frame_shape.h"
 
 static void build_tables(uint8_t *exp, uint8_t *log)
 {
@@ -61,10 +55,10 @@ long long demod_rs_frame_size(size_t len, int len_bytes, int crc, int fec)
 
 long long demod_rs_max_len(size_t row_bytes, int len_bytes, int crc, int fec)
 {
-    const size_t c = crc_bytes(crc);
+    const int c = frame_crc_bytes(crc);
     if (!rs_mode_valid((unsigned)fec) || c == 0 || (len_bytes != 1 && len_bytes != 2) || row_bytes > 0x7FFFFFFF)
         return DEMOD_BAD_ARG;
-    const long long m = rs_max_len((unsigned)row_bytes, (unsigned)len_bytes, (unsigned)c, rs_parity((unsigned)fec));
+    const long long m = frame_max_len((unsigned)row_bytes, (unsigned)len_bytes, (unsigned)c, rs_parity((unsigned)fec));
     return m < 0 ? DEMOD_BAD_ARG : m;
 }
 
@@ -158,11 +152,11 @@ static int decode_codeword(uint8_t *r, unsigned N, unsigned P, const uint8_t *ex
 
 int demod_rs_frame_decode(uint8_t *row, size_t cap, int len_bytes, int crc, int fec, demod_frame_rs_t *out)
 {
-    const size_t c = crc_bytes(crc), h = (size_t)len_bytes;
+    const size_t c = (size_t)frame_crc_bytes(crc), h = (size_t)len_bytes;
     if (!row || !out || c == 0 || (len_bytes != 1 && len_bytes != 2) || cap > 0x7FFFFFFF) return DEMOD_BAD_ARG;
     if (!rs_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
     const unsigned P = rs_parity((unsigned)fec);
-    const long long max_len = rs_max_len((unsigned)cap, (unsigned)h, (unsigned)c, P);
+    const long long max_len = frame_max_len((unsigned)cap, (unsigned)h, (unsigned)c, P);
     if (max_len < 0 || max_len > DEMOD_MAX_FRAME_PAYLOAD) return DEMOD_BAD_ARG;
     memset(out, 0, sizeof(*out));
     unsigned len = row[0];

@@ -1,10 +1,11 @@
-// demod_rx.cpp — the receiver handle (include/demod.h "receiver"): live streams
-// in, checked frames out. It owns a demod_streams_t for the sample side of a
-// push (carries, lead-in, staging: demod_streams.cpp's own functions) and, on
-// the device, two [S][C] rings of detector outputs, the stages' buffers and one
-// output block; a push is one copy in, the stages' launches on the detector
-// handle's stream (demod_acquire.cpp's *_async entries, as any caller would
-// chain them) and one copy out.
+// demod_rx.cpp — the receiver (include/demod.h "receiver"): live streams in,
+// checked frames out. The sizes and the two device stages' entry points
+// (frames_carry.hip), and the handle. It owns a demod_streams_t for the sample
+// side of a push (carries, lead-in, staging: demod_streams.cpp's own functions)
+// and, on the device, two [S][C] rings of detector outputs, the stages' buffers
+// and one output block; a push is one copy in, the stages' launches on the
+// detector handle's stream (the *_async entries of demod_acquire.cpp, demod_frames.cpp
+// and this file, as any caller would chain them) and one copy out.
 #include <cstring>
 #include <new>
 #include <vector>
@@ -12,6 +13,132 @@
 #include "demod_host.h"
 
 using namespace fskd;
+
+extern "C" {
+
+// ---- receiver stages (frames_carry.hip) ----------------------------------------
+
+int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n_streams,
+                   demod_rx_sizes_t *out)
+{
+    if (!rxcfg || !out || validate_cfg(cfg) != DEMOD_OK) return DEMOD_BAD_ARG;
+    const demod_rx_cfg_t &x = *rxcfg;
+    const size_t S = n_streams, L = x.sync_len, N = x.frame_symbols, C = x.ring_windows;
+    // the segmented scan's refusals (the ring's windows are refused below)
+    const uint32_t R = frames_args(*cfg, 0, x.sync, L, x.max_errors, N, x.max_frames, false);
+    if (R == 0) return DEMOD_BAD_ARG;
+    // the check's (or the decode's and the coded check's): S, max_frames, the row shape
+    frame_shape s;
+    if (!stage_shape(*cfg, S, x.max_frames, L, N, (int)x.len_bytes, (int)x.crc, (int)x.fec, s))
+        return DEMOD_BAD_ARG;
+    if (C < 2 * (L + N) * R || C >= ((size_t)1 << 31) / S || S * C > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const size_t rows = S * x.max_frames;
+    out->max_len = s.max_len;
+    out->row_bytes = s.row_bytes;
+    out->ring_sym_bytes = S * C;
+    out->ring_mag_bytes = S * C * cfg->k * sizeof(float);
+    out->scan_work_bytes = demod_frames_segments_workspace_size(cfg, S, S * C);
+    out->decode_work_bytes = s.fec ? demod_fec_decode_workspace_size(cfg, S, x.max_frames, N, s.fec) : 0;
+    out->collect_work_bytes = demod_rx_collect_workspace_size(cfg, S);
+    out->frames_bytes = rows * sizeof(demod_rx_frame_t);
+    out->bodies_bytes = rows * s.max_len;
+    if (out->scan_work_bytes == 0 || (s.fec && out->decode_work_bytes == 0)) return DEMOD_BAD_ARG;
+    return DEMOD_OK;
+}
+
+int demod_rx_advance_async(demod_t *st, demod_rx_stream_state_t *d_state, const uint8_t *d_ring_sym_in,
+                           const float *d_ring_mag_in, const uint8_t *d_new_sym, const float *d_new_mag,
+                           size_t n_new_windows, const uint64_t *d_new_first,
+                           const uint32_t *d_new_count, size_t n_streams, size_t ring_windows,
+                           uint8_t *d_ring_sym_out, float *d_ring_mag_out, uint64_t *d_first,
+                           uint32_t *d_count, void *stream)
+{
+    if (!st || !d_state || !d_ring_sym_in || !d_ring_mag_in || !d_new_sym || !d_new_mag || !d_new_first ||
+        !d_new_count || !d_ring_sym_out || !d_ring_mag_out || !d_first || !d_count)
+        return DEMOD_BAD_ARG;
+    if (d_ring_sym_in == d_ring_sym_out || d_ring_mag_in == d_ring_mag_out) return DEMOD_BAD_ARG;
+    if (n_streams == 0 || n_streams > DEMOD_MAX_SEGMENTS || ring_windows == 0 || ring_windows > 0x7FFFFFFF ||
+        n_streams * ring_windows > 0x7FFFFFFF || n_new_windows > 0x7FFFFFFF)
+        return DEMOD_BAD_ARG;
+    if (!aligned8(d_state, d_new_first, d_first) ||
+        !aligned4(d_new_count, d_count, d_ring_mag_in, d_ring_mag_out, d_new_mag))
+        return DEMOD_BAD_ARG;
+    RxAdvanceParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.state = d_state;
+    p.ring_sym_in = d_ring_sym_in;
+    p.ring_mag_in = d_ring_mag_in;
+    p.new_sym = d_new_sym;
+    p.new_mag = d_new_mag;
+    p.new_first = reinterpret_cast<const unsigned long long *>(d_new_first);
+    p.new_count = d_new_count;
+    p.n_new = n_new_windows;
+    p.n_streams = (unsigned)n_streams;
+    p.ring = (unsigned)ring_windows;
+    p.k = (int)st->cfg.k;
+    p.ring_sym_out = d_ring_sym_out;
+    p.ring_mag_out = d_ring_mag_out;
+    p.seg_first = reinterpret_cast<unsigned long long *>(d_first);
+    p.seg_count = d_count;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_rx_advance(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+size_t demod_rx_collect_workspace_size(const demod_cfg_t *cfg, size_t n_streams)
+{
+    if (validate_cfg(cfg) != DEMOD_OK || n_streams == 0 || n_streams > DEMOD_MAX_SEGMENTS) return 0;
+    return rx_collect_work_bytes(n_streams);
+}
+
+int demod_rx_collect_async(demod_t *st, demod_rx_stream_state_t *d_state, const demod_frame_hit_t *d_hits,
+                           const demod_frames_result_t *d_results, const demod_frame_check_t *d_check,
+                           const uint32_t *d_kept, const uint8_t *d_body,
+                           const demod_frames_check_result_t *d_check_summary, size_t n_streams,
+                           size_t max_frames, size_t sync_len, size_t frame_symbols, int len_bytes,
+                           int crc, int fec, demod_rx_frame_t *d_frames, uint8_t *d_bodies,
+                           demod_rx_summary_t *d_summary, void *d_work, size_t work_bytes, void *stream)
+{
+    if (!st || !d_state || !d_hits || !d_results || !d_check || !d_kept || !d_check_summary || !d_frames ||
+        !d_summary || !d_work)
+        return DEMOD_BAD_ARG;
+    if (!aligned8(d_state, d_hits, d_results, d_check_summary, d_frames, d_summary, d_work) ||
+        !aligned4(d_check, d_kept))
+        return DEMOD_BAD_ARG;
+    frame_shape s;   // the shape the check saw: the same refusals, the same span
+    const uint32_t R = stage_shape(st->cfg, n_streams, max_frames, sync_len, frame_symbols, len_bytes, crc, fec, s);
+    if (R == 0) return DEMOD_BAD_ARG;
+    if (s.max_len && (!d_body || !d_bodies)) return DEMOD_BAD_ARG;
+    const size_t need = demod_rx_collect_workspace_size(&st->cfg, n_streams);
+    if (need == 0 || work_bytes < need) return DEMOD_BAD_ARG;
+    RxCollectParams p;
+    std::memset(&p, 0, sizeof(p));
+    fill_shape_fields(p, s, max_frames, R, sync_len);
+    p.n_streams = (unsigned)n_streams;
+    p.fec_depth = s.fec_depth;
+    p.state = d_state;
+    p.hits = d_hits;
+    p.res = d_results;
+    p.check = d_check;
+    p.kept = d_kept;
+    p.body = d_body;
+    p.chk_sum = d_check_summary;
+    p.frames = d_frames;
+    p.bodies = d_bodies;
+    p.summary = d_summary;
+    p.w_hold = static_cast<unsigned long long *>(d_work);
+    p.w_bytes = p.w_hold + n_streams;
+    p.w_cnt = reinterpret_cast<unsigned *>(p.w_bytes + n_streams);
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_rx_collect(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+}  // extern "C"
+
+// ---- the handle ----------------------------------------------------------------
 
 struct demod_rx {
     demod_cfg_t cfg;

@@ -25,18 +25,14 @@ static bool tx_shape(const demod_cfg_t *cfg, const demod_tx_cfg_t *x, size_t S, 
         if (x->sync[i] >= K) return false;
     for (uint32_t i = 0; i < x->idle_len; ++i)
         if (x->idle[i] >= K) return false;
-    if (x->len_bytes != 1 && x->len_bytes != 2) return false;
-    if (x->crc != DEMOD_CRC16_CCITT_FALSE && x->crc != DEMOD_CRC32_MPEG2) return false;
-    if (x->fec != 0 && !rs_mode_valid(x->fec)) return false;
-    if (rs_mode_conv(x->fec) && (K & (K - 1)) != 0) return false;
     const uint32_t most = x->len_bytes == 1 ? 255u : (uint32_t)DEMOD_MAX_FRAME_PAYLOAD;
     if (x->max_len > most) return false;
+    // A(max_len), or negative for an unknown len_bytes, crc or fec, or a coded mode with K no power of two
     const long long A = demod_tx_frame_symbol_count(x, K, x->max_len);
     if (A < 0) return false;
     const unsigned long long C = x->ring_symbols;
     if (C < (unsigned long long)A + x->gap) return false;
-    if (S == 0 || S > DEMOD_MAX_SEGMENTS || x->max_frames == 0) return false;
-    if ((unsigned long long)S * x->max_frames > 0x7FFFFFFFull || S * C > 0x7FFFFFFFull) return false;
+    if (!group_rows_ok(S, x->max_frames, false) || S * C > 0x7FFFFFFFull) return false;
     if (x->max_samples == 0 || x->max_samples % 8 != 0) return false;
     if ((unsigned long long)S * x->max_samples > 0x7FFFFFFFull) return false;
     if (x->amplitude < 0 || x->amplitude > 32767 || x->sigma < 0 || x->sigma > 32767) return false;
@@ -57,7 +53,7 @@ static bool tx_shape(const demod_cfg_t *cfg, const demod_tx_cfg_t *x, size_t S, 
     p.max_len = x->max_len;
     p.gap = x->gap;
     p.len_bytes = (int)x->len_bytes;
-    p.crc_bytes = x->crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4;
+    p.crc_bytes = frame_crc_bytes((int)x->crc);
     p.fec = (int)rs_mode_conv(x->fec);
     p.parity = (int)rs_parity(x->fec);
     if (p.parity) {
@@ -65,18 +61,7 @@ static bool tx_shape(const demod_cfg_t *cfg, const demod_tx_cfg_t *x, size_t S, 
         rs_generator((unsigned)p.parity, g);
         for (int i = 0; i < p.parity; ++i) p.rs_g8[i >> 3] |= (unsigned long long)g[i + 1] << ((i & 7) * 8);
     }
-    p.poly = p.crc_bytes == 2 ? 0x1021u << 16 : 0x04C11DB7u;
-    p.init = p.crc_bytes == 2 ? 0xFFFFu << 16 : 0xFFFFFFFFu;
-    // x^8, then its squares mod P, as the check passes them (demod_acquire.cpp frames_check_shape)
-    const int width = 8 * p.crc_bytes;
-    p.xpow8[0] = 1u << (32 - width + 8);
-    for (int j = 1; j < kCrcPowBits; ++j) {
-        const uint32_t a = p.xpow8[j - 1];
-        uint32_t r = 0, b = a;
-        for (int i = 0; i < width; ++i, b <<= 1)
-            r = (r << 1) ^ ((r >> 31) ? p.poly : 0u) ^ ((b >> 31) ? a : 0u);
-        p.xpow8[j] = r;
-    }
+    fill_crc_fields(p, p.crc_bytes);   // as the check passes them
     for (uint32_t t = 0; t < K; ++t)
         p.inc[t] = (uint32_t)((unsigned long long)std::llround(cfg->freqs[t] / cfg->fs * 4294967296.0) &
                               0xFFFFFFFFULL);
@@ -123,9 +108,7 @@ int demod_tx_encode_async(demod_t *st, const demod_tx_cfg_t *txcfg, demod_tx_str
     if (!st || !d_state || !d_ring || !d_records || !d_count || !d_place || (!d_bytes && n_bytes))
         return DEMOD_BAD_ARG;
     if (n_bytes > 0xFFFFFFFFull) return DEMOD_BAD_ARG;
-    if (((uintptr_t)d_state & 7) != 0 || ((uintptr_t)d_place & 7) != 0 || ((uintptr_t)d_records & 3) != 0 ||
-        ((uintptr_t)d_count & 3) != 0)
-        return DEMOD_BAD_ARG;
+    if (!aligned8(d_state, d_place) || !aligned4(d_records, d_count)) return DEMOD_BAD_ARG;
     TxParams p;
     std::memset(&p, 0, sizeof(p));
     if (!tx_shape(&st->cfg, txcfg, n_streams, p)) return DEMOD_BAD_ARG;
@@ -147,9 +130,7 @@ int demod_tx_modulate_async(demod_t *st, const demod_tx_cfg_t *txcfg, demod_tx_s
                             int16_t *d_pcm, void *d_work, size_t work_bytes, void *stream)
 {
     if (!st || !d_state || !d_ring || !d_count || !d_pcm || !d_work) return DEMOD_BAD_ARG;
-    if (((uintptr_t)d_pcm & 15) != 0 || ((uintptr_t)d_state & 7) != 0 || ((uintptr_t)d_count & 3) != 0 ||
-        ((uintptr_t)d_work & 3) != 0)
-        return DEMOD_BAD_ARG;
+    if (((uintptr_t)d_pcm & 15) != 0 || !aligned8(d_state) || !aligned4(d_count, d_work)) return DEMOD_BAD_ARG;
     TxParams p;
     std::memset(&p, 0, sizeof(p));
     if (!tx_shape(&st->cfg, txcfg, n_streams, p)) return DEMOD_BAD_ARG;

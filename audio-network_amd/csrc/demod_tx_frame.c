@@ -8,9 +8,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "../../include/demod.h"
-#include "fec_map.h"
-#include "rs_ops.h"
+#include "frame_shape.h"
 
 /* bits, or a negative code for what the format or K rules out */
 static int tx_format_bits(const demod_tx_cfg_t *x, uint32_t k)
@@ -18,7 +16,7 @@ static int tx_format_bits(const demod_tx_cfg_t *x, uint32_t k)
     if (!x || k < 2 || k > DEMOD_MAX_TONES) return DEMOD_BAD_ARG;
     if (x->sync_len < 1 || x->sync_len > DEMOD_MAX_SYNC) return DEMOD_BAD_ARG;
     if (x->len_bytes != 1 && x->len_bytes != 2) return DEMOD_BAD_ARG;
-    if (x->crc != DEMOD_CRC16_CCITT_FALSE && x->crc != DEMOD_CRC32_MPEG2) return DEMOD_BAD_ARG;
+    if (frame_crc_bytes((int)x->crc) == 0) return DEMOD_BAD_ARG;
     if (x->fec != 0 && !rs_mode_valid(x->fec)) return DEMOD_BAD_ARG;
     if (rs_mode_conv(x->fec) && (k & (k - 1)) != 0) return DEMOD_BAD_ARG;
     return demod_bits_per_symbol(k);

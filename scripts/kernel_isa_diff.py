@@ -37,7 +37,8 @@ import sys
 import tempfile
 
 UNITS = ["goertzel", "fold", "residue", "fft_quad", "rescue", "synth", "acquire", "acquire_segments",
-         "acquire_frames", "acquire_frames_segments", "frames_check", "frames_fec", "frame_gpu"]
+         "acquire_frames", "acquire_frames_segments", "frames_check", "frames_fec", "frames_rs", "frames_carry",
+         "frames_tx", "frame_gpu"]
 CSRC = os.path.join("audio-network_amd", "csrc")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
