@@ -35,6 +35,7 @@
 // same call. No floating-point atomics; every output byte is a function of the
 // inputs alone.
 #include "acquire_scan.h"
+#include "frame_rows.h"
 
 namespace fskd {
 

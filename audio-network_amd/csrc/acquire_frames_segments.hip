@@ -42,6 +42,9 @@
 // every word of d_work a launch reads was stored by an earlier launch of the
 // same call.
 #include "acquire_seg_scan.h"
+#include "frame_rows.h"
+
+static_assert(fskd::kSegWaves == fskd::kRowWaves, "the gathers are launched by frame_rows.h's arithmetic");
 
 namespace fskd {
 
@@ -235,12 +238,8 @@ hipError_t launch_frames_segments(const FrameSegParams &q, hipStream_t s)
         hipLaunchKernelGGL(frames_seg_emit_kernel, dim3(grid), dim3(kSegThreads), 0, s, q);
         if (q.frame_symbols > 0 && (q.payload || q.packed)) {
             const unsigned long long row = q.max_frames * (unsigned long long)q.frame_symbols;   // >= a packed row
-            const unsigned long long want = (row + kSegLanes - 1) / kSegLanes;
-            const unsigned long long most = 16384 / S ? 16384 / S : 1;
-            const unsigned wps = (unsigned)(want < most ? want : most);
-            const unsigned long long gblocks = ((unsigned long long)S * wps + kSegWaves - 1) / kSegWaves;
-            hipLaunchKernelGGL(frames_seg_gather_kernel, dim3((unsigned)gblocks), dim3(kSegThreads), 0, s,
-                               q, wps);
+            const unsigned wps = row_waves_per_group(S, (row + kSegLanes - 1) / kSegLanes);   // frame_rows.h
+            hipLaunchKernelGGL(frames_seg_gather_kernel, dim3(row_blocks(S, wps)), dim3(kSegThreads), 0, s, q, wps);
         }
     }
     return hipGetLastError();

@@ -17,14 +17,9 @@
 // it the same number of times). At the end the block adds its threads' sums
 // per phase in thread order and stores one partial per phase to part[block][R]
 // by plain stores.
-//
-// Also here, because acquire_seg_scan.h includes this file: what the frame scan
-// and the segmented frame scan share (frame_span, frame_packed_byte).
 #pragma once
 #include "../../include/demod.h"
 #include "demod_internal.h"
-#include "fec_map.h"
-#include "rs_ops.h"
 
 namespace fskd {
 
@@ -83,62 +78,6 @@ __device__ __forceinline__ void acq_stage_tile(const uint8_t *sym, long long W, 
         const long long w = base + kAcqTile + h;
         s_sym[kAcqTile + h] = w < W ? sym[w] : (uint8_t)0xFF;
     }
-}
-
-// the frame scans: a hit at w is complete when w + frame_span is below the
-// windows of its batch or segment, so that its word and payload fit. (The
-// fields by reference, as the two units' own copies read them: by value the
-// segmented scan kernel compiles to other machine code.)
-__device__ __forceinline__ long long frame_span(const int &sync_len, const long long &frame_symbols,
-                                                const int &phases)
-{
-    return ((long long)sync_len + frame_symbols - 1) * phases;
-}
-
-// byte b of a frame's packed row; src: the payload's first symbol, the next R
-// bytes on. MSB first, each symbol masked to `bits` bits (mask: the caller's
-// (1 << bits) - 1), pad bits 0 (demod_pack_symbols). One thread per byte, so no
-// two threads share one.
-__device__ __forceinline__ uint8_t frame_packed_byte(const uint8_t *src, unsigned long long R,
-                                                     unsigned long long N, unsigned bits, unsigned mask,
-                                                     unsigned long long b)
-{
-    unsigned q = 0;   // bits of the byte filled
-    unsigned long long j = b * 8 / bits;
-    unsigned used = (unsigned)(b * 8 - j * bits);   // bits of symbol j in the bytes before
-    unsigned byte = 0;
-    while (q < 8 && j < N) {
-        const unsigned v = src[j * R] & mask;
-        const unsigned left = bits - used, room = 8 - q;
-        const unsigned take = left < room ? left : room;
-        byte |= ((v >> (left - take)) & ((1u << take) - 1u)) << (room - take);
-        q += take;
-        used += take;
-        if (used == bits) {
-            used = 0;
-            ++j;
-        }
-    }
-    return (uint8_t)byte;
-}
-
-// the symbols a checked frame of `length` data bytes occupies behind its word
-// (include/demod.h "checked frames": S, its h + len + c bytes; with fec_depth
-// "coded frames": Sc, its coded bits on the air). The one copy of the span that
-// `covered` (frames_check.hip) and the receiver's `hold` (frames_carry.hip) use.
-// A mapped mode (fec_map.h: punctured, interleaved) has Sc of its Na(len) air bits.
-// With an outer code of `parity` bytes a codeword (rs_ops.h) the bytes are n'.
-__device__ __forceinline__ unsigned checked_frame_span(unsigned length, unsigned len_bytes, unsigned crc_bytes,
-                                                       unsigned bits, unsigned fec_depth, unsigned fec,
-                                                       unsigned parity)
-{
-    unsigned span = rs_frame_bytes(len_bytes + crc_bytes + length, parity) * 8;
-    if (fec_depth) {
-        const unsigned least = 8u * len_bytes + fec_depth;
-        const unsigned T = span + 6u > least ? span + 6u : least;
-        span = fec_mode_mapped(fec) ? fec_air_bits(fec, fec_kept_bits(fec, T)) : 2u * T;
-    }
-    return (span + bits - 1) / bits;
 }
 
 template <typename OnHit, typename TileDone>

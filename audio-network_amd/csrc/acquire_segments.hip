@@ -45,6 +45,9 @@
 // the slot s, S or the grid. No floating-point atomics. Every word of d_work a
 // launch reads was stored by an earlier launch of the same call.
 #include "acquire_seg_scan.h"
+#include "frame_rows.h"
+
+static_assert(fskd::kSegWaves == fskd::kRowWaves, "the gathers are launched by frame_rows.h's arithmetic");
 
 namespace fskd {
 
@@ -173,12 +176,8 @@ hipError_t launch_acquire_segments(const AcquireSegParams &p, hipStream_t s)
     hipLaunchKernelGGL(acquire_seg_final_kernel, dim3((S + kSegWaves - 1) / kSegWaves),
                        dim3(kSegThreads), 0, s, p);
     if (p.cap > 0) {
-        const unsigned long long want = (p.cap + kSegLanes - 1) / kSegLanes;
-        const unsigned long long most = 16384 / S ? 16384 / S : 1;
-        const unsigned wps = (unsigned)(want < most ? want : most);
-        const unsigned long long gblocks = ((unsigned long long)S * wps + kSegWaves - 1) / kSegWaves;
-        hipLaunchKernelGGL(acquire_seg_gather_kernel, dim3((unsigned)gblocks), dim3(kSegThreads), 0, s,
-                           p, wps);
+        const unsigned wps = row_waves_per_group(S, (p.cap + kSegLanes - 1) / kSegLanes);   // frame_rows.h
+        hipLaunchKernelGGL(acquire_seg_gather_kernel, dim3(row_blocks(S, wps)), dim3(kSegThreads), 0, s, p, wps);
     }
     return hipGetLastError();
 }

@@ -16,6 +16,16 @@ static __device__ __forceinline__ unsigned crc_xtime(unsigned r, unsigned poly)
     return (r << 1) ^ ((r >> 31) ? poly : 0u);
 }
 
+// The 256-entry byte table (crc_xtime eight times over t << 24) into s_tab by
+// a workgroup of 256 threads, one entry each; the caller's barrier follows.
+static __device__ __forceinline__ void crc_byte_table(unsigned *s_tab, unsigned poly)
+{
+    const int t = threadIdx.x;
+    unsigned r = (unsigned)t << 24;
+    for (int b = 0; b < 8; ++b) r = crc_xtime(r, poly);
+    s_tab[t] = r;
+}
+
 // a(x) b(x) mod P by Horner over b's WIDTH coefficients, highest first; no
 // branches. Unrolled by 8 only, and its caller's loop not at all: a wave runs
 // this code once, and straight-line code costs more to fetch than it saves.
@@ -33,7 +43,7 @@ static __device__ __forceinline__ unsigned crc_mul(unsigned a, unsigned b, unsig
 
 // The wave's CRC register over row[0 .. n): lane `lane` of 64 takes its
 // contiguous chunk of ceil(n / 64) bytes, lane 0 from init and the others from
-// 0. tab is the 256-entry byte table (crc_xtime eight times over t << 24),
+// 0. tab is the 256-entry byte table (crc_byte_table),
 // xpow8[j] = x^(8 2^j) mod P from the host. The same value in every lane.
 template <int WIDTH>
 static __device__ __forceinline__ unsigned crc_wave(const uint8_t *row, unsigned n, int lane, unsigned init,

@@ -28,19 +28,21 @@ static unsigned parity7(unsigned v)
     return v & 1u;
 }
 
-/* T(len) of the frame's n bytes, or with an outer code of P parity bytes its n' */
-static long long frame_steps(size_t len, int len_bytes, int crc, unsigned P)
+/* The span of a frame in a mode with the convolutional code (frame_shape.h), in symbols of `bits` bits, with
+ * its T and Nt; or the negative code of demod_checked_frame_size. */
+static long long coded_span(size_t len, int len_bytes, int crc, int bits, unsigned fec, unsigned *T, unsigned *Nt)
 {
-    long long n = demod_checked_frame_size(len, len_bytes, crc);
+    const long long n = demod_checked_frame_size(len, len_bytes, crc);
     if (n < 0) return n;
-    n = (long long)rs_frame_bytes((unsigned)n, P);
-    const long long body = 8 * n + 6, least = 8 * (long long)len_bytes + DEMOD_FEC_DEPTH;
-    return body > least ? body : least;
+    return (long long)frame_air_symbols((unsigned)len, (unsigned)len_bytes, (unsigned)frame_crc_bytes(crc),
+                                        (unsigned)bits, rs_mode_conv(fec), rs_parity(fec), T, Nt);
 }
 
 long long demod_coded_frame_steps(size_t len, int len_bytes, int crc)
 {
-    return frame_steps(len, len_bytes, crc, 0);
+    unsigned T, Nt;
+    const long long rc = coded_span(len, len_bytes, crc, 1, DEMOD_FEC_CONV_K7, &T, &Nt);
+    return rc < 0 ? rc : (long long)T;
 }
 
 /* a mode with the convolutional code: one of the six, with or without a parity flag */
@@ -56,22 +58,13 @@ long long demod_fec_air_index(int fec, size_t m)
     return a == FEC_MAP_NONE ? -1 : (long long)a;
 }
 
-/* Na(len): the frame's bits on the air, or a negative code */
-static long long fec_frame_air_bits(size_t len, int len_bytes, int crc, int fec)
-{
-    if (!conv_mode_valid(fec)) return DEMOD_BAD_ARG;
-    const unsigned conv = rs_mode_conv((unsigned)fec);
-    const long long T = frame_steps(len, len_bytes, crc, rs_parity((unsigned)fec));
-    if (T < 0) return T;
-    return (long long)fec_air_bits(conv, fec_kept_bits(conv, (unsigned)T));
-}
-
 long long demod_fec_frame_symbols(size_t len, int len_bytes, int crc, int bits, int fec)
 {
-    const long long Na = fec_frame_air_bits(len, len_bytes, crc, fec);
-    if (Na < 0) return Na;
-    if (bits < 1 || bits > 4) return DEMOD_BAD_ARG;
-    return (Na + bits - 1) / bits;
+    unsigned T, Nt;
+    if (!conv_mode_valid(fec)) return DEMOD_BAD_ARG;
+    const int ok = bits >= 1 && bits <= 4;   /* refused behind what the frame's size refuses */
+    const long long sp = coded_span(len, len_bytes, crc, ok ? bits : 1, (unsigned)fec, &T, &Nt);
+    return sp < 0 || ok ? sp : DEMOD_BAD_ARG;
 }
 
 long long demod_coded_frame_symbols(size_t len, int len_bytes, int crc, int bits)
@@ -82,11 +75,12 @@ long long demod_coded_frame_symbols(size_t len, int len_bytes, int crc, int bits
 int demod_fec_frame_encode(const uint8_t *data, size_t len, int len_bytes, int crc, int fec, uint8_t *out,
                            size_t cap)
 {
-    const long long Na = fec_frame_air_bits(len, len_bytes, crc, fec);
+    unsigned T, Nt;
+    if (!conv_mode_valid(fec)) return DEMOD_BAD_ARG;
+    const long long Na = coded_span(len, len_bytes, crc, 1, (unsigned)fec, &T, &Nt);   /* one bit a symbol: Na */
     if (Na < 0) return (int)Na;
     if ((!data && len) || !out) return DEMOD_BAD_ARG;
     const unsigned P = rs_parity((unsigned)fec), conv = rs_mode_conv((unsigned)fec);
-    const long long T = frame_steps(len, len_bytes, crc, P);
     const size_t need = (size_t)(Na + 7) / 8;
     if (need > cap) return DEMOD_BUFFER_TOO_SMALL;
     uint8_t info[2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 19 * RS_MAX_PARITY];   /* the longest n' */
@@ -96,7 +90,7 @@ int demod_fec_frame_encode(const uint8_t *data, size_t len, int len_bytes, int c
     n = (int)rs_frame_bytes((unsigned)n, P);
     memset(out, 0, need);
     unsigned reg = 0;
-    for (long long t = 0; t < T; ++t) {
+    for (long long t = 0; t < (long long)T; ++t) {
         const unsigned u = t < 8 * (long long)n ? (info[t >> 3] >> (7 - (t & 7))) & 1u : 0u;
         reg = ((reg << 1) | u) & 0x7Fu;
         for (unsigned v = 0; v < 2; ++v) {

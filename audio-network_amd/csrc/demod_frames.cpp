@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "demod_host.h"
+#include "frame_rows.h"
 
 using namespace fskd;
 
@@ -153,7 +154,7 @@ size_t demod_fec_decode_workspace_size(const demod_cfg_t *cfg, size_t n_groups, 
     if (validate_cfg(cfg) != DEMOD_OK || cfg->k < 2 || (cfg->k & (cfg->k - 1)) != 0) return 0;
     if (!group_rows_ok(n_groups, max_frames, false) || frame_symbols == 0 || frame_symbols > 0x7FFFFFFF) return 0;
     const size_t St = frame_row_steps(conv, frame_symbols * (size_t)demod_bits_per_symbol(cfg->k));
-    return n_groups * (size_t)fec_waves_per_group((unsigned)n_groups, (unsigned)max_frames) * St * 8;
+    return n_groups * (size_t)row_waves_per_group((unsigned)n_groups, (unsigned)max_frames) * St * 8;
 }
 
 int demod_frames_decode_async(demod_t *st, const demod_frame_hit_t *d_hits, const float *d_mags,

@@ -1,6 +1,6 @@
 // demod_internal.h — the contract between the C-ABI host layer and the
 // kernels: constants, parameter structs and launch declarations. No device
-// code (kernel_ops.h, rescue_ops.h, rescue_rows.h, lane_ops.h hold it).
+// code (kernel_ops.h, rescue_ops.h, rescue_rows.h, lane_ops.h, frame_rows.h hold it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -392,14 +392,8 @@ hipError_t launch_frames_kept_rows(const ::demod_frame_hit *hits, const ::demod_
                                    hipStream_t s);
 
 // frames_fec.hip: soft values and Viterbi decode of the rows a frame scan
-// listed (groups and rows as frames_check.hip). One wave per row; wave v of the
+// listed (groups and rows as frame_rows.h). One wave per row; wave v of the
 // launch keeps the survivor words of its current row in work[v steps ..).
-constexpr unsigned kFecMaxWaves = 16384;  // waves per call (or one per group), as the check's
-constexpr unsigned fec_waves_per_group(unsigned n_groups, unsigned max_frames)
-{
-    const unsigned most = kFecMaxWaves / n_groups ? kFecMaxWaves / n_groups : 1;
-    return max_frames < most ? max_frames : most;
-}
 struct FramesFecParams {
     const ::demod_frame_hit *hits;        // [n_groups][max_frames]
     const float *mag;                     // [n_windows][k]
@@ -426,7 +420,7 @@ struct FramesFecParams {
 hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s);
 
 // frames_rs.hip: the Reed-Solomon outer code over the rows a frame scan or the
-// decode above wrote, in place (groups and rows as frames_check.hip). One wave
+// decode above wrote, in place (groups and rows as frame_rows.h). One wave
 // per row, no workspace.
 struct FramesRsParams {
     uint8_t *rows;                        // [n_groups][max_frames][row_bytes]
@@ -492,12 +486,6 @@ hipError_t launch_rx_collect(const RxCollectParams &p, hipStream_t s);
 // "transmitter"). encode = plan + write, modulate = phase + samples + state.
 // The word and the idle pattern travel as 4-bit symbols, 16 to a 64-bit word:
 // a lookup is four selects and a shift, no table in memory.
-constexpr unsigned kTxMaxWaves = 16384;   // write: waves per call (or one per group), as the check's
-constexpr unsigned tx_waves_per_group(unsigned n_streams, unsigned max_frames)
-{
-    const unsigned most = kTxMaxWaves / n_streams ? kTxMaxWaves / n_streams : 1;
-    return max_frames < most ? max_frames : most;
-}
 struct TxParams {
     ::demod_tx_stream_state *state;       // [n_streams]
     uint8_t *ring;                        // [n_streams][ring_symbols]

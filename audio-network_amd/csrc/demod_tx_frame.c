@@ -31,9 +31,12 @@ long long demod_tx_frame_symbol_count(const demod_tx_cfg_t *x, uint32_t k, size_
     if (rs_mode_conv(x->fec)) {
         sp = demod_fec_frame_symbols(len, (int)x->len_bytes, (int)x->crc, bits, (int)x->fec);
     } else {
-        /* the frame's n bytes, or with an outer code its n' */
-        const long long n = demod_checked_frame_size(len, (int)x->len_bytes, (int)x->crc);
-        sp = n < 0 ? n : (8 * (long long)rs_frame_bytes((unsigned)n, rs_parity(x->fec)) + bits - 1) / bits;
+        /* the frame's n bytes, or with an outer code its n' (frame_shape.h) */
+        unsigned T, Nt;
+        sp = demod_checked_frame_size(len, (int)x->len_bytes, (int)x->crc);
+        if (sp >= 0)
+            sp = frame_air_symbols((unsigned)len, x->len_bytes, (unsigned)frame_crc_bytes((int)x->crc), (unsigned)bits,
+                                   0, rs_parity(x->fec), &T, &Nt);
     }
     return sp < 0 ? sp : (long long)x->sync_len + sp;
 }

@@ -1,7 +1,7 @@
 /*
  * fec_map.h — the one copy of the map between the trellis's coded-bit index
  * and the position on the air (include/demod.h "coded frames": punctured and
- * interleaved), shared by frames_fec.hip, frames_tx.hip, acquire_scan.h and
+ * interleaved), shared by frames_fec.hip, frames_tx.hip, frame_shape.h and
  * the host C (demod_fec.c). Plain integer code that compiles for both; only
  * constants are divided (the periods 2 and 3, the block of 256).
  *

@@ -1,8 +1,9 @@
 /*
  * frame_shape.h — the one copy of a frame row's shape (include/demod.h "checked frames", "coded frames",
- * "Reed-Solomon outer code"): what the `fec` mode, the CRC kind and len_bytes make of frame_symbols. Shared by
- * the host entry points of the stages over a scan's rows and the host C (demod_fec.c, demod_rs.c,
- * demod_tx_frame.c). Plain integer code that compiles for both.
+ * "Reed-Solomon outer code"): what the `fec` mode, the CRC kind and len_bytes make of frame_symbols, and a
+ * frame's span on the air. Shared by the host entry points of the stages over a scan's rows, the host C
+ * (demod_fec.c, demod_rs.c, demod_tx_frame.c) and the stages' kernels (frame_rows.h, frames_tx.hip). Plain
+ * integer code that compiles for all of them.
  *
  *  row    N symbols of `bits` bits are C = N bits air bits: B = ceil(C / 8) packed bytes, or with the
  *         convolutional code St trellis steps that decode to Bd = (St - 6) / 8 bytes
@@ -35,6 +36,25 @@ FRAME_SHAPE_FN unsigned long long frame_row_steps(unsigned conv, unsigned long l
 FRAME_SHAPE_FN long long frame_max_len(unsigned W, unsigned h, unsigned c, unsigned P)
 {
     return P ? rs_max_len(W, h, c, P) : (long long)W - (long long)(h + c);
+}
+
+/* A frame's span on the air, the one copy: the symbols of `bits` bits that a frame of len data bytes occupies
+ * behind its word. Its n' bytes' bits; with the convolutional code `conv` its T = max(8 n' + 6, 8 h +
+ * DEMOD_FEC_DEPTH) steps, *kept = Nt(T) code bits and Na air bits (T and Nt 0 without the code). Arithmetic on
+ * accepted values alone: len <= DEMOD_MAX_FRAME_PAYLOAD, h, c, bits and the mode valid; the callers refuse
+ * the rest. */
+FRAME_SHAPE_FN unsigned frame_air_symbols(unsigned len, unsigned h, unsigned c, unsigned bits, unsigned conv,
+                                          unsigned P, unsigned *steps, unsigned *kept)
+{
+    unsigned span = 8u * rs_frame_bytes(h + len + c, P);
+    *steps = *kept = 0;
+    if (conv) {
+        const unsigned least = 8u * h + DEMOD_FEC_DEPTH;
+        *steps = span + 6u > least ? span + 6u : least;
+        *kept = fec_kept_bits(conv, *steps);
+        span = fec_air_bits(conv, *kept);
+    }
+    return (span + bits - 1u) / bits;
 }
 
 struct frame_shape {

@@ -12,8 +12,8 @@
 // 32-bit words), no atomics; every output byte is a function of the inputs.
 //
 // advance, two launches whatever S and the counts are:
-//  copy    wps waves per stream (bounded as the segmented gather bounds its
-//          waves per segment). Output position j of stream s is Y[j + d]: the
+//  copy    wps waves per stream (frame_rows.h's walk, a wave per 64 elements).
+//          Output position j of stream s is Y[j + d]: the
 //          old ring's window keep' + j + d while that is below fill, else the
 //          packet's window first' + (j + d - kept). Wave c takes elements 64 c +
 //          lane, + 64 wps, .. of the slot's fill' K power words and then of its
@@ -37,13 +37,9 @@
 //          the ballot below the lane; its body offset the same with a wave scan
 //          of the lengths. The record is stored, then the wave copies the
 //          chunk's bodies one after the other, 64 consecutive bytes a step.
-#include "acquire_scan.h"
+#include "frame_rows.h"
 
 namespace fskd {
-
-constexpr int kRxLanes = 64;
-constexpr int kRxWaves = kAcqThreads / kRxLanes;
-constexpr unsigned kRxMaxWaves = 16384;   // the copy launch: waves per call (or one per stream)
 
 // Step 1 of one stream, from the state and the tables as they are stored.
 struct RxMove {
@@ -70,17 +66,17 @@ static __device__ __forceinline__ RxMove rx_move(const RxAdvanceParams &p, unsig
     return m;
 }
 
-__global__ __launch_bounds__(kAcqThreads) void rx_advance_copy_kernel(RxAdvanceParams p, unsigned wps)
+__global__ __launch_bounds__(kRowThreads) void rx_advance_copy_kernel(RxAdvanceParams p, unsigned wps)
 {
-    const int wave = threadIdx.x / kRxLanes, lane = threadIdx.x % kRxLanes;
-    const unsigned long long gw = (unsigned long long)blockIdx.x * kRxWaves + wave;
-    const unsigned long long s64 = gw / wps, c = gw % wps;
-    if (s64 >= p.n_streams) return;
-    const unsigned s = (unsigned)s64;
+    const int lane = threadIdx.x % kRowLanes;
+    const RowWave rw = row_wave(p.n_streams, wps);
+    if (!rw.live) return;
+    const unsigned s = rw.g;
+    const unsigned long long c = rw.c;
     const RxMove m = rx_move(p, s);
     const unsigned long long K = (unsigned long long)p.k;
     const unsigned long long slot = (unsigned long long)s * p.ring;
-    const unsigned long long step = (unsigned long long)wps * kRxLanes, e0 = c * kRxLanes + lane;
+    const unsigned long long step = (unsigned long long)wps * kRowLanes, e0 = c * kRowLanes + lane;
     // the powers as 32-bit words: moved, never computed with
     const unsigned *old_mag = reinterpret_cast<const unsigned *>(p.ring_mag_in) + (slot + m.keep) * K;
     const unsigned *new_mag = reinterpret_cast<const unsigned *>(p.new_mag) + m.first * K;
@@ -99,9 +95,9 @@ __global__ __launch_bounds__(kAcqThreads) void rx_advance_copy_kernel(RxAdvanceP
     }
 }
 
-__global__ __launch_bounds__(kAcqThreads) void rx_advance_state_kernel(RxAdvanceParams p)
+__global__ __launch_bounds__(kRowThreads) void rx_advance_state_kernel(RxAdvanceParams p)
 {
-    const unsigned s = blockIdx.x * kAcqThreads + threadIdx.x;
+    const unsigned s = blockIdx.x * kRowThreads + threadIdx.x;
     if (s >= p.n_streams) return;
     const RxMove m = rx_move(p, s);
     demod_rx_stream_state_t *st = p.state + s;
@@ -116,22 +112,14 @@ __global__ __launch_bounds__(kAcqThreads) void rx_advance_state_kernel(RxAdvance
 hipError_t launch_rx_advance(const RxAdvanceParams &p, hipStream_t s)
 {
     const unsigned S = p.n_streams;
-    const unsigned long long want = ((unsigned long long)p.ring * p.k + kRxLanes - 1) / kRxLanes;
-    const unsigned long long most = kRxMaxWaves / S ? kRxMaxWaves / S : 1;
-    const unsigned wps = (unsigned)(want < most ? want : most);
-    const unsigned long long blocks = ((unsigned long long)S * wps + kRxWaves - 1) / kRxWaves;
-    hipLaunchKernelGGL(rx_advance_copy_kernel, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wps);
-    hipLaunchKernelGGL(rx_advance_state_kernel, dim3((S + kAcqThreads - 1) / kAcqThreads), dim3(kAcqThreads), 0,
+    const unsigned wps = row_waves_per_group(S, ((unsigned long long)p.ring * p.k + kRowLanes - 1) / kRowLanes);
+    hipLaunchKernelGGL(rx_advance_copy_kernel, dim3(row_blocks(S, wps)), dim3(kRowThreads), 0, s, p, wps);
+    hipLaunchKernelGGL(rx_advance_state_kernel, dim3((S + kRowThreads - 1) / kRowThreads), dim3(kRowThreads), 0,
                        s, p);
     return hipGetLastError();
 }
 
 // ---- collect -------------------------------------------------------------------
-
-static __device__ __forceinline__ unsigned rx_rows(unsigned long long stored, unsigned max_frames)
-{
-    return stored < max_frames ? (unsigned)stored : max_frames;
-}
 
 // a row's data bytes as the record reports and the copy moves them
 static __device__ __forceinline__ unsigned rx_length(const RxCollectParams &p, size_t row)
@@ -149,19 +137,19 @@ static __device__ __forceinline__ bool rx_emitted(const RxCollectParams &p, size
     return i < p.max_frames && base + p.hits[row0 + i].window >= hold;
 }
 
-__global__ __launch_bounds__(kAcqThreads) void rx_collect_stream_kernel(RxCollectParams p)
+__global__ __launch_bounds__(kRowThreads) void rx_collect_stream_kernel(RxCollectParams p)
 {
-    const int wave = threadIdx.x / kRxLanes, lane = threadIdx.x % kRxLanes;
-    const unsigned s = blockIdx.x * kRxWaves + wave;
+    const int wave = threadIdx.x / kRowLanes, lane = threadIdx.x % kRowLanes;
+    const unsigned s = blockIdx.x * kRowWaves + wave;
     if (s >= p.n_streams) return;
     const size_t row0 = (size_t)s * p.max_frames;
     const demod_frames_result_t *res = p.res + s;
-    const unsigned nw = rx_rows(res->n_written, p.max_frames);
-    const unsigned nk = rx_rows(p.chk_sum[s].n_kept, p.max_frames);
+    const unsigned nw = rows_clamped(res->n_written, p.max_frames);
+    const unsigned nk = rows_clamped(p.chk_sum[s].n_kept, p.max_frames);
     const unsigned long long base = p.state[s].base, hold = p.state[s].hold;
     const unsigned long long R = (unsigned long long)p.phases, L = (unsigned long long)p.sync_len;
     unsigned long long reach = hold;   // max(hold, the largest end over the OK rows)
-    for (unsigned i = lane; i < nw; i += kRxLanes) {
+    for (unsigned i = lane; i < nw; i += kRowLanes) {
         if (p.check[row0 + i].status != DEMOD_CHECK_OK) continue;
         const unsigned S = checked_frame_span(rx_length(p, row0 + i), (unsigned)p.len_bytes,
                                               (unsigned)p.crc_bytes, (unsigned)p.bits, (unsigned)p.fec_depth, (unsigned)p.fec,
@@ -171,14 +159,14 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_stream_kernel(RxCollec
     }
     unsigned cnt = 0;
     unsigned long long bytes = 0;
-    for (unsigned r = lane; r < nk; r += kRxLanes) {
+    for (unsigned r = lane; r < nk; r += kRowLanes) {
         unsigned i;
         if (rx_emitted(p, row0, r, base, hold, i)) {
             ++cnt;
             bytes += rx_length(p, row0 + i);
         }
     }
-    for (int d = kRxLanes / 2; d > 0; d >>= 1) {
+    for (int d = kRowLanes / 2; d > 0; d >>= 1) {
         const unsigned long long y = __shfl_xor(reach, d);
         if (y > reach) reach = y;
         cnt += __shfl_xor(cnt, d);
@@ -202,12 +190,12 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_stream_kernel(RxCollec
     st->cut_hits += n_hits > n_written ? n_hits - n_written : 0ull;
 }
 
-__global__ __launch_bounds__(kAcqThreads) void rx_collect_prefix_kernel(RxCollectParams p)
+__global__ __launch_bounds__(kRowThreads) void rx_collect_prefix_kernel(RxCollectParams p)
 {
-    __shared__ unsigned s_cnt[kAcqThreads];
-    __shared__ unsigned long long s_bytes[kAcqThreads], s_checked[kAcqThreads], s_valid[kAcqThreads];
+    __shared__ unsigned s_cnt[kRowThreads];
+    __shared__ unsigned long long s_bytes[kRowThreads], s_checked[kRowThreads], s_valid[kRowThreads];
     const unsigned t = threadIdx.x, S = p.n_streams;
-    const unsigned chunk = (S + kAcqThreads - 1) / kAcqThreads;
+    const unsigned chunk = (S + kRowThreads - 1) / kRowThreads;
     const unsigned lo = t * chunk < S ? t * chunk : S;
     const unsigned hi = lo + chunk < S ? lo + chunk : S;
     unsigned cnt = 0;
@@ -215,8 +203,8 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_prefix_kernel(RxCollec
     for (unsigned s = lo; s < hi; ++s) {
         cnt += p.w_cnt[s];
         bytes += p.w_bytes[s];
-        checked += rx_rows(p.chk_sum[s].n_checked, p.max_frames);
-        valid += rx_rows(p.chk_sum[s].n_valid, p.max_frames);
+        checked += rows_clamped(p.chk_sum[s].n_checked, p.max_frames);
+        valid += rows_clamped(p.chk_sum[s].n_valid, p.max_frames);
     }
     s_cnt[t] = cnt;
     s_bytes[t] = bytes;
@@ -237,9 +225,9 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_prefix_kernel(RxCollec
         run += c;
         brun += b;
     }
-    if (t == kAcqThreads - 1) {   // the last thread's running sums are the totals
+    if (t == kRowThreads - 1) {   // the last thread's running sums are the totals
         unsigned long long nc = 0, nv = 0;
-        for (unsigned g = 0; g < kAcqThreads; ++g) {
+        for (unsigned g = 0; g < kRowThreads; ++g) {
             nc += s_checked[g];
             nv += s_valid[g];
         }
@@ -252,23 +240,23 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_prefix_kernel(RxCollec
     }
 }
 
-__global__ __launch_bounds__(kAcqThreads) void rx_collect_write_kernel(RxCollectParams p)
+__global__ __launch_bounds__(kRowThreads) void rx_collect_write_kernel(RxCollectParams p)
 {
-    const int wave = threadIdx.x / kRxLanes, lane = threadIdx.x % kRxLanes;
-    const unsigned s = blockIdx.x * kRxWaves + wave;
+    const int wave = threadIdx.x / kRowLanes, lane = threadIdx.x % kRowLanes;
+    const unsigned s = blockIdx.x * kRowWaves + wave;
     if (s >= p.n_streams) return;
     const size_t row0 = (size_t)s * p.max_frames;
-    const unsigned nk = rx_rows(p.chk_sum[s].n_kept, p.max_frames);
+    const unsigned nk = rows_clamped(p.chk_sum[s].n_kept, p.max_frames);
     const unsigned long long base = p.state[s].base, hold = p.w_hold[s];
     unsigned long long rank = p.w_cnt[s], off = p.w_bytes[s];
     const unsigned long long M = p.max_len;
-    for (unsigned r0 = 0; r0 < nk; r0 += kRxLanes) {   // the same for every lane of the wave
+    for (unsigned r0 = 0; r0 < nk; r0 += kRowLanes) {   // the same for every lane of the wave
         const unsigned r = r0 + lane;
         unsigned i = 0;
         const bool emit = r < nk && rx_emitted(p, row0, r, base, hold, i);
         const unsigned len = emit ? rx_length(p, row0 + i) : 0u;
         unsigned x = len;   // inclusive sum of the lengths over the lanes up to this one
-        for (int d = 1; d < kRxLanes; d <<= 1) {
+        for (int d = 1; d < kRowLanes; d <<= 1) {
             const unsigned y = __shfl_up(x, d);
             if (lane >= d) x += y;
         }
@@ -290,19 +278,19 @@ __global__ __launch_bounds__(kAcqThreads) void rx_collect_write_kernel(RxCollect
             const unsigned long long dst = __shfl(at, src);
             const unsigned n = __shfl(len, src);
             const uint8_t *from = p.body + (row0 + r0 + (unsigned)src) * M;
-            for (unsigned b = lane; b < n; b += kRxLanes) p.bodies[dst + b] = from[b];
+            for (unsigned b = lane; b < n; b += kRowLanes) p.bodies[dst + b] = from[b];
         }
         rank += (unsigned)__popcll(ballot);
-        off += __shfl(x, kRxLanes - 1);
+        off += __shfl(x, kRowLanes - 1);
     }
 }
 
 hipError_t launch_rx_collect(const RxCollectParams &p, hipStream_t s)
 {
-    const unsigned blocks = (p.n_streams + kRxWaves - 1) / kRxWaves;
-    hipLaunchKernelGGL(rx_collect_stream_kernel, dim3(blocks), dim3(kAcqThreads), 0, s, p);
-    hipLaunchKernelGGL(rx_collect_prefix_kernel, dim3(1), dim3(kAcqThreads), 0, s, p);
-    hipLaunchKernelGGL(rx_collect_write_kernel, dim3(blocks), dim3(kAcqThreads), 0, s, p);
+    const unsigned blocks = (p.n_streams + kRowWaves - 1) / kRowWaves;
+    hipLaunchKernelGGL(rx_collect_stream_kernel, dim3(blocks), dim3(kRowThreads), 0, s, p);
+    hipLaunchKernelGGL(rx_collect_prefix_kernel, dim3(1), dim3(kRowThreads), 0, s, p);
+    hipLaunchKernelGGL(rx_collect_write_kernel, dim3(blocks), dim3(kRowThreads), 0, s, p);
     return hipGetLastError();
 }
 

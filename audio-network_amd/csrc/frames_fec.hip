@@ -3,10 +3,9 @@
 // detector's per-tone powers, and their soft-decision Viterbi decode under the
 // constraint-length-7, rate-1/2 code 0171/0133, in order or punctured to 2/3 or
 // 3/4 and interleaved (fec_map.h: the trellis does not change, a soft value's
-// place on the air does). The 64 trellis states are one wave: lane = state. Groups and rows as frames_check.hip: group g owns rows
-// g max_frames + i, i < nw_g = min(res[g].n_written, max_frames), the count
-// read and clamped here; wave c of a group's wpg waves takes rows c, c + wpg, ..
-// One launch, no atomics; every output byte is a function of the inputs alone
+// place on the air does). The 64 trellis states are one wave: lane = state.
+// Groups, rows and the walk as frame_rows.h, one wave per row. One launch, no
+// atomics; every output byte is a function of the inputs alone
 // (demod_fec.c's demod_coded_frame_decode restates it on the host).
 //
 //  soft     64 values at a time, one per lane: trellis value m sits at air
@@ -33,13 +32,11 @@
 // The forward pass stops at t0 for the header and at T(len) for the row: the
 // outputs do not depend on later steps. A wave's loads of its slot follow its
 // own stores in program order behind a workgroup fence.
-#include "acquire_scan.h"
+#include "frame_rows.h"
 
 namespace fskd {
 
-constexpr int kFecLanes = 64;
-constexpr int kFecWaves = kAcqThreads / kFecLanes;
-constexpr unsigned kFecPass = kFecLanes / 2;   // steps of one pass: 64 soft values
+constexpr unsigned kFecPass = kRowLanes / 2;   // steps of one pass: 64 soft values
 
 // trellis soft value m of a row whose symbol 0 of the word sits at window bw.
 // MAPPED (fec_map.h): m is kept or not, then its code index, then its air
@@ -126,28 +123,23 @@ static __device__ __forceinline__ unsigned long long fec_trace(const unsigned lo
 }
 
 template <bool MAPPED>
-__global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecParams p, unsigned wpg)
+__global__ __launch_bounds__(kRowThreads) void frames_decode_kernel(FramesFecParams p, unsigned wpg)
 {
-    const int wave = threadIdx.x / kFecLanes, lane = threadIdx.x % kFecLanes;
-    const unsigned long long gw = (unsigned long long)blockIdx.x * kFecWaves + wave;
-    const unsigned long long g64 = gw / wpg;
-    if (g64 >= p.n_groups) return;
-    const unsigned g = (unsigned)g64, c0 = (unsigned)(gw % wpg);
-    unsigned nw;
-    {
-        const unsigned long long n = p.res[g].n_written;
-        nw = n < p.max_frames ? (unsigned)n : p.max_frames;
-    }
+    const int lane = threadIdx.x % kRowLanes;
+    const RowWave rw = row_wave(p.n_groups, wpg);
+    if (!rw.live) return;
+    const unsigned g = rw.g;
+    const unsigned nw = rows_clamped(p.res[g].n_written, p.max_frames);
     unsigned long long base = 0;
     if (p.first) base = p.first[g] < p.n_windows ? p.first[g] : p.n_windows;
-    unsigned long long *slot = p.work + (size_t)gw * p.steps;   // gw < n_groups wpg
+    unsigned long long *slot = p.work + (size_t)rw.gw * p.steps;   // gw < n_groups wpg
     FecLane c;
     c.sgn0 = (__popc((unsigned)lane & 0171u) & 1) ? -1 : 1;
     c.sgn1 = (__popc((unsigned)lane & 0133u) & 1) ? -1 : 1;
     c.at0 = (lane >> 1) * 4;
     c.at1 = ((lane >> 1) | 32) * 4;
     const unsigned h = (unsigned)p.len_bytes, t0 = 8u * h + DEMOD_FEC_DEPTH;   // t0 <= St
-    for (unsigned i = c0; i < nw; i += wpg) {   // the same for every lane of the wave
+    for (unsigned i = rw.c; i < nw; i += wpg) {   // the same for every lane of the wave
         const size_t r = (size_t)g * p.max_frames + i;
         const unsigned long long window = p.hits[r].window;
         const bool live = window < p.n_windows;   // else every value an erasure; no wrap below
@@ -157,7 +149,7 @@ __global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecPar
             fec_steps<MAPPED>(p, c, live, bw, t, t0 - t < kFecPass ? t0 - t : kFecPass, M, slot, lane);
         __threadfence_block();
         int mx = M;
-        for (int d = kFecLanes / 2; d > 0; d >>= 1) {
+        for (int d = kRowLanes / 2; d > 0; d >>= 1) {
             const int y = __shfl_xor(mx, d);
             if (y > mx) mx = y;
         }
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecPar
         demod_frame_decode_t out;
         out.length = len;
         if (len > p.max_len) {
-            if ((unsigned)lane < h) row[lane] = (uint8_t)(len >> (8u * (h - 1u - (unsigned)lane)));
+            row_length_store(row, h, len, lane);
             out.metric = 0;
             out.status = DEMOD_DECODE_BAD_LENGTH;
             out.steps = 0;
@@ -190,12 +182,11 @@ __global__ __launch_bounds__(kAcqThreads) void frames_decode_kernel(FramesFecPar
 
 hipError_t launch_frames_decode(const FramesFecParams &p, hipStream_t s)
 {
-    const unsigned wpg = fec_waves_per_group(p.n_groups, p.max_frames);
-    const unsigned long long blocks = ((unsigned long long)p.n_groups * wpg + kFecWaves - 1) / kFecWaves;
+    const unsigned wpg = row_waves_per_group(p.n_groups, p.max_frames), blocks = row_blocks(p.n_groups, wpg);
     if (fec_mode_mapped(p.fec))
-        hipLaunchKernelGGL(frames_decode_kernel<true>, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
+        hipLaunchKernelGGL(frames_decode_kernel<true>, dim3(blocks), dim3(kRowThreads), 0, s, p, wpg);
     else
-        hipLaunchKernelGGL(frames_decode_kernel<false>, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
+        hipLaunchKernelGGL(frames_decode_kernel<false>, dim3(blocks), dim3(kRowThreads), 0, s, p, wpg);
     return hipGetLastError();
 }
 

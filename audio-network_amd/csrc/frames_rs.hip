@@ -2,15 +2,13 @@
 // "Reed-Solomon outer code", DESIGN.md §4.9 "Reed-Solomon outer code"): a pass
 // over the rows a frame scan (packed rows) or the Viterbi decode (decoded rows)
 // wrote, which corrects up to t = P / 2 wrong bytes in each codeword of each
-// row, in place, before the check reads the rows. Groups and rows as
-// frames_check.hip: group g owns rows g max_frames + i, i < nw_g, the count
-// read and clamped here; every index below is bounded by the clamped count,
-// max_len and the row width alone. One launch, no workspace, no atomics, no
+// row, in place, before the check reads the rows. Groups, rows and the walk as
+// frame_rows.h; every index below is bounded by the clamped count, max_len and
+// the row width alone. One launch, no workspace, no atomics, no
 // floating point; every output byte is a function of the inputs alone, the
 // same as demod_rs_frame_decode's (demod_rs.c).
 //
-// One wave per row, wave c of a group's wpg waves taking rows c, c + wpg, ..
-// (wave-uniform). The row's n' bytes go into the wave's own LDS slice by
+// One wave per row. The row's n' bytes go into the wave's own LDS slice by
 // coalesced loads. Then, 64 / P codewords at a time (slot = lane / P, i = lane
 // % P):
 //
@@ -34,14 +32,11 @@
 //
 // A codeword is accepted under the same conditions as on the host: L <= t, L
 // roots among its positions, no zero denominator or value.
-#include "acquire_scan.h"
+#include "frame_rows.h"
 #include "rs_ops.h"
 
 namespace fskd {
 
-constexpr int kRsLanes = 64;
-constexpr int kRsWaves = kAcqThreads / kRsLanes;
-constexpr unsigned kRsMaxWaves = 16384;   // waves per call (or one per group), as the check's
 // n' at the payload limit is 4710 (h = 2, c = 4, P = 32, D = 19), rounded up to a multiple of 8
 constexpr unsigned kRsRowBytes = 4712;
 static_assert(2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 19 * 32 <= kRsRowBytes, "the longest protected frame");
@@ -55,13 +50,6 @@ struct RsWaveLds {
     uint8_t om[RS_MAX_T];
     uint8_t pos[RS_MAX_T];
 };
-
-// the wave's own LDS slice: no other wave touches it
-static __device__ __forceinline__ void rs_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 static __device__ __forceinline__ unsigned rs_uniform(unsigned v)
 {
@@ -120,12 +108,12 @@ static __device__ __forceinline__ int rs_correct(RsWaveLds &w, uint8_t *grow, un
         }
     }
     if (L > kT) return -1;
-    rs_wave_sync();   // the codeword before has read lam, om and pos
+    wave_sync();   // the codeword before has read lam, om and pos
     if (l <= kT) w.lam[l] = (uint8_t)C;
-    rs_wave_sync();
+    wave_sync();
     // the roots among the codeword's own positions: x has X = alpha^(N - 1 - x)
     unsigned found = 0;
-    for (unsigned x0 = 0; x0 < N; x0 += kRsLanes) {
+    for (unsigned x0 = 0; x0 < N; x0 += kRowLanes) {
         const unsigned x = x0 + l;
         bool root = false;
         if (x < N) {
@@ -146,7 +134,7 @@ static __device__ __forceinline__ int rs_correct(RsWaveLds &w, uint8_t *grow, un
         for (unsigned i = 0; i <= l; ++i) v ^= rs_tmul(w.exp, w.log, w.lam[i], w.syn[l - i]);
         w.om[l] = (uint8_t)v;
     }
-    rs_wave_sync();
+    wave_sync();
     unsigned val = 0, at = 0;
     bool bad = false;
     if (l < L) {
@@ -167,41 +155,27 @@ static __device__ __forceinline__ int rs_correct(RsWaveLds &w, uint8_t *grow, un
 }
 
 template <int P>
-__global__ __launch_bounds__(kAcqThreads) void frames_rs_kernel(FramesRsParams p, unsigned wpg)
+__global__ __launch_bounds__(kRowThreads) void frames_rs_kernel(FramesRsParams p, unsigned wpg)
 {
-    __shared__ RsWaveLds s_w[kRsWaves];
-    constexpr unsigned kSlots = kRsLanes / P;
-    const int wave = threadIdx.x / kRsLanes, lane = threadIdx.x % kRsLanes;
-    const unsigned long long gw = (unsigned long long)blockIdx.x * kRsWaves + wave;
-    const unsigned long long g64 = gw / wpg;
-    if (g64 >= p.n_groups) return;
-    const unsigned g = (unsigned)g64, c0 = (unsigned)(gw % wpg);
-    unsigned nw;
-    {
-        const unsigned long long nn = p.res[g].n_written;
-        nw = nn < p.max_frames ? (unsigned)nn : p.max_frames;
-    }
-    RsWaveLds &w = s_w[wave];
+    __shared__ RsWaveLds s_w[kRowWaves];
+    constexpr unsigned kSlots = kRowLanes / P;
+    const int wave = threadIdx.x / kRowLanes, lane = threadIdx.x % kRowLanes;
+    const RowWave rw = row_wave(p.n_groups, wpg);
+    if (!rw.live) return;
+    const unsigned g = rw.g;
+    const unsigned nw = rows_clamped(p.res[g].n_written, p.max_frames);
+    RsWaveLds &w = s_w[wave];   // the wave's own LDS slice: no other wave touches it
     const unsigned slot = (unsigned)lane / P, si = (unsigned)lane % P;
     // times alpha^si as a GF(2)-linear map: col[b] = alpha^(si + b)
-    unsigned col[8];
-    {
-        unsigned a = 1;
-        for (unsigned k = 0; k < si; ++k) a = rs_xtime(a);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            col[b] = a;
-            a = rs_xtime(a);
-        }
-    }
+    unsigned col[8], asi = 1;
+    for (unsigned k = 0; k < si; ++k) asi = rs_xtime(asi);
+    rs_times_cols(col, asi);
     const unsigned h = (unsigned)p.len_bytes;
     bool tables = false;
-    for (unsigned i = c0; i < nw; i += wpg) {   // the same for every lane of the wave
+    for (unsigned i = rw.c; i < nw; i += wpg) {   // the same for every lane of the wave
         const size_t r = (size_t)g * p.max_frames + i;
         uint8_t *grow = p.rows + r * p.row_bytes;
-        unsigned len = grow[0];
-        if (h == 2) len = (len << 8) | grow[1];
-        len = rs_uniform(len);
+        const unsigned len = row_length_load(grow, h);
         demod_frame_rs_t out;
         out.status = DEMOD_RS_BAD_LENGTH;
         out.codewords = out.corrected = out.failed = 0;
@@ -209,9 +183,9 @@ __global__ __launch_bounds__(kAcqThreads) void frames_rs_kernel(FramesRsParams p
         const unsigned D = rs_codewords(n, P), np = n + D * P;
         // len <= max_len gives n' <= row_bytes and <= kRsRowBytes (the host checked max_len)
         if (len <= p.max_len && np <= p.row_bytes && np <= kRsRowBytes) {
-            rs_wave_sync();   // the row before has been read
-            for (unsigned b = (unsigned)lane; b < np; b += kRsLanes) w.row[b] = grow[b];
-            rs_wave_sync();
+            wave_sync();   // the row before has been read
+            for (unsigned b = (unsigned)lane; b < np; b += kRowLanes) w.row[b] = grow[b];
+            wave_sync();
             unsigned corrected = 0, failed = 0;
             for (unsigned j0 = 0; j0 < D; j0 += kSlots) {
                 const unsigned j = j0 + slot;
@@ -241,9 +215,9 @@ __global__ __launch_bounds__(kAcqThreads) void frames_rs_kernel(FramesRsParams p
                 for (unsigned s = 0; s < kSlots; ++s) {
                     const unsigned long long mask = (P == 64 ? ~0ull : (1ull << P) - 1ull) << (s * P);
                     if (!(dirty & mask)) continue;
-                    rs_wave_sync();   // the codeword before has read syn
+                    wave_sync();   // the codeword before has read syn
                     if (slot == s) w.syn[si] = (uint8_t)syn;
-                    rs_wave_sync();
+                    wave_sync();
                     const unsigned js = j0 + s;
                     const int e = rs_correct<P>(w, grow, n, D, js, rs_message_bytes(n, D, js), lane);
                     if (e < 0) ++failed;
@@ -261,14 +235,11 @@ __global__ __launch_bounds__(kAcqThreads) void frames_rs_kernel(FramesRsParams p
 
 hipError_t launch_frames_rs(const FramesRsParams &p, hipStream_t s)
 {
-    const unsigned S = p.n_groups;
-    const unsigned most = kRsMaxWaves / S ? kRsMaxWaves / S : 1;
-    const unsigned wpg = p.max_frames < most ? p.max_frames : most;
-    const unsigned long long blocks = ((unsigned long long)S * wpg + kRsWaves - 1) / kRsWaves;
+    const unsigned wpg = row_waves_per_group(p.n_groups, p.max_frames), blocks = row_blocks(p.n_groups, wpg);
     if (p.parity == 16)
-        hipLaunchKernelGGL(frames_rs_kernel<16>, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
+        hipLaunchKernelGGL(frames_rs_kernel<16>, dim3(blocks), dim3(kRowThreads), 0, s, p, wpg);
     else
-        hipLaunchKernelGGL(frames_rs_kernel<32>, dim3((unsigned)blocks), dim3(kAcqThreads), 0, s, p, wpg);
+        hipLaunchKernelGGL(frames_rs_kernel<32>, dim3(blocks), dim3(kRowThreads), 0, s, p, wpg);
     return hipGetLastError();
 }
 

@@ -14,9 +14,9 @@
 //           + gap (0 for a length above max_len), the inclusive prefix e by a
 //           shuffle scan with a running carry, acceptance tail + e - head <= C,
 //           the places; then tail, accepted, refused.
-//  write    one wave per frame, wave c of a group's wpg waves taking frames c,
-//           c + wpg, .. (wave-uniform). len || data || CRC in the wave's LDS,
-//           the CRC by the check's lane-split scheme (crc_ops.h); with an outer
+//  write    one wave per frame (frame_rows.h's walk, a stream's records its
+//           rows). len || data || CRC in the wave's LDS, the CRC by the
+//           check's lane-split scheme (crc_ops.h); with an outer
 //           code (rs_ops.h) its parity behind them, 64 / P codewords at a time:
 //           lane (slot, i) holds byte i of the slot's parity register, a step
 //           takes the register's top byte and the neighbour's by shuffle, and
@@ -40,16 +40,12 @@
 //           pull that ends inside an idle symbol past the queue stores that
 //           symbol in the ring: it is queued now (tail' = head' + 1), and the
 //           next pull reads it there.
-#include "../../include/demod.h"
 #include "crc_ops.h"
-#include "fec_map.h"
-#include "rs_ops.h"
+#include "frame_rows.h"
 #include "synth_ops.h"
 
 namespace fskd {
 
-constexpr int kTxThreads = 256;
-constexpr int kTxWaves = kTxThreads / 64;
 constexpr int kTxPhaseRun = 4;        // phase: consecutive symbols a thread sums per step
 constexpr int kTxPhaseMaxWaves = 16;  // phase: waves a stream at most (one workgroup)
 // len || data || CRC || parity of the longest frame (19 codewords of 32 parity
@@ -95,27 +91,23 @@ static __device__ __forceinline__ TxState tx_load(const TxParams &p, unsigned s)
     return t;
 }
 
-// Sp(len): the payload symbols of a frame of len data bytes
-// (coded: Sc of the mode; kept: Nt(T), the frame's code bits, 0 without a code)
+// Sp(len): the payload symbols of a frame of len data bytes, frame_shape.h's
+// span (kept: Nt(T), the frame's code bits, 0 without a code)
 static __device__ __forceinline__ unsigned tx_payload_symbols(const TxParams &p, unsigned len, unsigned &kept)
 {
-    const unsigned nb = rs_frame_bytes((unsigned)p.len_bytes + len + (unsigned)p.crc_bytes, (unsigned)p.parity);
-    const unsigned bits = (unsigned)p.bits;
-    kept = 0;
-    if (!p.fec) return (8 * nb + bits - 1) / bits;
-    const unsigned body = 8 * nb + 6, least = 8 * (unsigned)p.len_bytes + DEMOD_FEC_DEPTH;
-    kept = fec_kept_bits((unsigned)p.fec, body > least ? body : least);
-    return (fec_air_bits((unsigned)p.fec, kept) + bits - 1) / bits;
+    unsigned T;
+    return frame_air_symbols(len, (unsigned)p.len_bytes, (unsigned)p.crc_bytes, (unsigned)p.bits, (unsigned)p.fec,
+                             (unsigned)p.parity, &T, &kept);
 }
 
-__global__ __launch_bounds__(kTxThreads) void tx_plan_kernel(TxParams p)
+__global__ __launch_bounds__(kRowThreads) void tx_plan_kernel(TxParams p)
 {
     const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    const unsigned long long s64 = (unsigned long long)blockIdx.x * kTxWaves + wave;
+    const unsigned long long s64 = (unsigned long long)blockIdx.x * kRowWaves + wave;
     if (s64 >= p.n_streams) return;
     const unsigned s = (unsigned)s64;
     const TxState t = tx_load(p, s);
-    const unsigned cnt = p.count[s] < p.max_frames ? p.count[s] : p.max_frames;
+    const unsigned cnt = rows_clamped(p.count[s], p.max_frames);
     const size_t row0 = (size_t)s * p.max_frames;
     const unsigned long long used = t.tail - t.head, C = p.ring_symbols;
     unsigned long long carry = 0, last_e = 0;
@@ -160,22 +152,17 @@ __global__ __launch_bounds__(kTxThreads) void tx_plan_kernel(TxParams p)
 }
 
 template <int WIDTH>
-__global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsigned wpg)
+__global__ __launch_bounds__(kRowThreads) void tx_write_kernel(TxParams p, unsigned wpg)
 {
     __shared__ unsigned s_tab[256];
-    __shared__ uint8_t s_frame[kTxWaves][kTxFrameBytes];
-    const int t = threadIdx.x, wave = t / 64, lane = t % 64;
-    {
-        unsigned r = (unsigned)t << 24;
-        for (int b = 0; b < 8; ++b) r = crc_xtime(r, p.poly);
-        s_tab[t] = r;
-    }
+    __shared__ uint8_t s_frame[kRowWaves][kTxFrameBytes];
+    const int wave = threadIdx.x / kRowLanes, lane = threadIdx.x % kRowLanes;
+    crc_byte_table(s_tab, p.poly);
     __syncthreads();
-    const unsigned long long gw = (unsigned long long)blockIdx.x * kTxWaves + wave;
-    const unsigned long long g64 = gw / wpg;
-    if (g64 >= p.n_streams) return;
-    const unsigned g = (unsigned)g64, c = (unsigned)(gw % wpg);
-    const unsigned cnt = p.count[g] < p.max_frames ? p.count[g] : p.max_frames;
+    const RowWave rw = row_wave(p.n_streams, wpg);
+    if (!rw.live) return;
+    const unsigned g = rw.g;
+    const unsigned cnt = rows_clamped(p.count[g], p.max_frames);
     const unsigned h = (unsigned)p.len_bytes, cb = (unsigned)p.crc_bytes, bits = (unsigned)p.bits;
     const unsigned C = p.ring_symbols, L = p.sync_len;
     uint8_t *buf = s_frame[wave];
@@ -190,37 +177,25 @@ __global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsign
         if ((si >> 3) == 1) w = p.rs_g8[1];
         if ((si >> 3) == 2) w = p.rs_g8[2];
         if ((si >> 3) == 3) w = p.rs_g8[3];
-        unsigned a = (unsigned)(w >> ((si & 7u) * 8u)) & 0xFFu;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            col[b] = a;
-            a = rs_xtime(a);
-        }
+        rs_times_cols(col, (unsigned)(w >> ((si & 7u) * 8u)) & 0xFFu);
     }
-    for (unsigned i = c; i < cnt; i += wpg) {   // the same for every lane of the wave
+    for (unsigned i = rw.c; i < cnt; i += wpg) {   // the same for every lane of the wave
         const size_t r = (size_t)g * p.max_frames + i;
         const demod_tx_place_t pl = p.place[r];   // plan's, of this call
         if (pl.status != DEMOD_TX_OK) continue;
         const unsigned len = p.records[r].length < p.max_len ? p.records[r].length : p.max_len;
         const unsigned lenc = len < p.n_bytes ? len : p.n_bytes;
         const unsigned off = p.records[r].body < p.n_bytes - lenc ? p.records[r].body : p.n_bytes - lenc;
-        // the wave's own LDS row: no other wave touches it
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-            if (h == 2) buf[0] = (uint8_t)(len >> 8);
-            buf[h - 1] = (uint8_t)len;
-        }
+        wave_sync();   // the wave's own LDS row: the frame before has been read
+        row_length_store(buf, h, len, lane);
         for (unsigned b = (unsigned)lane; b < len; b += 64)
             buf[h + b] = b < lenc ? p.bytes[off + b] : (uint8_t)0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_sync();
         const unsigned n = h + len;
         unsigned nb = n + cb;
         const unsigned crc = crc_wave<WIDTH>(buf, n, lane, p.init, p.poly, p.xpow8, s_tab) >> (32 - WIDTH);
         if (lane < (int)cb) buf[n + lane] = (uint8_t)(crc >> (8 * (cb - 1 - (unsigned)lane)));
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_sync();
         if (P) {
             const unsigned n0 = nb, D = rs_codewords(n0, P);
             for (unsigned j0 = 0; j0 < D; j0 += 64u / P) {   // the same for every lane of the wave
@@ -245,8 +220,7 @@ __global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsign
                 if (have) buf[n0 + si * D + j] = (uint8_t)par;   // parity byte si D + j
             }
             nb = n0 + D * P;   // n' <= kTxFrameBytes: len <= max_len <= DEMOD_MAX_FRAME_PAYLOAD
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            wave_sync();
         }
         unsigned kept;
         const unsigned A = L + tx_payload_symbols(p, len, kept);
@@ -291,13 +265,12 @@ __global__ __launch_bounds__(kTxThreads) void tx_write_kernel(TxParams p, unsign
 hipError_t launch_tx_encode(const TxParams &p, hipStream_t s)
 {
     const unsigned S = p.n_streams;
-    hipLaunchKernelGGL(tx_plan_kernel, dim3((S + kTxWaves - 1) / kTxWaves), dim3(kTxThreads), 0, s, p);
-    const unsigned wpg = tx_waves_per_group(S, p.max_frames);
-    const unsigned long long blocks = ((unsigned long long)S * wpg + kTxWaves - 1) / kTxWaves;
+    hipLaunchKernelGGL(tx_plan_kernel, dim3((S + kRowWaves - 1) / kRowWaves), dim3(kRowThreads), 0, s, p);
+    const unsigned wpg = row_waves_per_group(S, p.max_frames), blocks = row_blocks(S, wpg);
     if (p.crc_bytes == 2)
-        hipLaunchKernelGGL(tx_write_kernel<16>, dim3((unsigned)blocks), dim3(kTxThreads), 0, s, p, wpg);
+        hipLaunchKernelGGL(tx_write_kernel<16>, dim3(blocks), dim3(kRowThreads), 0, s, p, wpg);
     else
-        hipLaunchKernelGGL(tx_write_kernel<32>, dim3((unsigned)blocks), dim3(kTxThreads), 0, s, p, wpg);
+        hipLaunchKernelGGL(tx_write_kernel<32>, dim3(blocks), dim3(kRowThreads), 0, s, p, wpg);
     return hipGetLastError();
 }
 
@@ -376,10 +349,10 @@ __global__ __launch_bounds__(64 * kTxPhaseMaxWaves) void tx_phase_kernel(TxParam
     }
 }
 
-__global__ __launch_bounds__(kTxThreads) void tx_samples_kernel(TxParams p, unsigned bps)
+__global__ __launch_bounds__(kRowThreads) void tx_samples_kernel(TxParams p, unsigned bps)
 {
     const unsigned s = blockIdx.x / bps;
-    const unsigned x0 = ((blockIdx.x - s * bps) * kTxThreads + threadIdx.x) * 8u;
+    const unsigned x0 = ((blockIdx.x - s * bps) * kRowThreads + threadIdx.x) * 8u;
     const unsigned m = tx_samples(p, s);
     if (x0 >= m) return;
     const TxState t = tx_load(p, s);
@@ -427,9 +400,9 @@ __global__ __launch_bounds__(kTxThreads) void tx_samples_kernel(TxParams p, unsi
     }
 }
 
-__global__ __launch_bounds__(kTxThreads) void tx_state_kernel(TxParams p)
+__global__ __launch_bounds__(kRowThreads) void tx_state_kernel(TxParams p)
 {
-    const unsigned long long s64 = (unsigned long long)blockIdx.x * kTxThreads + threadIdx.x;
+    const unsigned long long s64 = (unsigned long long)blockIdx.x * kRowThreads + threadIdx.x;
     if (s64 >= p.n_streams) return;
     const unsigned s = (unsigned)s64;
     const TxState t = tx_load(p, s);
@@ -457,9 +430,9 @@ hipError_t launch_tx_modulate(const TxParams &p, hipStream_t s)
     const unsigned per_wave = 64 * kTxPhaseRun, want = (p.work_stride - 1 + per_wave - 1) / per_wave;
     const unsigned waves = want < (unsigned)kTxPhaseMaxWaves ? (want ? want : 1u) : (unsigned)kTxPhaseMaxWaves;
     hipLaunchKernelGGL(tx_phase_kernel, dim3(S), dim3(64 * waves), 0, s, p);
-    const unsigned bps = (p.stride / 8 + kTxThreads - 1) / kTxThreads;   // S bps <= 2^31 / 2048 + S
-    hipLaunchKernelGGL(tx_samples_kernel, dim3(S * bps), dim3(kTxThreads), 0, s, p, bps);
-    hipLaunchKernelGGL(tx_state_kernel, dim3((S + kTxThreads - 1) / kTxThreads), dim3(kTxThreads), 0, s, p);
+    const unsigned bps = (p.stride / 8 + kRowThreads - 1) / kRowThreads;   // S bps <= 2^31 / 2048 + S
+    hipLaunchKernelGGL(tx_samples_kernel, dim3(S * bps), dim3(kRowThreads), 0, s, p, bps);
+    hipLaunchKernelGGL(tx_state_kernel, dim3((S + kRowThreads - 1) / kRowThreads), dim3(kRowThreads), 0, s, p);
     return hipGetLastError();
 }
 

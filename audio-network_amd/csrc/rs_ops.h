@@ -83,6 +83,19 @@ RS_OPS_FN unsigned rs_tscale(const uint8_t *exp, const uint8_t *log, unsigned a,
     return a ? exp[(unsigned)log[a] + z] : 0u;
 }
 
+#ifdef __HIPCC__
+/* times a as a GF(2)-linear map held in eight registers: col[b] = a alpha^b, so that a f is the XOR of the
+ * col[b] with bit b of f set (device code: the syndromes of frames_rs.hip, the parity of frames_tx.hip) */
+static __device__ __forceinline__ void rs_times_cols(unsigned (&col)[8], unsigned a)
+{
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        col[b] = a;
+        a = rs_xtime(a);
+    }
+}
+#endif
+
 /* ---- the layout ------------------------------------------------------------ */
 
 /* D: the codewords of a frame of n >= 1 bytes */

@@ -19,7 +19,9 @@ multisets of hashes are compared per unit. Exit status 0: equal everywhere.
 
 For every function that is not identical and has a namesake on the other side,
 a second line says whether the normalised lines are equal as a multiset
-("reordered": the same instructions in another order), the line count before
+("reordered": the same instructions in another order) or, failing that, whether
+the mnemonics, the first token of each normalised line, are ("same
+instructions, other registers or order"; else "changed"), the line count before
 and after, and the kernel descriptor's register, LDS and scratch fields.
 
 A refactor that renames or drops template parameters changes every mangled
@@ -101,6 +103,11 @@ def descriptor(lines):
     return "/".join(got.get(key, "-") for key in DESCRIPTOR)
 
 
+def mnemonics(lines):
+    """The multiset of the first tokens of a function's normalised lines."""
+    return collections.Counter(line.split()[0] for line in lines)
+
+
 def materialise(arg, stack):
     """Directory for `arg`: (path, is_assembly)."""
     if os.path.isdir(os.path.join(arg, CSRC)):
@@ -161,7 +168,12 @@ def main():
             for name in sorted(set(fa) & set(fb)):
                 (ha, la), (hb, lb) = fa[name], fb[name]
                 if ha != hb:
-                    kind = "reordered" if collections.Counter(la) == collections.Counter(lb) else "changed"
+                    if collections.Counter(la) == collections.Counter(lb):
+                        kind = "reordered"
+                    elif mnemonics(la) == mnemonics(lb):
+                        kind = "same instructions, other registers or order"
+                    else:
+                        kind = "changed"
                     print(f"  {kind}: {name}: lines {len(la)} -> {len(lb)}, "
                           f"vgpr/sgpr/lds/scratch {descriptor(la)} -> {descriptor(lb)}")
         print("machine code: " + ("DIFFERENT" if differ else "identical"))

@@ -1,23 +1,33 @@
 /*
- * frame_shape_test.c — csrc/frame_shape.h in a program of its own, built with
- * -fsanitize=address,undefined by tests/test_frame_shape_cpu.py; it links
- * nothing from the library. The header's closed forms are held to counts
- * written here from the definitions (include/demod.h):
+ * frame_shape_test.c — csrc/frame_shape.h and the launch arithmetic of
+ * csrc/frame_rows.h in a program of its own, built with
+ * -fsanitize=address,undefined by tests/test_frame_shape_cpu.py together with
+ * the library's host C files (no device code, no shared library). The
+ * headers' closed forms are held to counts written here from the definitions
+ * (include/demod.h):
  *
  *   St       the greatest T with Nt(T) <= Cu, Nt counted step by step from the
  *            puncturing pattern, Cu whole interleaver blocks with the flag
  *   max_len  the greatest len with n'(h + len + c) <= W, n' counted codeword
  *            by codeword
+ *   span     the symbols of a frame on the air: its n' bytes' bits, or T =
+ *            max(8 n' + 6, 8 h + DEMOD_FEC_DEPTH) steps, Nt(T) kept bits, whole
+ *            interleaver blocks with the flag
+ *   wpg      min(want, max(16384 / n_groups, 1)) waves a group, and the
+ *            workgroups of four waves that hold them
  *
- * Both are monotone in N, so a sweep of N upward advances them step by step.
- * Every N from 0 to eight past the first one refused for a max_len beyond
- * DEMOD_MAX_FRAME_PAYLOAD, for fec 0 and the 20 modes, bits 1 .. 4, h 1 and 2
- * and both CRC kinds; then the refusals of what is no shape at all.
+ * St and max_len are monotone in N, so a sweep of N upward advances them step
+ * by step. Every N from 0 to eight past the first one refused for a max_len
+ * beyond DEMOD_MAX_FRAME_PAYLOAD, for fec 0 and the 20 modes, bits 1 .. 4, h 1
+ * and 2 and both CRC kinds; then the refusals of what is no shape at all. The
+ * span at every len from 0 to DEMOD_MAX_FRAME_PAYLOAD in the same modes, also
+ * against the public functions that are expressed through it.
  */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "../../audio-network_amd/csrc/frame_rows.h"
 #include "../../audio-network_amd/csrc/frame_shape.h"
 
 #define CHECK(c)                                                              \
@@ -99,6 +109,67 @@ static unsigned long sweep(int fec, int bits, int h, int crc)
     }
 }
 
+/* the span of every len in one (mode, bits, h, crc): returns the calls compared */
+static unsigned long span_sweep(int fec, int bits, int h, int crc)
+{
+    const int conv = fec & 0xFF, P = fec & DEMOD_FEC_RS16 ? 16 : fec & DEMOD_FEC_RS32 ? 32 : 0;
+    const unsigned long c = crc == DEMOD_CRC16_CCITT_FALSE ? 2 : 4;
+    unsigned long calls = 0, Tc = 0, NtTc = 0;   /* Nt counted step by step: T does not fall as len grows */
+    demod_tx_cfg_t x = {.sync_len = 5, .len_bytes = (uint32_t)h, .crc = (uint32_t)crc, .fec = (uint32_t)fec,
+                        .max_len = DEMOD_MAX_FRAME_PAYLOAD};
+    g_fec = fec, g_bits = bits, g_h = h, g_crc = crc;
+    for (size_t len = 0; len <= DEMOD_MAX_FRAME_PAYLOAD; ++len) {
+        g_N = len;
+        const unsigned long np = protected_bytes((unsigned long)h + len + c, (unsigned)P);
+        unsigned long T = 0, Nt = 0, air = 8 * np;
+        if (conv) {
+            T = 8 * np + 6 > 8 * (unsigned long)h + DEMOD_FEC_DEPTH ? 8 * np + 6 : 8 * (unsigned long)h + DEMOD_FEC_DEPTH;
+            while (Tc < T) NtTc += kept_in_step(conv, Tc++);
+            CHECK(Tc == T);
+            Nt = NtTc;
+            air = conv & DEMOD_FEC_INTERLEAVE ? (Nt + DEMOD_FEC_IL_ROWS * DEMOD_FEC_IL_COLS - 1) / 256 * 256 : Nt;
+            if (!(conv & (DEMOD_FEC_RATE_2_3 | DEMOD_FEC_RATE_3_4 | DEMOD_FEC_INTERLEAVE)))   /* the unmapped mode */
+                CHECK(2 * T == fec_air_bits((unsigned)conv, fec_kept_bits((unsigned)conv, (unsigned)T)));
+        }
+        const unsigned long want = (air + (unsigned long)bits - 1) / (unsigned long)bits;
+        unsigned steps = 77, kept = 77;
+        CHECK(frame_air_symbols((unsigned)len, (unsigned)h, (unsigned)c, (unsigned)bits, (unsigned)conv, (unsigned)P,
+                                &steps, &kept) == want);
+        CHECK(steps == T && kept == Nt);
+        ++calls;
+        /* the public functions: they refuse a len that h bytes cannot say, the arithmetic does not */
+        const int fits = len <= (h == 1 ? 0xFFu : 0xFFFFu);
+        const long long n = demod_checked_frame_size(len, h, crc);
+        CHECK(n == (fits ? (long long)((unsigned long)h + len + c) : DEMOD_FRAME_TOO_LARGE));
+        if (fec == DEMOD_FEC_CONV_K7 && bits == 1)
+            CHECK(demod_coded_frame_steps(len, h, crc) == (fits ? (long long)T : DEMOD_FRAME_TOO_LARGE));
+        if (conv)
+            CHECK(demod_fec_frame_symbols(len, h, crc, bits, fec) == (fits ? (long long)want : DEMOD_FRAME_TOO_LARGE));
+        /* K = 2^bits tones; fec 0, the plain mode, runs the uncoded branch as the parity-only modes do */
+        CHECK(demod_tx_frame_symbol_count(&x, 1u << bits, len) == (fits ? (long long)(5 + want) : DEMOD_FRAME_TOO_LARGE));
+        calls += 3 + (conv != 0);
+    }
+    return calls;
+}
+
+/* row_waves_per_group and row_blocks against include/demod.h's formula */
+static void launches(void)
+{
+    static const unsigned groups[] = {1, 2, 4096, 5461, 8193, 16383, 16384, 16385, 65536};
+    static const unsigned long long wants[] = {1, 2, 3, 4, 5, 16384, 16385, 0x7FFFFFFF};
+    g_fec = g_bits = g_h = g_crc = 0;
+    for (size_t i = 0; i < sizeof(groups) / sizeof(groups[0]); ++i)
+        for (size_t j = 0; j < sizeof(wants) / sizeof(wants[0]); ++j) {
+            const unsigned long long S = groups[i], most = 16384 / S > 1 ? 16384 / S : 1;
+            const unsigned long long wpg = wants[j] < most ? wants[j] : most;
+            g_N = (size_t)S;
+            CHECK(row_waves_per_group(groups[i], wants[j]) == wpg);
+            CHECK(row_blocks(groups[i], (unsigned)wpg) == (S * wpg + 3) / 4);
+            CHECK(S * wpg <= (S > 16384 ? S : 16384) && wpg >= 1);
+        }
+    CHECK(kRowThreads == 256 && kRowLanes == 64 && kRowWaves == 4 && kRowMaxWaves == 16384);
+}
+
 static void refusals(void)
 {
     static const int bad[] = {2,     0x10,  0x20,  0x30,  0x31,  0x81,  0x41 | 0x30, 0x300,
@@ -143,7 +214,7 @@ int main(void)
                                 DEMOD_FEC_CONV_K7 | DEMOD_FEC_RATE_2_3 | DEMOD_FEC_INTERLEAVE,
                                 DEMOD_FEC_CONV_K7 | DEMOD_FEC_RATE_3_4 | DEMOD_FEC_INTERLEAVE};
     static const int flags[] = {0, DEMOD_FEC_RS16, DEMOD_FEC_RS32};
-    unsigned long shapes = 0, combos = 0;
+    unsigned long shapes = 0, combos = 0, spans = 0;
     for (size_t m = 0; m < sizeof(convs) / sizeof(convs[0]); ++m)
         for (size_t f = 0; f < sizeof(flags) / sizeof(flags[0]); ++f) {
             const int fec = convs[m] | flags[f];
@@ -151,10 +222,13 @@ int main(void)
             CHECK(fec == 0 || rs_mode_valid((unsigned)fec));
             for (int bits = 1; bits <= 4; ++bits)
                 for (int h = 1; h <= 2; ++h)
-                    for (int crc = DEMOD_CRC16_CCITT_FALSE; crc <= DEMOD_CRC32_MPEG2; ++crc, ++combos)
+                    for (int crc = DEMOD_CRC16_CCITT_FALSE; crc <= DEMOD_CRC32_MPEG2; ++crc, ++combos) {
                         shapes += sweep(fec, bits, h, crc);
+                        spans += span_sweep(fec, bits, h, crc);
+                    }
         }
     refusals();
-    printf("frame_shape_test OK: %lu combinations, %lu shapes\n", combos, shapes);
+    launches();
+    printf("frame_shape_test OK: %lu combinations, %lu shapes, %lu span calls\n", combos, shapes, spans);
     return 0;
 }

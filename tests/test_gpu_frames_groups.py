@@ -1,9 +1,11 @@
 """The frame check (frames_check.hip) and the soft-decision decode
 (frames_fec.hip) at every group count a segmented scan can hand them, up to
 DEMOD_MAX_SEGMENTS, against tests/frames_check_ref.py, tests/frames_fec_ref.py
-and tests/frames_segments_ref.py.
+and tests/frames_segments_ref.py; and the other launches that walk their rows
+the same way (the outer code's stage, the transmitter's write, the receiver's
+copy) across the same cap, against the host references of their own tests.
 
-Both stages size their launch from a cap of 16384 waves a call: with most =
+The stages size their launch from a cap of 16384 waves a call: with most =
 16384 / S (at least 1) a group gets wpg = min(max_frames, most) waves (the
 body kernel min(ceil(max_frames max_len / 64), most)). The cases here reach
 what the neighbouring files do not: most below max_frames, most = 1 and the
@@ -37,15 +39,21 @@ import frames_fec_ref as X
 import frames_ref as F
 import frames_segments_ref as FS
 import guards as G
+import rs_ref as RS
+import rx_ref as RX
 import test_gpu_fec_modes as TM
 import test_gpu_frames_check as TC
 import test_gpu_frames_fec as TF
 import test_gpu_frames_segments as TS
+import test_gpu_rs as TR
+import test_gpu_rx as TX
+import test_gpu_tx as TT
+import tx_ref as T
 from test_gpu_frames import result_bytes
 
 pytestmark = pytest.mark.gpu
 
-MAX_WAVES = 16384            # kChkMaxWaves, kFecMaxWaves
+MAX_WAVES = 16384            # kRowMaxWaves (csrc/frame_rows.h)
 WAVES_PER_BLOCK = 4
 LANES = 64
 LEAD = 4096
@@ -690,3 +698,226 @@ def test_chain_behind_sparse_scan(A, torch, handle):
     torch.cuda.synchronize()
     g.replay()
     TF.same_dict(ch.results(Chain.SCAN + Chain.LATER), want, "replay")
+
+
+# ---- Part 4: the other launches on the same walk (csrc/frame_rows.h) -----------------------------
+
+RS_FLAG, RS_H, RS_KIND = RS.FLAG16, 1, C.CRC16
+
+
+def rs_width():
+    """The shortest row that holds two codewords at parity 16: n = 240 bytes
+    (239 fill one codeword), n' = 272."""
+    P = RS.PARITY[RS_FLAG]
+    n = 255 - P + 1
+    assert RS.codewords(n, P) == 2 and RS.codewords(n - 1, P) == 1
+    return RS.frame_size(n, P)
+
+
+@functools.lru_cache(maxsize=2)
+def rs_case(A, S, max_frames):
+    """POOL groups of rows drawn from the CPU test's cases (lengths 0, 5, the
+    last with one codeword, the first with two; every pattern but "parity"), the
+    host decoder's rows and records for them over poison, and the slots."""
+    W = rs_width()
+    rng = np.random.default_rng(S * 10 + max_frames + RS_FLAG)
+    P, c = RS.PARITY[RS_FLAG], C.CRC_BYTES[RS_KIND]
+    most = RS.max_len(W, RS_H, c, P)
+    assert RS.codewords(RS_H + most + c, P) == 2
+    cases = np.stack(TR.case_rows(A, RS_FLAG, RS_H, RS_KIND, W, rng, lengths=(0, 5, most - 1, most),
+                                  patterns=("none", "one", "t", "t+1", "ends", "header")))
+    rows = cases[rng.integers(0, len(cases), (POOL, max_frames))]
+    counts = stored_counts(rng, max_frames)
+    want = TR.host_stage(A, rows.reshape(POOL * max_frames, W), counts, max_frames, RS_H, RS_KIND, RS_FLAG)
+    return W, rows, counts, want, draw_slots(rng, S)
+
+
+@pytest.mark.parametrize("S,max_frames,most,waves", [GEOMETRY[1], GEOMETRY[4]])
+def test_rs_geometry(A, torch, handle, S, max_frames, most, waves):
+    """demod_frames_rs_async at parity 16, h 1, CRC-16, rows of 272 bytes (two
+    codewords): S = 5461 x 4 rows (3 waves a group, a last block with a wave
+    that leaves) and S = 16385 x 3 (the 16384 / S == 0 fallback). Rows and
+    records whole against the host decoder over poison, between guard bands;
+    the stored counts stay as they were."""
+    W, rows, counts, (w_rows, w_rec), idx = rs_case(A, S, max_frames)
+    wpg = waves_per_group(S, max_frames)
+    assert (MAX_WAVES // S if MAX_WAVES // S else 1) == most and S * wpg == waves
+    assert_last_block_holds_rows(S, wpg, idx, counts, max_frames, LIVE.get(S, WAVES_PER_BLOCK))
+    statuses = [w_rec[p, :min(counts[p], max_frames)].copy().view(A.FRAME_RS_DTYPE)["status"].reshape(-1)
+                for p in range(POOL)]
+    stats = tally(S, max_frames, idx, counts, statuses)
+    assert set(stats["status"]) == {RS.OK, RS.FAILED, RS.BAD_LENGTH}
+    assert not np.array_equal(w_rows, rows)                       # the host decoder corrected bytes
+    print(f"rs S={S} max_frames={max_frames}: {stats}")
+    d = handle(4, 2)
+    N = 8 * W
+    assert d._frame_shape(N, RS_H, RS_KIND, RS_FLAG) == (W, RS.max_len(W, RS_H, 2, 16))
+    got = TR.run_stage(A, torch, d, rows[idx].reshape(S * max_frames, W), [counts[p] for p in idx], max_frames, N,
+                       RS_H, RS_KIND, RS_FLAG)
+    TR.same(got, (w_rows[idx], w_rec[idx]), S)
+
+
+TXG = dict(S=16385, max_frames=3, K=2, n=1024, L=8, h=1, kind=C.CRC16, gap=2, max_len=2)
+
+
+def host_encoder(A, x, K):
+    """tx_ref's frame_count and frame_symbols by the host encoder
+    (demod_tx_frame_symbols, which tests/test_tx_cpu.py and tests/test_rs_cpu.py
+    hold to the references): every mode, the parity flags among them."""
+    memo = {}
+
+    def symbols(c, data):
+        data = bytes(data)
+        if data not in memo:
+            memo[data] = np.asarray(A.tx_frame_symbols(x, K, data), np.uint8)
+        return memo[data]
+
+    return (lambda c, length: len(symbols(c, bytes(length)))), symbols
+
+
+@pytest.mark.parametrize("fec", [0, RS.FLAG16])
+def test_tx_encode_geometry(A, torch, handle, monkeypatch, fec):
+    """demod_tx_encode_async at n_streams = 16385 (one wave a stream: the 16384
+    / S == 0 fallback), max_frames 3, a ring of three shortest frames and their
+    gaps, in a plain mode and with parity 16: places, states and rings whole
+    against tests/tx_ref.py's send over the host encoder's symbols, between
+    guard bands; records, counts and bytes as they were. Stored counts 0, 3,
+    above 3 and 2^32 - 1. The host encoder takes a frame's span from the same
+    frame_air_symbols (csrc/frame_shape.h) as the write kernel: the span is
+    independent of the device code through the CPU tests named above alone,
+    and through this test's passing on the commit before the span was shared."""
+    g = TXG
+    S, mf, K = g["S"], g["max_frames"], g["K"]
+    assert waves_per_group(S, mf) == 1 and last_block(S, 1)[0] == LIVE[S]
+    word = (np.arange(g["L"]) * 5 // 3) % K
+    c = T.make(T.loop_tones(K), g["n"], [0], word, h=g["h"], kind=g["kind"], fec=fec, max_len=g["max_len"],
+               gap=g["gap"], idle=(1, 0, 1), max_frames=mf, stride=2880, ring=1)
+    x = A.make_tx_cfg(c.sync, c.h, c.kind, c.fec, c.max_len, c.gap, c.idle, c.amplitude, c.sigma, c.seed, 1, mf,
+                      c.stride)
+    count_fn, symbols_fn = host_encoder(A, x, K)
+    monkeypatch.setattr(T, "frame_count", count_fn)
+    monkeypatch.setattr(T, "frame_symbols", symbols_fn)
+    c.C = 3 * (T.frame_count(c, 0) + c.gap)
+    x.ring_symbols = c.C
+    rng = np.random.default_rng(S + fec)
+    state = TT.random_state(c, POOL, rng)
+    state["tail"][:8] = state["head"][:8]                          # empty rings: three shortest frames fit
+    state["offset"][:8] = 0
+    records = np.zeros((POOL, mf), T.RECORD_DTYPE)
+    records["length"] = rng.choice([0, 0, 1, c.max_len, c.max_len + 1], (POOL, mf))
+    records["length"][0] = 0                                       # pool entry 0: all three accepted
+    data = rng.integers(0, 256, 64).astype(np.uint8)
+    records["body"] = rng.integers(0, data.size + 3, (POOL, mf))
+    count = np.array(stored_counts(rng, mf), np.uint64)
+    count[3] = 2 ** 32 - 1
+    count = count.astype(np.uint32)
+    idx = draw_slots(rng, S)
+    for poison in TT.POISONS:
+        ring = np.full((POOL, c.C), poison, np.uint8)
+        place0 = TT.poisoned((POOL, mf), T.PLACE_DTYPE, poison)
+        w_state, w_ring, w_place = T.send(c, state, ring, records, count, data, place0)
+        assert (w_place["status"][0] == T.OK).all()
+        assert {int(v) for p in range(POOL) for v in w_place["status"][p, :min(int(count[p]), mf)]} == \
+            {T.OK, T.BAD_LENGTH, T.NO_ROOM}
+        o = TT.Outs(torch, poison)
+        d_state = o.u8(S * 40, init=state[idx])
+        d_ring = o.u8(S * c.C, init=ring[idx])
+        d_place = o.u8(S * mf * 16)
+        ins = [records[idx].view(np.uint8).reshape(-1), count[idx].view(np.uint8), data]
+        d_in = [torch.from_numpy(a.copy()).cuda() for a in ins]
+        handle(4, K).tx_encode_async(x, d_state, d_ring, d_in[0], d_in[1].view(torch.int32), d_in[2], data.size, S,
+                                     d_place)
+        o.guards_intact()
+        TT.same(TT.host(d_place, np.uint8), w_place[idx].view(np.uint8), (fec, poison, "place"))
+        TT.same(TT.host(d_state, np.uint8), w_state[idx].view(np.uint8), (fec, poison, "state"))
+        TT.same(TT.host(d_ring, np.uint8), w_ring[idx], (fec, poison, "ring"))
+        for t, a in zip(d_in, ins):
+            TT.same(t.cpu().numpy(), a, "an input was written to")
+
+
+RXG = dict(S=16385, K=2, L=8, max_len=1, max_frames=2, pool=12, loaded=0.04)
+
+
+@functools.lru_cache(maxsize=1)
+def rx_push_case(A, d):
+    """One push's packets as a pool of 12: none (entries 1, 5, 9), a cut of a
+    one-frame recording (entry 0: all of it) and a two-frame recording behind
+    some noise, more windows than the ring holds: its first frame is lost to
+    the overflow. What the reference receiver (tests/rx_ref.py, on the
+    detector's own outputs) returns for each, and the slots: most streams push
+    nothing, about one in 25 a drawn entry."""
+    g = RXG
+    S, K, L = g["S"], g["K"], g["L"]
+    rng = np.random.default_rng(S)
+    word = np.array([1, 1, 0, 1, 0, 0, 1, 0], np.uint8)
+    Nsym = RX.row_symbols(TX.H, TX.KIND, 0, 1, g["max_len"])
+    ring = RX.min_ring(L, Nsym, TX.R)
+    short = RX.synth_pcm(TX.tones(K), RX.stream_symbols([4, b"\x5a", 5], K, word, TX.H, TX.KIND, 0, rng)[0], TX.N, 99)
+    long = RX.synth_pcm(TX.tones(K), RX.stream_symbols([30, b"\xc3", 3, b"", 12], K, word, TX.H, TX.KIND, 0, rng)[0],
+                        TX.N, 98)
+    assert (len(short) - TX.N) // TX.HOP + 1 < ring < (len(long) - TX.N) // TX.HOP + 1
+    packets, want, states = [], [], []
+    for p in range(g["pool"]):
+        if p % 4 == 1:
+            pk = None
+        elif p % 4 == 3:
+            pk = np.concatenate([rng.integers(-300, 301, 100 + 256 * (p // 4)).astype(np.int16), long])
+        else:
+            pk = short[:int(rng.integers(TX.N, len(short) + 1))] if p else short
+        ref = RX.Rx(1, K, TX.R, word, 0, Nsym, TX.H, TX.KIND, 0, g["max_frames"], ring)
+        piece = None
+        if pk is not None:
+            Wp = (len(pk) - TX.N) // TX.HOP + 1
+            sym, P = d.batch(pk[:(Wp - 1) * TX.HOP + TX.N], mags=True)
+            piece = (sym, P)
+            assert (Wp > ring) == (p % 4 == 3)
+        fr, bodies, summ = ref.push([piece])
+        packets.append(pk)
+        want.append((fr, bodies, summ))
+        states.append({k: int(ref.state[k][0]) for k in ref.state.dtype.names})
+    idx = np.where(rng.random(S) < g["loaded"], rng.integers(0, g["pool"], S), 1)
+    idx[0], idx[1], idx[2], idx[S - 1] = 0, 1, 3, 0
+    return word, Nsym, ring, packets, want, states, idx
+
+
+def test_rx_push_geometry(A, torch, handle):
+    """demod_rx_push at n_streams = 16385 (the copy launch runs one wave a
+    stream: the 16384 / S == 0 fallback), the smallest ring the receiver
+    accepts, 2 tones, one push: records, bytes and summary whole against the
+    reference receiver per stream, and the state of every one of the 16385
+    streams, those that pushed nothing included."""
+    g = RXG
+    S, K = g["S"], g["K"]
+    word, Nsym, ring, packets, want, states, idx = rx_push_case(A, handle(4, K))
+    assert row_waves(S, ring * K) == 1 and last_block(S, 1)[0] == LIVE[S]
+    assert len(want[0][0]) == 1 and states[3]["dropped"] > 0 and len(want[3][0]) >= 1
+    assert states[1] == dict(base=0, hold=0, dropped=0, cut_hits=0, fill=0, keep=0)
+    rxcfg = A.make_rx_cfg(word, 0, Nsym, TX.H, TX.KIND, 0, g["max_frames"], ring)
+    with pytest.raises(A.DemodError):
+        A.rx_sizes(handle(4, K).cfg, A.make_rx_cfg(word, 0, Nsym, TX.H, TX.KIND, 0, g["max_frames"], ring - 1), S)
+    frames, bodies, nb, checked, valid = [], [], 0, 0, 0
+    for s in np.flatnonzero(idx != 1):
+        fr, bo, summ = want[idx[s]]
+        for f, b in zip(fr, bo):
+            frames.append((s, len(b), int(f["window"]), nb, int(f["errors"]), 0))
+            nb += len(b)
+        bodies += bo
+        checked, valid = checked + summ["n_checked"], valid + summ["n_valid"]
+    w_frames = np.array(frames, RX.FRAME_DTYPE).reshape(-1)
+    host_packets = [None if packets[p] is None else packets[p].copy() for p in range(g["pool"])]
+    with A.Receiver(S, rxcfg, n=TX.N, hop=TX.HOP, freqs=TX.tones(K)) as rx:
+        fr, bo, summ = rx.push([packets[p] for p in idx])
+        assert fr.tobytes() == w_frames.tobytes() and bo == bodies
+        assert summ == dict(n_frames=len(frames), n_bytes=nb, n_checked=checked, n_valid=valid)
+        for s in range(S):
+            assert rx.state(s) == states[idx[s]], s
+    for a, b in zip(packets, host_packets):
+        assert a is None or np.array_equal(a, b), "a packet was written to"
+    print(f"rx push S={S} ring={ring}: {len(frames)} frames of {int((idx != 1).sum())} loaded streams, "
+          f"{int((idx % 4 == 3).sum())} of them past the ring")
+
+
+def row_waves(S, elements):
+    """waves a group of a launch that moves `elements` 4-byte words a group"""
+    most = MAX_WAVES // S if MAX_WAVES // S else 1
+    return min(-(-elements // LANES), most)
