@@ -279,6 +279,42 @@ class DemodFrameRs(ctypes.Structure):
 FRAME_RS_DTYPE = np.dtype(DemodFrameRs)
 
 
+class DemodFrameErase(ctypes.Structure):
+    """demod_frame_erase_t (include/demod.h "erasure decoding"): one row's
+    flagged bytes, the codewords the first attempt accepted and those that went
+    to the errors-only rule."""
+    _fields_ = [("erased", ctypes.c_uint32), ("used", ctypes.c_uint32), ("fallback", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+FRAME_ERASE_DTYPE = np.dtype(DemodFrameErase)
+
+
+def DEMOD_FEC_ERASE(level: int) -> int:
+    """The level's field of `fec` (include/demod.h "erasure decoding"): only with
+    a parity flag and fec & 0xFF == 0, and only for frames_coded and DemodRx."""
+    return (int(level) & 0x7F) << 16
+
+
+def erase_mode_parts(fec: int) -> Tuple[int, int]:
+    """(the mode without the level, the level) of a mode frames_coded and the
+    receiver take: one of the 20 modes, with a level only where there is a
+    parity flag and no convolutional code."""
+    fec = int(fec)
+    level, base = (fec >> 16) & 0x7F, fec & ~(0x7F << 16)
+    if base not in RS_MODES or (level and (base & 0xFF or base not in RS_PARITY_MODES)):
+        raise DemodError(DEMOD_BAD_ARG, "fec: not one of the 20 modes, or a level without a parity flag alone")
+    return base, level
+
+
+MAX_ROW_BYTES = 2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 19 * 32   # the widest row any mode takes: n' = 4710
+
+
+def mask_words(row_bytes: int) -> int:
+    """Wm: the uint64 words of one row's erasure mask."""
+    return (int(row_bytes) + 63) // 64
+
+
 def rs_mode_parts(fec: int) -> Tuple[int, int]:
     """(the coded mode or 0, P) of one of the 20 modes."""
     if fec not in RS_MODES:
@@ -481,6 +517,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                                  ctypes.POINTER(DemodFrameRs)]),
         "demod_frames_rs_async": (ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _SZ, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, _P, _P]),
+        "demod_rs_frame_decode_erasures": (ctypes.c_int, [_P, _SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
+                                                          _P]),
+        "demod_soft_erasures": (ctypes.c_int, [_P, _SZ, ctypes.c_int, _P, _SZ]),
+        "demod_frames_erasures_async": (ctypes.c_int, [_P, _P, _P, _SZ, _P, _P, _SZ, _SZ, _SZ, _SZ, ctypes.c_int,
+                                                       _P, _P]),
+        "demod_frames_rs_erasures_async": (ctypes.c_int, [_P, _P, _P, _P, _SZ, _SZ, _SZ, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, _P, _P, _P]),
         "demod_frame_size": (_SZ, [_SZ]),
         "demod_frame_encode": (ctypes.c_int, [_P, _SZ, _P, _SZ]),
         "demod_frame_decode": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(ctypes.c_void_p),
@@ -1469,6 +1512,60 @@ class Demodulator(_Handle):
         if rc < 0:
             raise DemodError(rc, "demod_frames_rs_async")
 
+    def frames_erasures_async(self, d_hits, d_mag, n_windows: int, d_first, d_results, n_groups: int,
+                              max_frames: int, sync_len: int, frame_symbols: int, level: int, d_erase,
+                              stream: int = 0) -> None:
+        """demod_frames_erasures_async: the erasure masks of the plain rows a
+        frame scan listed, from the detector's powers (arguments as
+        frames_decode_async's). d_erase (int64 holding the uint64 words,
+        n_groups * max_frames * Wm of the packed row's B bytes) is written.
+        Device tensors, checked like the batch calls'."""
+        S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
+        W = int(n_windows)
+        if W < 0 or W >= 2 ** 31:
+            raise DemodError(DEMOD_BAD_ARG, "n_windows not in 0 .. 2^31 - 1")
+        if not 1 <= int(level) <= 127:
+            raise DemodError(DEMOD_BAD_ARG, "level not in 1 .. 127")
+        if self.k not in (2, 4, 8, 16):
+            raise DemodError(DEMOD_BAD_ARG, "the erasure masks need K = 2, 4, 8 or 16 tones")
+        B = (N * bits_per_symbol(self.k) + 7) // 8     # plain rows, whatever header, CRC and parity they are read with
+        if not 1 <= B <= MAX_ROW_BYTES:
+            raise DemodError(DEMOD_BAD_ARG, "frame_symbols: no row, or one wider than any mode takes")
+        dev = int(self.cfg.device)
+        _check_dev(d_hits, "d_hits", "uint8", S * cap * ctypes.sizeof(DemodFrameHit), dev)
+        _check_dev(d_mag, "d_mag", "float32", max(W, 1) * self.k, dev)
+        _check_dev(d_first, "d_first", "int64", S, dev, nullable=True)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_erase, "d_erase", "int64", S * cap * mask_words(B), dev)
+        rc = self._lib.demod_frames_erasures_async(
+            self._h, _ptr(d_hits), _ptr(d_mag), W, _ptr(d_first) if d_first is not None else None,
+            _ptr(d_results), S, cap, int(sync_len), N, int(level), _ptr(d_erase), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_erasures_async")
+
+    def frames_rs_erasures_async(self, d_rows, d_erase, d_results, n_groups: int, max_frames: int,
+                                 frame_symbols: int, len_bytes: int, crc: int, fec: int, d_rs, d_erec,
+                                 stream: int = 0) -> None:
+        """demod_frames_rs_erasures_async: frames_rs_async with the rows'
+        erasure masks d_erase (int64 holding the uint64 words, Wm of the row
+        width a row); d_erec (uint8, 16 bytes a row: FRAME_ERASE_DTYPE) is
+        written beside d_rs."""
+        S, cap, N = _rows_shape(n_groups, max_frames, frame_symbols, "n_groups")
+        if fec not in RS_PARITY_MODES:
+            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the modes with a parity flag")
+        W, _ = self._frame_shape(N, len_bytes, crc, fec)
+        dev = int(self.cfg.device)
+        _check_dev(d_rows, "d_rows", "uint8", S * cap * W, dev)
+        _check_dev(d_erase, "d_erase", "int64", S * cap * mask_words(W), dev)
+        _check_dev(d_results, "d_results", "uint8", S * ctypes.sizeof(DemodFramesResult), dev)
+        _check_dev(d_rs, "d_rs", "uint8", S * cap * ctypes.sizeof(DemodFrameRs), dev)
+        _check_dev(d_erec, "d_erec", "uint8", S * cap * ctypes.sizeof(DemodFrameErase), dev)
+        rc = self._lib.demod_frames_rs_erasures_async(
+            self._h, _ptr(d_rows), _ptr(d_erase), _ptr(d_results), S, cap, N, int(len_bytes), int(crc), int(fec),
+            _ptr(d_rs), _ptr(d_erec), stream or None)
+        if rc < 0:
+            raise DemodError(rc, "demod_frames_rs_erasures_async")
+
     def rx_advance_async(self, d_state, d_ring_sym_in, d_ring_mag_in, d_new_sym, d_new_mag,
                          n_new_windows: int, d_new_first, d_new_count, n_streams: int, ring_windows: int,
                          d_ring_sym_out, d_ring_mag_out, d_first, d_count, stream: int = 0) -> None:
@@ -1605,8 +1702,7 @@ class Demodulator(_Handle):
         and the coded check; with a parity flag the Reed-Solomon stage before
         the check, and with fec & 0xFF == 0 over the scan's packed rows.
         Returns what frames_checked returns."""
-        if fec not in RS_MODES:
-            raise DemodError(DEMOD_BAD_ARG, "fec: not one of the 20 modes")
+        erase_mode_parts(fec)   # alone here: with or without DEMOD_FEC_ERASE(level)
         return self._frames_checked(pcm, sync, max_errors, frame_symbols, len_bytes, crc, int(fec), max_frames,
                                     n_windows, body)
 
@@ -1618,7 +1714,7 @@ class Demodulator(_Handle):
         N = int(frame_symbols)
         if N < 0 or (max_frames is not None and max_frames < 1):
             raise DemodError(DEMOD_BAD_ARG, "frame_symbols < 0 or max_frames < 1")
-        _, max_len = self._frame_shape(N, len_bytes, crc, fec)
+        _, max_len = self._frame_shape(N, len_bytes, crc, fec & ~(0x7F << 16))
         if max_frames is None:
             max_frames = n_windows // max(self.n // self.hop, 1) + 1
         cap = int(max_frames)
@@ -2039,6 +2135,29 @@ def soft_bits(powers) -> np.ndarray:
     return out[:rc].copy()
 
 
+def pack_mask(flags, row_bytes: int) -> np.ndarray:
+    """A bool a row byte -> the row's Wm uint64 mask words (byte b is bit b & 63
+    of word b >> 6; bits at b >= row_bytes 0)."""
+    f = np.zeros(mask_words(row_bytes) * 64, dtype=np.uint8)
+    src = np.asarray(flags, dtype=bool).reshape(-1)[:int(row_bytes)]
+    f[:src.size] = src
+    return np.packbits(f, bitorder="little").view("<u8").astype(np.uint64)
+
+
+def soft_erasures(soft, level: int, row_bytes: int) -> np.ndarray:
+    """demod_soft_erasures: the Wm uint64 mask words of one plain row from its
+    int8 soft values in air order."""
+    q = np.ascontiguousarray(soft, dtype=np.int8).reshape(-1)
+    if int(row_bytes) < 1 or int(row_bytes) >= 2 ** 31:
+        raise DemodError(DEMOD_BAD_ARG, "row_bytes not in 1 .. 2^31 - 1")
+    out = np.zeros(mask_words(row_bytes), dtype=np.uint64)
+    keep = q if q.size else np.zeros(1, dtype=np.int8)
+    rc = load_library().demod_soft_erasures(keep.ctypes.data, q.size, int(level), out.ctypes.data, int(row_bytes))
+    if rc < 0:
+        raise DemodError(rc, "demod_soft_erasures")
+    return out
+
+
 def coded_frame_decode(soft, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE,
                        cap: Optional[int] = None) -> Tuple[bytes, dict]:
     """demod_coded_frame_decode: the host decoder on int8 soft values. Returns
@@ -2174,15 +2293,31 @@ def rs_frame_encode(data: bytes, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCIT
     return bytes(out[:n])
 
 
-def rs_frame_decode(row, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE, fec: int = DEMOD_FEC_RS16):
+def rs_frame_decode(row, len_bytes: int = 2, crc: int = DEMOD_CRC16_CCITT_FALSE, fec: int = DEMOD_FEC_RS16,
+                    erase=None):
     """demod_rs_frame_decode on a copy of `row` (bytes or uint8 array; its
     length is the row width): (the corrected row, the record as a dict, the
-    bytes covered)."""
+    bytes covered). With erase (the row's Wm uint64 mask words, or a bool
+    array a row byte) demod_rs_frame_decode_erasures: (the corrected row, the
+    record, the erasure record, the bytes covered)."""
     buf = np.array(np.frombuffer(bytes(row), np.uint8) if isinstance(row, (bytes, bytearray)) else row,
                    dtype=np.uint8).reshape(-1).copy()
     if buf.size == 0:
         raise DemodError(DEMOD_BAD_ARG, "row: empty")
     rec = DemodFrameRs()
+    if erase is not None:
+        words = np.asarray(erase)
+        words = pack_mask(words, buf.size) if words.dtype == np.bool_ else \
+            np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+        if words.size < mask_words(buf.size):
+            raise DemodError(DEMOD_BAD_ARG, "erase: fewer than Wm words")
+        erec = DemodFrameErase()
+        n = load_library().demod_rs_frame_decode_erasures(buf.ctypes.data, buf.size, int(len_bytes), int(crc),
+                                                          int(fec), words.ctypes.data, ctypes.byref(rec),
+                                                          ctypes.byref(erec))
+        if n < 0:
+            raise DemodError(n, "demod_rs_frame_decode_erasures")
+        return buf, _struct_dict(rec), _struct_dict(erec), n
     n = load_library().demod_rs_frame_decode(buf.ctypes.data, buf.size, int(len_bytes), int(crc), int(fec),
                                              ctypes.byref(rec))
     if n < 0:

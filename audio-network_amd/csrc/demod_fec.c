@@ -142,6 +142,23 @@ int demod_soft_bits(const float *powers, uint32_t k, int8_t *soft)
     return bits;
 }
 
+int demod_soft_erasures(const int8_t *soft, size_t n_soft, int level, uint64_t *erase, size_t row_bytes)
+{
+    if (!soft || !erase || ((uintptr_t)erase & 7) != 0 || level < 1 || level > 127) return DEMOD_BAD_ARG;
+    if (row_bytes == 0 || row_bytes > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    const unsigned Wm = rs_mask_words((unsigned)row_bytes);
+    memset(erase, 0, (size_t)Wm * sizeof(uint64_t));
+    for (size_t b = 0; b < row_bytes; ++b) {
+        int least = 128;
+        for (size_t m = 8 * b; m < 8 * b + 8; ++m) {
+            const int q = m < n_soft ? soft[m] : 0, a = q < 0 ? -q : q;
+            if (a < least) least = a;
+        }
+        if (least < level) erase[b >> 6] |= (uint64_t)1 << (b & 63u);
+    }
+    return (int)Wm;
+}
+
 /* u_t of steps t_end-1 .. 0 from state s at step t_end, into bits[] (one byte a bit) */
 static void trace_back(const uint64_t *surv, size_t t_end, unsigned s, uint8_t *bits)
 {

@@ -54,8 +54,13 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
     const uint32_t R = frames_args(st->cfg, n_windows, sync, sync_len, max_errors, frame_symbols, max_frames, true);
     if (R == 0) return DEMOD_BAD_ARG;   // before the detector runs
     const size_t dcap = hit_cap(max_frames, n_windows, R);
+    const int level = (int)rs_erase_level((unsigned)fec);   // of "erasure decoding": this call's own
+    fec = (int)rs_erase_strip((unsigned)fec);               // the stages' mode
     frame_shape s;
     if (!stage_shape(st->cfg, 1, dcap, sync_len, frame_symbols, len_bytes, crc, fec, s)) return DEMOD_BAD_ARG;
+    unsigned mask_row = 0;   // with a level: what the producer will ask, before anything is queued
+    if (level && (!erasures_shape(st->cfg, 1, dcap, sync_len, frame_symbols, mask_row) || mask_row != s.row_bytes))
+        return DEMOD_BAD_ARG;
     const int conv = s.fec;   // the trellis's mode or 0 (the scan's packed rows); s.parity: the outer code's stage
     const size_t fec_work = conv ? demod_fec_decode_workspace_size(&st->cfg, 1, dcap, frame_symbols, conv) : 0;
     DeviceGuard guard(st->device);
@@ -74,6 +79,10 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
         HIP_TRY(st->d_frm_packed.reserve(dcap * B));
     }
     if (s.parity) HIP_TRY(st->d_rs.reserve(dcap));
+    if (level) {
+        HIP_TRY(st->d_erase.reserve(dcap * rs_mask_words(s.row_bytes)));
+        HIP_TRY(st->d_erec.reserve(dcap));
+    }
     HIP_TRY(st->d_chk_check.reserve(dcap));
     HIP_TRY(st->d_chk_kept.reserve(dcap));
     HIP_TRY(st->d_chk_sum.reserve(1));
@@ -93,7 +102,14 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
                                        st->d_fec_decode.p, st->d_fec_work.p, fec_work, st->stream);
         if (rc < 0) return rc;
     }
-    if (s.parity) {
+    if (level) {   // the packed rows' masks from the powers, then the outer code with them
+        rc = demod_frames_erasures_async(st, st->d_frm_hits.p, st->d_mag.p, n_windows, nullptr, st->d_frm_res.p, 1,
+                                         dcap, sync_len, N, level, st->d_erase.p, st->stream);
+        if (rc < 0) return rc;
+        rc = demod_frames_rs_erasures_async(st, rows, st->d_erase.p, st->d_frm_res.p, 1, dcap, N, len_bytes, crc,
+                                            fec, st->d_rs.p, st->d_erec.p, st->stream);
+        if (rc < 0) return rc;
+    } else if (s.parity) {
         rc = demod_frames_rs_async(st, rows, st->d_frm_res.p, 1, dcap, N, len_bytes, crc, fec, st->d_rs.p,
                                    st->stream);
         if (rc < 0) return rc;
@@ -122,6 +138,30 @@ static int frames_checked_run(demod_t *st, const int16_t *pcm, size_t n_windows,
         }
     }
     return (int)nk;
+}
+
+// The outer code's stage, with or without masks: its refusals and the launch's fields.
+static int frames_rs_params(demod_t *st, uint8_t *d_rows, const demod_frames_result_t *d_results, size_t n_groups,
+                            size_t max_frames, size_t frame_symbols, int len_bytes, int crc, int fec,
+                            demod_frame_rs_t *d_rs, FramesRsParams &p)
+{
+    if (!st || !d_rows || !d_results || !d_rs) return DEMOD_BAD_ARG;
+    if (((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_rs & 3) != 0) return DEMOD_BAD_ARG;
+    if (!rs_mode_valid((unsigned)fec) || !rs_parity((unsigned)fec)) return DEMOD_BAD_ARG;
+    frame_shape s;   // the shape the coded check will see: the same refusals (it has no word here)
+    if (!stage_shape(st->cfg, n_groups, max_frames, 1, frame_symbols, len_bytes, crc, fec, s)) return DEMOD_BAD_ARG;
+    std::memset(&p, 0, sizeof(FramesRsParams));
+    p.n_groups = (unsigned)n_groups;
+    p.max_frames = (unsigned)max_frames;
+    p.row_bytes = s.row_bytes;
+    p.max_len = s.max_len;
+    p.len_bytes = s.len_bytes;
+    p.crc_bytes = s.crc_bytes;
+    p.parity = s.parity;
+    p.rows = d_rows;
+    p.res = d_results;
+    p.rs = d_rs;
+    return DEMOD_OK;
 }
 
 extern "C" {
@@ -213,26 +253,68 @@ int demod_frames_rs_async(demod_t *st, uint8_t *d_rows, const demod_frames_resul
                           size_t n_groups, size_t max_frames, size_t frame_symbols, int len_bytes, int crc,
                           int fec, demod_frame_rs_t *d_rs, void *stream)
 {
-    if (!st || !d_rows || !d_results || !d_rs) return DEMOD_BAD_ARG;
-    if (((uintptr_t)d_results & 7) != 0 || ((uintptr_t)d_rs & 3) != 0) return DEMOD_BAD_ARG;
-    if (!rs_mode_valid((unsigned)fec) || !rs_parity((unsigned)fec)) return DEMOD_BAD_ARG;
-    frame_shape s;   // the shape the coded check will see: the same refusals (it has no word here)
-    if (!stage_shape(st->cfg, n_groups, max_frames, 1, frame_symbols, len_bytes, crc, fec, s)) return DEMOD_BAD_ARG;
     FramesRsParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.n_groups = (unsigned)n_groups;
-    p.max_frames = (unsigned)max_frames;
-    p.row_bytes = s.row_bytes;
-    p.max_len = s.max_len;
-    p.len_bytes = s.len_bytes;
-    p.crc_bytes = s.crc_bytes;
-    p.parity = s.parity;
-    p.rows = d_rows;
-    p.res = d_results;
-    p.rs = d_rs;
+    const int rc = frames_rs_params(st, d_rows, d_results, n_groups, max_frames, frame_symbols, len_bytes, crc, fec,
+                                    d_rs, p);
+    if (rc != DEMOD_OK) return rc;
     DeviceGuard guard(st->device);
     HIP_TRY(guard.err);
     HIP_TRY(launch_frames_rs(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+// ---- erasure decoding (frames_erasures.hip, frames_rs.hip) ------------------------
+
+int demod_frames_erasures_async(demod_t *st, const demod_frame_hit_t *d_hits, const float *d_mags,
+                                size_t n_windows, const uint64_t *d_first,
+                                const demod_frames_result_t *d_results, size_t n_groups, size_t max_frames,
+                                size_t sync_len, size_t frame_symbols, int level, uint64_t *d_erase,
+                                void *stream)
+{
+    if (!st || !d_hits || !d_mags || !d_results || !d_erase) return DEMOD_BAD_ARG;
+    if (!aligned8(d_hits, d_results, d_first, d_erase) || !aligned4(d_mags)) return DEMOD_BAD_ARG;
+    if (level < 1 || level > 127 || n_windows > 0x7FFFFFFF) return DEMOD_BAD_ARG;
+    unsigned B;   // plain rows: the packed row's width is all of a row's shape that is used
+    const uint32_t R = erasures_shape(st->cfg, n_groups, max_frames, sync_len, frame_symbols, B);
+    if (R == 0) return DEMOD_BAD_ARG;
+    FramesEraseParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.hits = d_hits;
+    p.mag = d_mags;
+    p.first = reinterpret_cast<const unsigned long long *>(d_first);
+    p.res = d_results;
+    p.n_windows = (unsigned)n_windows;
+    p.n_groups = (unsigned)n_groups;
+    p.max_frames = (unsigned)max_frames;
+    p.frame_symbols = (unsigned)frame_symbols;
+    p.row_bytes = B;
+    p.k = (int)st->cfg.k;
+    p.bits = demod_bits_per_symbol(st->cfg.k);
+    p.phases = (int)R;
+    p.sync_len = (int)sync_len;
+    p.level = level;
+    p.erase = d_erase;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_frames_erasures(p, (hipStream_t)stream));
+    return DEMOD_OK;
+}
+
+int demod_frames_rs_erasures_async(demod_t *st, uint8_t *d_rows, const uint64_t *d_erase,
+                                   const demod_frames_result_t *d_results, size_t n_groups, size_t max_frames,
+                                   size_t frame_symbols, int len_bytes, int crc, int fec,
+                                   demod_frame_rs_t *d_rs, demod_frame_erase_t *d_erec, void *stream)
+{
+    FramesRsEraseParams p;
+    if (!d_erase || !d_erec || !aligned8(d_erase) || !aligned4(d_erec)) return DEMOD_BAD_ARG;
+    const int rc = frames_rs_params(st, d_rows, d_results, n_groups, max_frames, frame_symbols, len_bytes, crc, fec,
+                                    d_rs, p);
+    if (rc != DEMOD_OK) return rc;
+    p.erase = d_erase;
+    p.erec = d_erec;
+    DeviceGuard guard(st->device);
+    HIP_TRY(guard.err);
+    HIP_TRY(launch_frames_rs_erasures(p, (hipStream_t)stream));
     return DEMOD_OK;
 }
 
@@ -254,7 +336,7 @@ int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const 
                        size_t max_frames, demod_frames_result_t *result,
                        demod_frames_check_result_t *summary)
 {
-    if (!rs_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;
+    if (!rs_erase_mode_valid((unsigned)fec)) return DEMOD_BAD_ARG;   // alone here: with or without a level
     return frames_checked_run(st, pcm, n_windows, sync, sync_len, max_errors, frame_symbols, len_bytes, crc,
                               fec, hits, lengths, body, max_frames, result, summary);
 }

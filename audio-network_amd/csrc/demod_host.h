@@ -182,6 +182,8 @@ struct demod {
     fskd::DevBuf<demod_frame_decode_t> d_fec_decode;
     fskd::DevBuf<unsigned char> d_fec_work;
     fskd::DevBuf<demod_frame_rs_t> d_rs;
+    fskd::DevBuf<uint64_t> d_erase;     // with a level: the rows' erasure masks and the decoder's second records
+    fskd::DevBuf<demod_frame_erase_t> d_erec;
     fskd::PinnedBuf<int16_t> h_in;      // pinned staging for small host calls
     fskd::PinnedBuf<uint8_t> h_sym;
     fskd::PinnedBuf<float> h_mag;       // [h_sym.cap][k]
@@ -303,6 +305,21 @@ static inline uint32_t stage_shape(const demod_cfg_t &cfg, size_t n_groups, size
         return 0;
     const int bits = demod_bits_per_symbol(cfg.k);
     return frame_shape_fill(&s, bits, cfg.k == (1u << bits), frame_symbols, len_bytes, crc, fec) ? 0 : R;
+}
+
+// What the erasure masks' producer asks of its call beside the level and the pointers (include/demod.h "erasure
+// decoding"): K one of 2, 4, 8, 16, the groups and rows, the word's length and plain rows of B bytes. The entries
+// that run the producer for a level ask the same before they queue anything. R with B filled, or 0.
+static inline uint32_t erasures_shape(const demod_cfg_t &cfg, size_t n_groups, size_t max_frames, size_t sync_len,
+                                      size_t frame_symbols, unsigned &B)
+{
+    const uint32_t R = acquire_phases(cfg);
+    if (R == 0 || !group_rows_ok(n_groups, max_frames, false) || sync_len == 0 || sync_len > DEMOD_MAX_SYNC)
+        return 0;
+    if (cfg.k != 2 && cfg.k != 4 && cfg.k != 8 && cfg.k != 16) return 0;
+    B = frame_plain_row_bytes(demod_bits_per_symbol(cfg.k), frame_symbols);
+    if (B == 0 || (sync_len + frame_symbols) * (size_t)R > 0x7FFFFFFF) return 0;
+    return R;
 }
 
 // The shape fields FramesCheckParams, FramesFecParams and RxCollectParams name alike, from the row's shape

@@ -13,6 +13,7 @@ struct demod_frame_check;
 struct demod_frames_check_result;
 struct demod_frame_decode;
 struct demod_frame_rs;
+struct demod_frame_erase;
 struct demod_rx_stream_state;
 struct demod_rx_frame;
 struct demod_rx_summary;
@@ -435,6 +436,32 @@ struct FramesRsParams {
     ::demod_frame_rs *rs;                 // [n_groups][max_frames]
 };
 hipError_t launch_frames_rs(const FramesRsParams &p, hipStream_t s);
+// the same with the rows' erasure masks (include/demod.h "erasure decoding"): the kernel's second instantiation
+struct FramesRsEraseParams : FramesRsParams {
+    const uint64_t *erase;                // [n_groups][max_frames][ceil(row_bytes / 64)]
+    ::demod_frame_erase *erec;            // [n_groups][max_frames]
+};
+hipError_t launch_frames_rs_erasures(const FramesRsEraseParams &p, hipStream_t s);
+
+// frames_erasures.hip: the masks' producer over the plain rows a frame scan listed (groups and rows as
+// frame_rows.h): a wave per 64 bytes of a row, no workspace.
+struct FramesEraseParams {
+    const ::demod_frame_hit *hits;        // [n_groups][max_frames]
+    const float *mag;                     // [n_windows][k]
+    const unsigned long long *first;      // [n_groups] or nullptr: every base 0
+    const ::demod_frames_result *res;     // [n_groups]
+    unsigned n_windows;                   // < 2^31
+    unsigned n_groups;
+    unsigned max_frames;                  // n_groups * max_frames < 2^31
+    unsigned frame_symbols;               // N
+    unsigned row_bytes;                   // B = ceil(N bits / 8)
+    int k, bits;                          // k = 2^bits
+    int phases;                           // R
+    int sync_len;                         // L; (L + N) R < 2^31
+    int level;                            // 1 .. 127
+    uint64_t *erase;                      // [n_groups][max_frames][ceil(row_bytes / 64)]
+};
+hipError_t launch_frames_erasures(const FramesEraseParams &p, hipStream_t s);
 
 // frames_carry.hip: the receiver's device-resident carry (include/demod.h
 // "receiver"). advance moves each stream's kept windows and its new ones from

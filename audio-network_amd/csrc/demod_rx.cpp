@@ -29,7 +29,12 @@ int demod_rx_sizes(const demod_cfg_t *cfg, const demod_rx_cfg_t *rxcfg, size_t n
     if (R == 0) return DEMOD_BAD_ARG;
     // the check's (or the decode's and the coded check's): S, max_frames, the row shape
     frame_shape s;
-    if (!stage_shape(*cfg, S, x.max_frames, L, N, (int)x.len_bytes, (int)x.crc, (int)x.fec, s))
+    // (a level of "erasure decoding" is the receiver's own: the row's shape is the mode's without it)
+    if (x.fec && !rs_erase_mode_valid(x.fec)) return DEMOD_BAD_ARG;
+    if (!stage_shape(*cfg, S, x.max_frames, L, N, (int)x.len_bytes, (int)x.crc, (int)rs_erase_strip(x.fec), s))
+        return DEMOD_BAD_ARG;
+    unsigned mask_row = 0;   // with a level: what the producer will ask of every push
+    if (rs_erase_level(x.fec) && (!erasures_shape(*cfg, S, x.max_frames, L, N, mask_row) || mask_row != s.row_bytes))
         return DEMOD_BAD_ARG;
     if (C < 2 * (L + N) * R || C >= ((size_t)1 << 31) / S || S * C > 0x7FFFFFFF) return DEMOD_BAD_ARG;
     const size_t rows = S * x.max_frames;
@@ -157,6 +162,8 @@ struct demod_rx {
     DevBuf<uint8_t> d_rows;               // [S][max_frames][row_bytes]: packed, or decoded
     DevBuf<demod_frame_decode_t> d_decode;
     DevBuf<demod_frame_rs_t> d_rs;        // with a parity flag: the outer code's records
+    DevBuf<uint64_t> d_erase;             // with a level: the rows' erasure masks and the decoder's second records
+    DevBuf<demod_frame_erase_t> d_erec;
     DevBuf<demod_frame_check_t> d_check;
     DevBuf<uint32_t> d_kept;
     DevBuf<uint8_t> d_body;
@@ -189,11 +196,15 @@ static int rx_allocate(demod_rx_t *rx)
     HIP_TRY(rx->d_first.reserve(S));
     HIP_TRY(rx->d_count.reserve(S));
     HIP_TRY(rx->d_scan_work.reserve(z.scan_work_bytes));
-    if (rs_mode_conv(rx->rx.fec)) {
+    if (rs_mode_conv(rs_erase_strip(rx->rx.fec))) {
         HIP_TRY(rx->d_fec_work.reserve(z.decode_work_bytes));
         HIP_TRY(rx->d_decode.reserve(rows));
     }
     if (rs_parity(rx->rx.fec)) HIP_TRY(rx->d_rs.reserve(rows));
+    if (rs_erase_level(rx->rx.fec)) {
+        HIP_TRY(rx->d_erase.reserve(rows * rs_mask_words((unsigned)z.row_bytes)));
+        HIP_TRY(rx->d_erec.reserve(rows));
+    }
     HIP_TRY(rx->d_col_work.reserve(z.collect_work_bytes));
     HIP_TRY(rx->d_hits.reserve(rows));
     HIP_TRY(rx->d_res.reserve(S));
@@ -277,7 +288,8 @@ int demod_rx_state(const demod_rx_t *rx, size_t stream, demod_rx_stream_state_t 
 static int rx_run(demod_rx_t *rx, demod_t *st, const StreamsStage &sg)
 {
     const demod_rx_cfg_t &x = rx->rx;
-    const unsigned conv = rs_mode_conv(x.fec);   // the trellis's mode, or 0: the scan writes packed rows
+    const int level = (int)rs_erase_level(x.fec), fec = (int)rs_erase_strip(x.fec);   // the stages' mode
+    const unsigned conv = rs_mode_conv((unsigned)fec);   // the trellis's mode, or 0: the scan writes packed rows
     const size_t S = rx->S, C = x.ring_windows, Wb = sg.Wb, mf = x.max_frames;
     const size_t L = x.sync_len, N = x.frame_symbols;
     // the tables of demod_segments_layout's layout, 16-byte aligned behind the samples
@@ -312,18 +324,26 @@ static int rx_run(demod_rx_t *rx, demod_t *st, const StreamsStage &sg)
     uint8_t *d_body = rx->sz.max_len ? rx->d_body.p : nullptr;
     if (conv) {
         rc = demod_frames_decode_async(st, rx->d_hits.p, rx->ring_mag[out].p, S * C, rx->d_first.p, rx->d_res.p,
-                                       S, mf, L, N, (int)x.len_bytes, (int)x.crc, (int)x.fec, rx->d_rows.p,
+                                       S, mf, L, N, (int)x.len_bytes, (int)x.crc, fec, rx->d_rows.p,
                                        rx->d_decode.p, rx->d_fec_work.p, rx->sz.decode_work_bytes, st->stream);
         if (rc < 0) return rc;
     }
-    if (rs_parity(x.fec)) {   // the outer code over the packed or the decoded rows, before the check reads them
+    if (level) {   // the packed rows' masks from the ring's powers, then the outer code with them
+        rc = demod_frames_erasures_async(st, rx->d_hits.p, rx->ring_mag[out].p, S * C, rx->d_first.p, rx->d_res.p,
+                                         S, mf, L, N, level, rx->d_erase.p, st->stream);
+        if (rc < 0) return rc;
+        rc = demod_frames_rs_erasures_async(st, rx->d_rows.p, rx->d_erase.p, rx->d_res.p, S, mf, N,
+                                            (int)x.len_bytes, (int)x.crc, fec, rx->d_rs.p, rx->d_erec.p,
+                                            st->stream);
+        if (rc < 0) return rc;
+    } else if (rs_parity((unsigned)fec)) {   // the outer code over the packed or the decoded rows, before the check
         rc = demod_frames_rs_async(st, rx->d_rows.p, rx->d_res.p, S, mf, N, (int)x.len_bytes, (int)x.crc,
-                                   (int)x.fec, rx->d_rs.p, st->stream);
+                                   fec, rx->d_rs.p, st->stream);
         if (rc < 0) return rc;
     }
-    if (x.fec) {
+    if (fec) {
         rc = demod_frames_check_coded_async(st, rx->d_hits.p, rx->d_rows.p, rx->d_res.p, S, mf, L, N,
-                                            (int)x.len_bytes, (int)x.crc, (int)x.fec, rx->d_check.p,
+                                            (int)x.len_bytes, (int)x.crc, fec, rx->d_check.p,
                                             rx->d_kept.p, d_body, rx->d_chk_sum.p, st->stream);
     } else {
         rc = demod_frames_check_async(st, rx->d_hits.p, rx->d_rows.p, rx->d_res.p, S, mf, L, N,
@@ -332,7 +352,7 @@ static int rx_run(demod_rx_t *rx, demod_t *st, const StreamsStage &sg)
     }
     if (rc < 0) return rc;
     rc = demod_rx_collect_async(st, rx->d_state(), rx->d_hits.p, rx->d_res.p, rx->d_check.p, rx->d_kept.p,
-                                d_body, rx->d_chk_sum.p, S, mf, L, N, (int)x.len_bytes, (int)x.crc, (int)x.fec,
+                                d_body, rx->d_chk_sum.p, S, mf, L, N, (int)x.len_bytes, (int)x.crc, fec,
                                 reinterpret_cast<demod_rx_frame_t *>(rx->d_out.p + rx->frames_off()),
                                 rx->d_out.p + rx->bodies_off(),
                                 reinterpret_cast<demod_rx_summary_t *>(rx->d_out.p), rx->d_col_work.p,

@@ -8,6 +8,9 @@
  *  row    N symbols of `bits` bits are C = N bits air bits: B = ceil(C / 8) packed bytes, or with the
  *         convolutional code St trellis steps that decode to Bd = (St - 6) / 8 bytes
  *  frame  len (h bytes) || data || CRC (c bytes), n bytes; with an outer code of P parity bytes n' (rs_ops.h)
+ *  level  DEMOD_FEC_ERASE(level) changes none of this: the entries that take it (demod_frames_coded, the receiver)
+ *         strip it (rs_ops.h rs_erase_strip) before they ask for a shape, and frame_shape_fill refuses it like any
+ *         unknown bit; a row's mask has rs_mask_words(row_bytes) words
  */
 #ifndef FSKD_FRAME_SHAPE_H
 #define FSKD_FRAME_SHAPE_H
@@ -55,6 +58,18 @@ FRAME_SHAPE_FN unsigned frame_air_symbols(unsigned len, unsigned h, unsigned c, 
         span = fec_air_bits(conv, *kept);
     }
     return (span + bits - 1u) / bits;
+}
+
+/* The widest row any mode takes: n' at the payload limit with h = 2, CRC-32 and P = 32 (D = 19) */
+#define FRAME_MAX_ROW_BYTES (2 + DEMOD_MAX_FRAME_PAYLOAD + 4 + 19 * RS_MAX_PARITY)
+
+/* B of plain rows of frame_symbols symbols of `bits` bits, whatever header, CRC and parity flag they are read
+ * with (the erasure masks' producer, which reads none of them); 0 for no symbol or more than the widest row. */
+FRAME_SHAPE_FN unsigned frame_plain_row_bytes(int bits, size_t frame_symbols)
+{
+    if (frame_symbols == 0 || frame_symbols > 8u * FRAME_MAX_ROW_BYTES) return 0;
+    const unsigned B = ((unsigned)frame_symbols * (unsigned)bits + 7u) / 8u;
+    return B <= FRAME_MAX_ROW_BYTES ? B : 0u;
 }
 
 struct frame_shape {

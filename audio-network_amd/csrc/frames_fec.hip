@@ -33,6 +33,7 @@
 // outputs do not depend on later steps. A wave's loads of its slot follow its
 // own stores in program order behind a workgroup fence.
 #include "frame_rows.h"
+#include "soft_ops.h"
 
 namespace fskd {
 
@@ -51,22 +52,8 @@ static __device__ __forceinline__ int fec_soft(const FramesFecParams &p, bool li
         m = fec_air_of_mother(p.fec, m);
         if (m == FEC_MAP_NONE) return 0;
     }
-    const unsigned bits = (unsigned)p.bits, j = m / bits, b = m - j * bits;   // j < N
-    const unsigned long long w = bw + ((unsigned long long)p.sync_len + j) * (unsigned)p.phases;
-    if (w >= p.n_windows) return 0;
-    const float *P = p.mag + (size_t)w * (unsigned)p.k;
-    const unsigned mask = 1u << (bits - 1u - b);
-    float a0 = P[0], a1 = P[mask];
-    for (unsigned i = 1; i < (unsigned)p.k; ++i) {
-        const float f = P[i];
-        if (i & mask) {
-            if (f > a1) a1 = f;
-        } else if (f > a0) {
-            a0 = f;
-        }
-    }
-    const double d = (double)a0 - (double)a1, s = fabs((double)a0) + fabs((double)a1);
-    return (s > 0.0 && s <= 1.7976931348623157e308) ? (int)rint(127.0 * d / s) : 0;
+    return soft_air_value(p.mag, p.n_windows, (unsigned)p.k, (unsigned)p.bits, (unsigned)p.sync_len,
+                          (unsigned)p.phases, bw, m);   // m / bits < N
 }
 
 struct FecLane {

@@ -12,6 +12,8 @@
  *            P)) codewords byte by byte: codeword j holds F[j], F[j + D], ..
  *            (k_j = ceil((n - j) / D) bytes) and the parity bytes n + i D + j,
  *            i < P. n' = n + D P.
+ *  erasures  the level's bits of `fec`, the mask's addressing and the flag of a
+ *            codeword's symbol (include/demod.h "erasure decoding")
  */
 #ifndef FSKD_RS_OPS_H
 #define FSKD_RS_OPS_H
@@ -26,6 +28,8 @@
 #define RS_FLAG_32 0x200u
 #define RS_MAX_PARITY 32
 #define RS_MAX_T 16
+#define RS_MAX_ERRATA RS_MAX_PARITY      /* f erasures and e errors, 2 e + f <= P: at most P places */
+#define RS_MAX_PSI (RS_MAX_PARITY + 1)   /* the coefficients of the errata locator, degree e + f <= P */
 
 /* P of a mode: 16, 32, or 0 without a parity flag */
 RS_OPS_FN unsigned rs_parity(unsigned fec) { return (fec & RS_FLAG_16) ? 16u : (fec & RS_FLAG_32) ? 32u : 0u; }
@@ -42,6 +46,33 @@ RS_OPS_FN int rs_mode_valid(unsigned fec)
 
 /* the convolutional part of a valid mode: 0 or one of the six coded modes */
 RS_OPS_FN unsigned rs_mode_conv(unsigned fec) { return fec & ~(RS_FLAG_16 | RS_FLAG_32); }
+
+/* ---- the erasure level and mask (include/demod.h "erasure decoding") ---------
+ *
+ *  level   DEMOD_FEC_ERASE(level): bits 16 .. 22 of `fec`, 0 for none; only with a parity flag and low nibble 0
+ *  mask    one bit per row byte: row r has Wm = ceil(row_bytes / 64) words, byte b is bit b & 63 of word b >> 6
+ */
+#define RS_ERASE_SHIFT 16
+#define RS_ERASE_FIELD (0x7Fu << RS_ERASE_SHIFT)
+
+RS_OPS_FN unsigned rs_erase_level(unsigned fec) { return (fec & RS_ERASE_FIELD) >> RS_ERASE_SHIFT; }
+
+/* the mode without the level: what goes on the air, and what every other entry takes */
+RS_OPS_FN unsigned rs_erase_strip(unsigned fec) { return fec & ~RS_ERASE_FIELD; }
+
+/* a valid mode, with or without a level; a level only with a parity flag and no convolutional code */
+RS_OPS_FN int rs_erase_mode_valid(unsigned fec)
+{
+    const unsigned base = rs_erase_strip(fec);
+    if (!rs_mode_valid(base)) return 0;
+    return rs_erase_level(fec) == 0u || (rs_parity(base) != 0u && rs_mode_conv(base) == 0u);
+}
+
+/* Wm of rows of row_bytes bytes */
+RS_OPS_FN unsigned rs_mask_words(unsigned row_bytes) { return (row_bytes + 63u) / 64u; }
+
+/* byte b of a row in the row's mask words */
+RS_OPS_FN int rs_mask_bit(const uint64_t *words, unsigned b) { return (int)((words[b >> 6] >> (b & 63u)) & 1u); }
 
 /* ---- the field ------------------------------------------------------------ */
 
@@ -112,6 +143,12 @@ RS_OPS_FN unsigned rs_frame_bytes(unsigned n, unsigned P) { return n + rs_codewo
 RS_OPS_FN unsigned rs_symbol_offset(unsigned n, unsigned D, unsigned kj, unsigned j, unsigned x)
 {
     return x < kj ? j + x * D : n + (x - kj) * D + j;
+}
+
+/* symbol x of codeword j is flagged: its row byte's bit of the row's mask */
+RS_OPS_FN int rs_symbol_flagged(const uint64_t *words, unsigned n, unsigned D, unsigned kj, unsigned j, unsigned x)
+{
+    return rs_mask_bit(words, rs_symbol_offset(n, D, kj, j, x));
 }
 
 /* ---- the encoder ----------------------------------------------------------- */

@@ -1109,8 +1109,57 @@ int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const 
  *
  * The CRC stays the arbiter of a frame: the check does not read this record.
  *
- * Not here: erasure decoding, passing the Viterbi decoder's reliability to the
- * outer code, protecting the length header, the multi-GPU group, fskrx options.
+ * Erasure decoding. The detector knows which bytes to doubt: in a dropout or a
+ * fade the tones of a window are indistinguishable, the hard symbol is a coin
+ * toss, and the soft value q_m of "coded frames" is near 0. A decoder that is
+ * told where the doubtful bytes are corrects twice as many: with f flagged
+ * bytes in a codeword it corrects e further wrong ones as long as 2 e + f <= P.
+ *
+ * The erasure mask is one bit per row byte. Row r = g max_frames + i has Wm =
+ * ceil(row_bytes / 64) uint64_t words; byte b is bit b & 63 of word b >> 6; the
+ * mask is 8-byte aligned. Bits at b >= row_bytes are written as 0 by the
+ * producer and ignored by the decoder. One wave's ballot over 64 consecutive
+ * row bytes is one word of it.
+ *
+ * The decoder with a mask, again by its result. For codeword j let E be the
+ * positions of the received word r whose row byte is flagged, f = |E|.
+ *   f = 0 or f > P   exactly the rule above (errors only).
+ *   1 <= f <= P      first attempt: if a codeword c of the shortened code has
+ *                    2 |{x not in E : r_x != c_x}| + f <= P it is unique (two
+ *                    such words would differ in at most e1 + e2 + f <= P
+ *                    places); r is replaced by c and e_j is the number of bytes
+ *                    that changed, erased ones included (a flagged byte that
+ *                    was right costs nothing but its share of f). Otherwise the
+ *                    fallback: the rule above on the same word; if that fails
+ *                    too the bytes stay and the codeword counts as failed.
+ * A word with zero syndromes is its own codeword under every branch and is
+ * left as it is whatever the mask holds; it counts in neither `used` nor
+ * `fallback`. The length header is read as it is, as above, and the CRC stays
+ * the arbiter: with f = P any word "decodes". Beside demod_frame_rs_t (its
+ * fields as above) a row has a second record, demod_frame_erase_t:
+ *
+ *   erased    the flagged bytes among the frame's n' bytes
+ *   used      the codewords accepted by the first attempt
+ *   fallback  the codewords with f >= 1 and non-zero syndromes that were
+ *             accepted or failed under the errors-only rule: f > P, or the
+ *             first attempt found nothing
+ *   reserved  0
+ *
+ * all 0 with DEMOD_RS_BAD_LENGTH.
+ *
+ * The level. DEMOD_FEC_ERASE(level), level 1 .. 127, in `fec` asks the one-shot
+ * call and the receiver to flag byte b of a plain row where the least |q_m|
+ * over its eight air bits m = 8 b .. 8 b + 7 is below the level (q_m = 0 for m
+ * >= N bits), and to run the decoder with that mask. It is accepted only
+ * together with a parity flag and low nibble 0 (the Viterbi decoder's own
+ * reliability is not passed on), and only by demod_frames_coded,
+ * demod_rx_create and demod_rx_sizes; every other entry refuses
+ * it as it refuses any unknown bit. The frame on the air is the same: a
+ * transmitter is created with the mode without the field.
+ *
+ * Not here: passing the Viterbi decoder's reliability to the outer code,
+ * retries at several levels, protecting the length header, the multi-GPU
+ * group, fskrx options.
  *
  * Every entry that takes `fec` takes the 20 modes where the frame alone is
  * concerned (the check, the one-shot call, the receiver, the transmitter, the
@@ -1129,6 +1178,12 @@ int demod_frames_coded(demod_t *st, const int16_t *pcm, size_t n_windows, const 
 typedef struct demod_frame_rs {
     uint32_t status, codewords, corrected, failed;
 } demod_frame_rs_t;
+
+#define DEMOD_FEC_ERASE(level)  (((level) & 0x7F) << 16)   /* only with a parity flag and low nibble 0 */
+
+typedef struct demod_frame_erase {
+    uint32_t erased, used, fallback, reserved;
+} demod_frame_erase_t;
 
 /* The host codec; no device needed. `fec` is any of the 20 modes (without a
  * parity flag n' = n and there is nothing to decode); another value is refused
@@ -1154,6 +1209,24 @@ int demod_rs_frame_encode(const uint8_t *data, size_t len, int len_bytes, int cr
                           size_t cap);
 int demod_rs_frame_decode(uint8_t *row, size_t cap, int len_bytes, int crc, int fec, demod_frame_rs_t *out);
 
+/* frame_decode with a mask ("erasure decoding"): the reference of
+ * demod_frames_rs_erasures_async, bit for bit. erase is the row's Wm words of
+ * cap bytes, or NULL for no flags; the row, *out and the return value are then
+ * demod_rs_frame_decode's and *erec is 0. Takes the modes that carry a parity
+ * flag (without a level). DEMOD_BAD_ARG also for a NULL erec or a misaligned
+ * erase (8 bytes). */
+int demod_rs_frame_decode_erasures(uint8_t *row, size_t cap, int len_bytes, int crc, int fec,
+                                   const uint64_t *erase, demod_frame_rs_t *out, demod_frame_erase_t *erec);
+
+/* The mask of one plain row from its soft values in air order (demod_soft_bits
+ * of each window, n_soft = N bits of them): byte b < row_bytes is flagged iff
+ * the least |soft[m]| over m = 8 b .. 8 b + 7 is below level, soft[m] = 0 for m
+ * >= n_soft. Writes the Wm words of row_bytes bytes and returns Wm; with
+ * demod_soft_bits the reference of demod_frames_erasures_async.
+ * DEMOD_BAD_ARG for a NULL pointer, a misaligned erase (8 bytes), a level
+ * outside 1 .. 127, row_bytes 0 or >= 2^31. */
+int demod_soft_erasures(const int8_t *soft, size_t n_soft, int level, uint64_t *erase, size_t row_bytes);
+
 /*
  * The device stage, between the scan (low nibble 0: over its d_packed) or
  * demod_frames_decode_async (a coded mode: over its d_rows) and
@@ -1173,6 +1246,46 @@ int demod_rs_frame_decode(uint8_t *row, size_t cap, int len_bytes, int crc, int 
 int demod_frames_rs_async(demod_t *st, uint8_t *d_rows, const demod_frames_result_t *d_results,
                           size_t n_groups, size_t max_frames, size_t frame_symbols, int len_bytes, int crc,
                           int fec, demod_frame_rs_t *d_rs, void *stream);
+
+/*
+ * The mask's producer, behind either scan over plain (uncoded) rows. Enqueued
+ * on `stream`: one launch, no workspace, no atomics, nothing allocated or
+ * synchronised, capturable behind the scan. One thread per row byte; air bit m
+ * of a row is the soft value q_m of "coded frames" with a = m: the same window
+ * arithmetic (d_first NULL or the segmented scan's table), maxima and double
+ * expression, no wrap-around; a hit's window, or a symbol's, at or past
+ * n_windows gives 0 and is not read, m >= N bits gives 0. d_erase is
+ * [n_groups][max_frames][Wm] words, Wm of B = ceil(N bits / 8) bytes; every
+ * word of every row i < nw_g is written, no other row is touched. The counts
+ * are read and clamped on the device. Returns DEMOD_OK once enqueued;
+ * DEMOD_BAD_ARG, before the launch, for a NULL pointer (d_first may be), a
+ * misaligned d_hits, d_results, d_first or d_erase (8 bytes), K not 2, 4, 8 or
+ * 16, a level outside 1 .. 127, what demod_frames_check_async refuses about
+ * the configuration, the groups and rows and sync_len, frame_symbols 0 or B
+ * above 4710 (the widest row any mode with a parity flag takes); also
+ * n_windows >= 2^31 and (sync_len + frame_symbols) R >= 2^31.
+ */
+int demod_frames_erasures_async(demod_t *st, const demod_frame_hit_t *d_hits, const float *d_mags,
+                                size_t n_windows, const uint64_t *d_first,
+                                const demod_frames_result_t *d_results, size_t n_groups, size_t max_frames,
+                                size_t sync_len, size_t frame_symbols, int level, uint64_t *d_erase,
+                                void *stream);
+
+/*
+ * demod_frames_rs_async with a mask: the decoder of "erasure decoding" on the
+ * rows, in place. d_erase is [n_groups][max_frames][Wm] words, Wm of the row
+ * width (B, or Bd in a coded mode: a caller with a reliability of their own can
+ * run it behind the Viterbi decode), d_erec [n_groups][max_frames]. Launch,
+ * rows, counts and what is written as demod_frames_rs_async, and every byte of
+ * the d_erec records of rows i < nw_g. An all-zero mask gives exactly
+ * demod_frames_rs_async's rows and records. Takes the modes with a parity flag
+ * (without a level); refuses what demod_frames_rs_async refuses, a NULL d_erase
+ * or d_erec, a misaligned d_erase (8 bytes) or d_erec (4 bytes).
+ */
+int demod_frames_rs_erasures_async(demod_t *st, uint8_t *d_rows, const uint64_t *d_erase,
+                                   const demod_frames_result_t *d_results, size_t n_groups, size_t max_frames,
+                                   size_t frame_symbols, int len_bytes, int crc, int fec,
+                                   demod_frame_rs_t *d_rs, demod_frame_erase_t *d_erec, void *stream);
 
 /* ---- many streams, one launch (config 5 as a service) ----------------- */
 /*
