@@ -21,6 +21,13 @@ import math
 
 import numpy as np
 
+# demod_acquire_result_t, restated from the header: the one layout the tests read results with
+RESULT_DTYPE = np.dtype([("metric", "<f8", 64), ("phases", "<u4"), ("phase", "<u4"),
+                         ("per_phase", "<u8"), ("sync_window", "<i8"), ("sync_errors", "<u4"),
+                         ("reserved", "<u4"), ("first_window", "<u8"), ("n_out", "<u8"),
+                         ("n_written", "<u8")])
+assert RESULT_DTYPE.itemsize == 568
+
 
 def phase_metric(sym, P, R):
     sym = np.asarray(sym, np.uint8).reshape(-1)
@@ -113,3 +120,32 @@ def case_stream(O, name, tau):
     if tau:
         return np.ascontiguousarray(x[n - tau:]), truth[1:]
     return np.ascontiguousarray(x), truth
+
+
+# ---- test-made inputs (tests/test_gpu_acquire.py, tests/test_gpu_acquire_segments.py) -------
+
+def make_inputs(W, K, Rn, seed, boost=None, flat=False):
+    """sym random < K; P random positive fp32 over 1e0 .. 1e14, phase `boost`'s
+    powers scaled by 1.5. flat: every tone of a window the same power, so the
+    metric does not depend on the symbols (the sync tests plant symbols)."""
+    rng = np.random.default_rng(seed)
+    sym = rng.integers(0, K, W).astype(np.uint8)
+    P = (10.0 ** rng.uniform(0.0, 14.0, (W, 1 if flat else K))).astype(np.float32)
+    if flat:
+        P = np.repeat(P, K, axis=1)
+    if boost is not None:
+        P[boost::Rn] *= np.float32(1.5)
+    return sym, np.ascontiguousarray(P)
+
+
+def plant(sym, Rn, w0, word, n_bad, K, rng):
+    """word on sym[w0 :: Rn] with exactly n_bad mismatching positions, each
+    another symbol < K (K >= 2), so that with tone-independent powers the
+    metric stays what it was."""
+    assert K >= 2 or n_bad == 0
+    s = sym.copy()
+    L = len(word)
+    s[w0:w0 + L * Rn:Rn] = word
+    for pos in rng.choice(L, n_bad, replace=False):
+        s[w0 + pos * Rn] = (int(word[pos]) + 1 + int(rng.integers(0, K - 1))) % K
+    return s

@@ -12,6 +12,11 @@ A mode is decoded by re-ordering the air soft values into a rate-1/2 trellis
 array of 2 St values, zeros at the punctured positions, and handing that to
 the existing tests/frames_fec_ref.py decoder: the decoder the earlier tests
 hold to a maximum-likelihood reference is the oracle here too.
+
+span, row_shape and symbols_for take any `fec` the stages take: 0 or a mode in
+the low byte, with or without a parity flag of the outer code (tests/rs_ref.py).
+They are the one span, row shape and row size of the check references, of
+tests/rx_ref.py and of tests/rs_chain_ref.py.
 """
 import functools
 
@@ -19,6 +24,7 @@ import numpy as np
 
 import frames_check_ref as C
 import frames_fec_ref as X
+import rs_ref as R
 
 CONV_K7, RATE_2_3, RATE_3_4, INTERLEAVE = 1, 0x10, 0x20, 0x40
 BLOCK = 256
@@ -74,9 +80,20 @@ def air_bits(fec, T):
     return -(-n // BLOCK) * BLOCK if fec & INTERLEAVE else n
 
 
-def frame_symbols(length, h, kind, bits, fec):
-    """Sc of the mode."""
-    return -(-air_bits(fec, X.steps(length, h, kind)) // bits)
+def span(length, bits, h, kind, fec):
+    """The symbols a frame of `length` data bytes occupies behind its word, in
+    every mode: fec's low byte 0 or one of MODES, with or without a parity flag
+    of the outer code (rs_ref). Its n' bytes' bits; with the convolutional code
+    the Na air bits of its T = max(8 n' + 6, 8 h + 64) steps."""
+    n = R.frame_size(h + length + C.CRC_BYTES[kind], R.mode_parity(fec))
+    conv = fec & 0xFF
+    air = air_bits(conv, max(8 * n + 6, 8 * h + X.DEPTH)) if conv else 8 * n
+    return -(-air // bits)
+
+
+def span_of(bits, h, kind, fec):
+    """span of the mode as a function of the length: what frames_check_ref.check_group takes."""
+    return lambda length: span(length, bits, h, kind, fec)
 
 
 def encode_air(info, T, fec):
@@ -97,24 +114,33 @@ def encode(data, h, kind, fec):
 
 
 def row_shape(N, bits, h, kind, fec):
-    """(St, Bd, max_len) of rows of N symbols, or None where the row is refused."""
-    Cc = N * bits
-    St = steps_within(fec, Cc // BLOCK * BLOCK if fec & INTERLEAVE else Cc)
-    if St < 8 * h + X.DEPTH:
-        return None
-    Bd = (St - 6) // 8
-    max_len = Bd - h - C.CRC_BYTES[kind]
+    """(St, W, max_len) of rows of N symbols, or None where the row is refused:
+    W = B packed bytes and St = 0 without the convolutional code, else St steps
+    that decode to W = Bd bytes; max_len the greatest len whose n' fits W."""
+    Cc, conv = N * bits, fec & 0xFF
+    St, W = 0, (Cc + 7) // 8
+    if conv:
+        St = steps_within(conv, Cc // BLOCK * BLOCK if conv & INTERLEAVE else Cc)
+        if St < 8 * h + X.DEPTH:
+            return None
+        W = (St - 6) // 8
+    max_len = R.max_len(W, h, C.CRC_BYTES[kind], R.mode_parity(fec))
     if max_len < 0 or max_len > 4096:
         return None
-    return St, Bd, max_len
+    return St, W, max_len
 
 
-def symbols_for(max_len, bits, h, kind, fec):
-    """The smallest N whose rows hold frames of max_len data bytes."""
-    N = frame_symbols(max_len, h, kind, bits, fec)
-    while row_shape(N, bits, h, kind, fec) is None or row_shape(N, bits, h, kind, fec)[2] < max_len:
-        N += 1
-    return N
+def symbols_for(most, bits, h, kind, fec):
+    """The smallest N whose rows hold frames of `most` data bytes and all their
+    symbols. Where no row does (near the payload limit a row that holds `most`
+    can hold more than 4096 and is refused) that is an error, not a search
+    without end: a fitting row lies within two blocks and a byte of the span."""
+    first = span(most, bits, h, kind, fec)
+    for N in range(first, first + 2 * BLOCK + 8):
+        shape = row_shape(N, bits, h, kind, fec)
+        if shape is not None and shape[2] >= most:
+            return N
+    raise ValueError("no row of the mode holds frames of %d data bytes" % most)
 
 
 def trellis_soft(soft, fec):
@@ -149,39 +175,3 @@ def edge_lengths(max_len, h, kind, fec):
     for want in (255, 0, 1):
         out.add(min(range(max_len + 1), key=lambda n: min((res[n] - want) % BLOCK, (want - res[n]) % BLOCK)))
     return sorted(out)
-
-
-def scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames=None):
-    """rx_ref.scan_check, which takes a mode: the scan of (sym, P) as one
-    segment, the mode's decode of its rows and the coded check with the mode's span."""
-    import rx_ref as RX
-    return RX.scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames)
-
-
-def receiver(S, K, R, sync, max_errors, N, h, kind, fec, max_frames, ring):
-    """rx_ref.Rx, which takes a mode."""
-    import rx_ref as RX
-    return RX.Rx(S, K, R, sync, max_errors, N, h, kind, fec, max_frames, ring)
-
-
-def check_group(windows, rows, L, R, bits, h, kind, fec):
-    """frames_fec_ref.check_group with the mode's span Sc."""
-    nw = len(windows)
-    check = np.zeros(nw, C.CHECK_DTYPE)
-    kept, bodies = [], []
-    reach = 0
-    for i in range(nw):
-        length, got, status = C.check_row(rows[i], h, kind)
-        covered = 0
-        if status == C.OK:
-            w = int(windows[i])
-            covered = int(reach > w)
-            reach = max(reach, (w + (L + frame_symbols(length, h, kind, bits, fec)) * R) & C.M64)
-            if not covered:
-                kept.append(i)
-                bodies.append(bytes(rows[i][h:h + length]))
-        check[i] = (length, got, status, covered)
-    summary = np.zeros((), C.SUMMARY_DTYPE)
-    summary["n_checked"], summary["n_valid"] = nw, int((check["status"] == C.OK).sum())
-    summary["n_kept"] = len(kept)
-    return check, np.array(kept, np.uint32), bodies, summary

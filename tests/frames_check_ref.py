@@ -20,6 +20,11 @@ ceil((h + len + c) 8 / bits). Per group of rows (ascending windows):
   kept      OK and not covered; the kept rows' indices ascending, and their
             data bytes.
   summary   (rows, rows OK, rows kept, 0).
+
+check_group is the one copy of that loop, for the rows of every mode: the
+caller hands it S as a function of len (fec_modes_ref.span_of: the coded
+modes' and the outer code's spans are other functions of len) and, where the
+row is not a plain packed one, the length bound in place of B - h - c.
 """
 import numpy as np
 
@@ -83,40 +88,42 @@ def payload_row(frame, N, bits, rng, K=None):
     return row
 
 
-def check_row(row, len_bytes, kind):
-    """(length, crc, status) of one packed row."""
+def check_row(row, len_bytes, kind, most=None):
+    """(length, crc, status) of one row; `most` is the length bound, None for
+    a packed row's own len(row) - len_bytes - c."""
     row = bytes(row)
     c = CRC_BYTES[kind]
-    max_len = len(row) - len_bytes - c
-    assert max_len >= 0
+    if most is None:
+        most = len(row) - len_bytes - c
+    assert most >= 0
     length = int.from_bytes(row[:len_bytes], "big")
-    if length > max_len:
+    if length > most:
         return length, 0, BAD_LENGTH
     n = len_bytes + length
     got = crc(kind, row[:n])
     return length, got, OK if got == int.from_bytes(row[n:n + c], "big") else BAD_CRC
 
 
-def check_group(windows, rows, L, R, bits, len_bytes, kind):
-    """One group's rows (windows [nw], rows uint8 [nw][B]). Returns (check
-    CHECK_DTYPE [nw], kept uint32 [n_kept], bodies: the kept rows' data bytes,
-    summary SUMMARY_DTYPE scalar)."""
+def check_group(windows, rows, L, R, span, most, h, kind):
+    """One group's rows (windows [nw], rows uint8 [nw][W]): the one copy of the
+    loop. span(length) gives the symbols a frame of `length` data bytes
+    occupies behind its word (fec_modes_ref.span_of a mode); `most` is
+    check_row's. Returns (check CHECK_DTYPE [nw], kept uint32 [n_kept], bodies:
+    the kept rows' data bytes, summary SUMMARY_DTYPE scalar)."""
     nw = len(windows)
-    c = CRC_BYTES[kind]
     check = np.zeros(nw, CHECK_DTYPE)
     kept, bodies = [], []
     reach = 0          # max end over the OK rows so far
     for i in range(nw):
-        length, got, status = check_row(rows[i], len_bytes, kind)
+        length, got, status = check_row(rows[i], h, kind, most)
         covered = 0
         if status == OK:
             w = int(windows[i])
             covered = int(reach > w)
-            end = (w + (L + frame_symbols(len_bytes + length + c, bits)) * R) & M64
-            reach = max(reach, end)
+            reach = max(reach, (w + (L + span(length)) * R) & M64)
             if not covered:
                 kept.append(i)
-                bodies.append(bytes(rows[i][len_bytes:len_bytes + length]))
+                bodies.append(bytes(rows[i][h:h + length]))
         check[i] = (length, got, status, covered)
     summary = np.zeros((), SUMMARY_DTYPE)
     summary["n_checked"], summary["n_valid"] = nw, int((check["status"] == OK).sum())
@@ -124,12 +131,12 @@ def check_group(windows, rows, L, R, bits, len_bytes, kind):
     return check, np.array(kept, np.uint32), bodies, summary
 
 
-def check_groups(hits, packed, n_written, max_frames, L, R, bits, len_bytes, kind):
-    """hits HIT_DTYPE [G][max_frames], packed uint8 [G][max_frames][B],
-    n_written [G] as stored (clamped to max_frames here). One check_group
-    result per group."""
+def check_groups(hits, rows, n_written, max_frames, L, R, span, most, h, kind):
+    """hits HIT_DTYPE [G][max_frames], rows uint8 [G][max_frames][W], n_written
+    [G] as stored (clamped to max_frames here). One check_group result per
+    group."""
     out = []
     for g, n in enumerate(n_written):
         nw = min(int(n), max_frames)
-        out.append(check_group(hits[g]["window"][:nw], packed[g][:nw], L, R, bits, len_bytes, kind))
+        out.append(check_group(hits[g]["window"][:nw], rows[g][:nw], L, R, span, most, h, kind))
     return out

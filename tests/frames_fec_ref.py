@@ -65,14 +65,6 @@ def row_shape(N, bits, h, kind):
     return St, Bd, max_len
 
 
-def symbols_for(max_len, bits, h, kind):
-    """The smallest N whose rows hold frames of max_len data bytes."""
-    N = (2 * (8 * (h + max_len + C.CRC_BYTES[kind]) + 6) + bits - 1) // bits
-    while row_shape(N, bits, h, kind) is None or row_shape(N, bits, h, kind)[2] < max_len:
-        N += 1
-    return N
-
-
 def encode_bits(info, T):
     """The 2 T coded bits of the information bytes `info`, one per element."""
     u = np.unpackbits(np.frombuffer(bytes(info), np.uint8))
@@ -203,26 +195,3 @@ def hard_soft(bits01, rng=None, tail=0):
     if tail:
         q = np.concatenate([q, rng.integers(-127, 128, tail).astype(np.int8)])
     return q
-
-
-def check_group(windows, rows, L, R, bits, h, kind):
-    """frames_check_ref.check_group with the coded span S = ceil(2 T(len) / bits)."""
-    nw = len(windows)
-    check = np.zeros(nw, C.CHECK_DTYPE)
-    kept, bodies = [], []
-    reach = 0
-    for i in range(nw):
-        length, got, status = C.check_row(rows[i], h, kind)
-        covered = 0
-        if status == C.OK:
-            w = int(windows[i])
-            covered = int(reach > w)
-            reach = max(reach, (w + (L + coded_symbols(length, h, kind, bits)) * R) & C.M64)
-            if not covered:
-                kept.append(i)
-                bodies.append(bytes(rows[i][h:h + length]))
-        check[i] = (length, got, status, covered)
-    summary = np.zeros((), C.SUMMARY_DTYPE)
-    summary["n_checked"], summary["n_valid"] = nw, int((check["status"] == C.OK).sum())
-    summary["n_kept"] = len(kept)
-    return check, np.array(kept, np.uint32), bodies, summary

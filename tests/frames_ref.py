@@ -21,6 +21,11 @@ import numpy as np
 import acquire_ref
 
 HIT_DTYPE = np.dtype([("window", "<u8"), ("errors", "<u4"), ("reserved", "<u4")])
+# demod_frames_result_t, restated from the header: the one layout the tests build and read results with
+RESULT_DTYPE = np.dtype([("metric", "<f8", 64), ("phases", "<u4"), ("phase", "<u4"), ("per_phase", "<u8"),
+                         ("n_hits", "<u8"), ("n_written", "<u8"), ("tail_window", "<i8"),
+                         ("tail_errors", "<u4"), ("reserved", "<u4")])
+assert RESULT_DTYPE.itemsize == 560
 
 
 def bits_per_symbol(K):

@@ -2,12 +2,14 @@
 tests (tests/test_gpu_rs.py): the scan of (sym, P) by tests/frames_ref.py, the
 soft values by tests/frames_fec_ref.py, then the library's host functions
 demod_fec_frame_decode (the Viterbi part), demod_rs_frame_decode (the outer
-code) and the check, whose length bound and span follow n'. Also the symbol
+code) and the check of tests/frames_check_ref.py with the length bound that
+follows n' and the span of tests/fec_modes_ref.py. Also the symbol
 streams these tests send: frames in any of the 20 modes from
 demod_tx_frame_symbols, with wrong symbols planted.
 """
 import numpy as np
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as X
 import frames_ref as F
@@ -21,25 +23,6 @@ def row_width(A, N, bits, h, fec):
 
 def max_len(A, N, bits, h, kind, fec):
     return R.max_len(row_width(A, N, bits, h, fec), h, C.CRC_BYTES[kind], R.mode_parity(fec))
-
-
-def symbols_for(A, most, bits, h, kind, fec):
-    """The smallest N whose rows hold frames of `most` data bytes and all their symbols."""
-    N = span(A, most, bits, h, kind, fec)
-    while True:
-        try:
-            if max_len(A, N, bits, h, kind, fec) >= most:
-                return N
-        except A.DemodError:
-            pass
-        N += 1
-
-
-def span(A, length, bits, h, kind, fec):
-    """The symbols a frame of `length` data bytes occupies behind its word."""
-    if fec & 0xFF:
-        return A.fec_frame_symbols(length, h, kind, bits, fec)
-    return (8 * R.frame_size(h + length + C.CRC_BYTES[kind], R.mode_parity(fec)) + bits - 1) // bits
 
 
 def rows_of(A, sym, P, hits, L, Rn, N, h, kind, fec, poison=0):
@@ -72,31 +55,6 @@ def outer(A, rows, h, kind, fec):
     return out, rec
 
 
-def check_group(A, windows, rows, L, Rn, bits, h, kind, fec, most):
-    """frames_check_ref.check_group with the length bound `most` and the span
-    of the mode: (check, kept, bodies, summary)."""
-    nw, c = len(windows), C.CRC_BYTES[kind]
-    check = np.zeros(nw, C.CHECK_DTYPE)
-    kept, bodies, reach = [], [], 0
-    for i in range(nw):
-        row = bytes(rows[i])
-        length = int.from_bytes(row[:h], "big")
-        got, status, covered = 0, C.BAD_LENGTH, 0
-        if length <= most:
-            got = C.crc(kind, row[:h + length])
-            status = C.OK if got == int.from_bytes(row[h + length:h + length + c], "big") else C.BAD_CRC
-        if status == C.OK:
-            w = int(windows[i])
-            covered = int(reach > w)
-            reach = max(reach, (w + (L + span(A, length, bits, h, kind, fec)) * Rn) & C.M64)
-            if not covered:
-                kept.append(i)
-                bodies.append(row[h:h + length])
-        check[i] = (length, got, status, covered)
-    summary = dict(n_checked=nw, n_valid=int((check["status"] == C.OK).sum()), n_kept=len(kept), reserved=0)
-    return check, np.array(kept, np.uint32), bodies, summary
-
-
 def chain(A, sym, P, Rn, word, max_errors, N, h, kind, fec):
     """Scan, decode, outer decode, check on one batch: (hits, rows before the
     outer code, rows after, records, check_group's four, the scan's result)."""
@@ -104,7 +62,8 @@ def chain(A, sym, P, Rn, word, max_errors, N, h, kind, fec):
     bits = F.bits_per_symbol(P.shape[1])
     before = rows_of(A, np.asarray(sym, np.uint8), P, hits, len(word), Rn, N, h, kind, fec)
     after, rec = outer(A, before, h, kind, fec)
-    chk = check_group(A, hits["window"], after, len(word), Rn, bits, h, kind, fec, max_len(A, N, bits, h, kind, fec))
+    chk = C.check_group(hits["window"], after, len(word), Rn, Z.span_of(bits, h, kind, fec),
+                        max_len(A, N, bits, h, kind, fec), h, kind)
     return hits, before, after, rec, chk, res
 
 

@@ -1,8 +1,8 @@
 """Numpy restatement of the receiver (include/demod.h "receiver"): the reference
 of tests/test_rx_cpu.py and tests/test_gpu_rx.py, composed from
-frames_segments_ref (the scan of X as one segment), frames_check_ref (the plain
-check), frames_fec_ref (soft values) and fec_modes_ref (row shape, decode, span
-and the coded check of every coded mode; mode 1 is the rate-1/2 code).
+frames_segments_ref (the scan of X as one segment), frames_check_ref (the
+check of a group's rows), frames_fec_ref (soft values) and fec_modes_ref (row
+shape, decode and span of every mode; mode 1 is the rate-1/2 code).
 
 fec is 0 or a coded mode (fec_modes_ref.MODES) everywhere: span(), sizes(),
 row_symbols() and scan_check() are the one place that turns it into a span, a
@@ -43,19 +43,12 @@ FRAME_DTYPE = np.dtype([("stream", "<u4"), ("length", "<u4"), ("window", "<u8"),
 STATE_DTYPE = np.dtype([("base", "<u8"), ("hold", "<u8"), ("dropped", "<u8"), ("cut_hits", "<u8"),
                         ("fill", "<u4"), ("keep", "<u4")])
 SUMMARY_DTYPE = np.dtype([("n_frames", "<u8"), ("n_bytes", "<u8"), ("n_checked", "<u8"), ("n_valid", "<u8")])
-RESULT_DTYPE = np.dtype([("metric", "<f8", (64,)), ("phases", "<u4"), ("phase", "<u4"), ("per_phase", "<u8"),
-                         ("n_hits", "<u8"), ("n_written", "<u8"), ("tail_window", "<i8"),
-                         ("tail_errors", "<u4"), ("reserved", "<u4")])       # demod_frames_result_t
+RESULT_DTYPE = F.RESULT_DTYPE          # demod_frames_result_t
 M64 = C.M64
 assert FRAME_DTYPE.itemsize == 32 and STATE_DTYPE.itemsize == 40 and SUMMARY_DTYPE.itemsize == 32
-assert RESULT_DTYPE.itemsize == 560
 
 
-def span(length, bits, h, kind, fec):
-    """S: the symbols a frame of `length` data bytes occupies behind its word."""
-    if fec:
-        return Z.frame_symbols(length, h, kind, bits, fec)
-    return C.frame_symbols(h + length + C.CRC_BYTES[kind], bits)
+span = Z.span          # S: the symbols a frame of `length` data bytes occupies behind its word
 
 
 def min_ring(L, N, R):
@@ -172,8 +165,9 @@ def scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames=None):
     K, L = P.shape[1], len(sync)
     bits = F.bits_per_symbol(K)
     hits, _, packed, res = FS.frames_segments(sym, P, R, [0], [sym.size], sync, max_errors, N, max_frames)[0]
+    group = lambda rows: C.check_group(hits["window"], rows, L, R, Z.span_of(bits, h, kind, fec), None, h, kind)
     if not fec:
-        return (hits,) + C.check_group(hits["window"], packed, L, R, bits, h, kind) + (res,)
+        return (hits,) + group(packed) + (res,)
     _, Bd, _ = Z.row_shape(N, bits, h, kind, fec)
     rows = np.zeros((len(hits), Bd), np.uint8)
     if len(hits):
@@ -182,7 +176,7 @@ def scan_check(sym, P, R, sync, max_errors, N, h, kind, fec, max_frames=None):
         written, _ = Z.decode_rows(q, h, kind, fec)
         for i, b in enumerate(written):
             rows[i, :len(b)] = np.frombuffer(b, np.uint8)
-    return (hits,) + Z.check_group(hits["window"], rows, L, R, bits, h, kind, fec) + (res,)
+    return (hits,) + group(rows) + (res,)
 
 
 def one_shot(sym, P, R, sync, max_errors, N, h, kind, fec):
@@ -255,9 +249,7 @@ class Rx:
 
 def row_symbols(h, kind, fec, bits, max_len):
     """The smallest N whose rows hold frames of max_len data bytes."""
-    if fec:
-        return Z.symbols_for(max_len, bits, h, kind, fec)
-    return C.frame_symbols(h + max_len + C.CRC_BYTES[kind], bits)
+    return Z.symbols_for(max_len, bits, h, kind, fec)
 
 
 def frame_symbols(data, word, bits, h, kind, fec):

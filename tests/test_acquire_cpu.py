@@ -15,11 +15,10 @@ def test_exports_and_result_struct(A):
         assert hasattr(lib, name), name
         assert name in A.header_exports()
     T = A.DemodAcquireResult
-    assert ctypes.sizeof(T) == 64 * 8 + 56
-    assert T.metric.offset == 0 and T.phases.offset == 512 and T.phase.offset == 516
-    assert T.per_phase.offset == 520 and T.sync_window.offset == 528
-    assert T.sync_errors.offset == 536 and T.reserved.offset == 540
-    assert (T.first_window.offset, T.n_out.offset, T.n_written.offset) == (544, 552, 560)
+    assert ctypes.sizeof(T) == R.RESULT_DTYPE.itemsize and [f for f, _ in T._fields_] == list(R.RESULT_DTYPE.names)
+    for f in R.RESULT_DTYPE.names:                                  # every field where the tests' one dtype has it
+        at, size = R.RESULT_DTYPE.fields[f][1], R.RESULT_DTYPE[f].itemsize
+        assert (getattr(T, f).offset, getattr(T, f).size) == (at, size), f
     assert A.DEMOD_MAX_PHASES == 64 and A.DEMOD_MAX_SYNC == 64
     hdr = open(A.HEADER_PATH).read()
     assert "#define DEMOD_ACQUIRE_TILE %d" % A.ACQUIRE_TILE in hdr

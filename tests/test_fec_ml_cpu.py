@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import fec_ml_ref as ML
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as X
 
@@ -26,7 +27,7 @@ H2 = (2, C.CRC32, 24)           # 246 steps
 
 def n_soft(h, kind, max_len):
     """C of the smallest row of one soft value a symbol that holds max_len data bytes."""
-    return X.symbols_for(max_len, 1, h, kind)
+    return Z.symbols_for(max_len, 1, h, kind, X.CONV_K7)
 
 
 # ---- the input families: int8 soft values [n][C] --------------------------------------
@@ -267,7 +268,7 @@ def longest_negated(rng):
     the row's verdict does not hang on the decoder's tie rule. Returns (q int8
     [C], h, kind)."""
     h, kind = 2, C.CRC32
-    Cs = X.symbols_for(4096, 1, h, kind)
+    Cs = Z.symbols_for(4096, 1, h, kind, X.CONV_K7)
     info = C.encode(rng.integers(0, 256, 4095).astype(np.uint8).tobytes(), h, kind)
     T = Cs // 2
     q = -X.hard_soft(X.encode_bits(bytes(b ^ 0xFF for b in info) + b"\xff" * ((T + 7) // 8 - len(info)), T))

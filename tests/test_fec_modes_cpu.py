@@ -63,7 +63,7 @@ def test_map(A, fec):
             for bits in (1, 2, 3, 4):
                 for length in (0, 1, 5, 6, 38, 255):
                     assert A.fec_frame_symbols(length, h, kind, bits, fec) == \
-                        Z.frame_symbols(length, h, kind, bits, fec)
+                        Z.span(length, bits, h, kind, fec)
                 for N in range(86, 400, 7):
                     shape = Z.row_shape(N, bits, h, kind, fec)
                     St = Z.steps_within(fec, N * bits // Z.BLOCK * Z.BLOCK if fec & Z.INTERLEAVE else N * bits)
@@ -274,7 +274,7 @@ def test_refusals(A):
         assert A.rx_sizes(cfg2, A.make_rx_cfg(fec=fec, **rx_base), 2)["decode_work_bytes"] == \
             A.fec_decode_workspace_size(cfg2, 2, 4, 600, fec)
         assert A.tx_sizes(cfg2, A.make_tx_cfg(fec=fec, **tx_base), 2)["max_symbols"] == \
-            5 + Z.frame_symbols(16, 1, C.CRC16, 1, fec)
+            5 + Z.span(16, 1, 1, C.CRC16, fec)
     for fec in Z.BAD_MODES:
         assert lib.demod_fec_air_index(fec, 0) == A.DEMOD_BAD_ARG
         assert lib.demod_fec_frame_symbols(0, 1, C.CRC16, 1, fec) == A.DEMOD_BAD_ARG

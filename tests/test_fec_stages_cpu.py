@@ -38,7 +38,8 @@ def test_modes_0_and_1_are_unchanged():
                     assert RX.span(length, bits, h, kind, 1) == X.coded_symbols(length, h, kind, bits)
                 for max_len in (0, 3, 7, 40):
                     assert RX.row_symbols(h, kind, 0, bits, max_len) == C.frame_symbols(h + max_len + c, bits)
-                    assert RX.row_symbols(h, kind, 1, bits, max_len) == X.symbols_for(max_len, bits, h, kind)
+                    assert RX.row_symbols(h, kind, 1, bits, max_len) == \
+                        min(N for N in range(1, 800) if (X.row_shape(N, bits, h, kind) or (0, 0, -1))[2] >= max_len)
                 for N in range(150 // bits, 420, 13):
                     assert Z.row_shape(N, bits, h, kind, 1) == X.row_shape(N, bits, h, kind)
                     if X.row_shape(N, bits, h, kind) is None:
@@ -72,12 +73,12 @@ def test_sizes_every_mode(A, fec):
 def test_spans_of_the_modes():
     """The spans the fixtures rely on, counted: 40- and 30-byte frames at 1 bit
     a symbol (h 1, CRC-16), and one block at 3 bits ending inside a symbol."""
-    assert [Z.frame_symbols(40, 1, C.CRC16, 1, f) for f in Z.MODES] == [700, 525, 467, 768, 768, 512]
-    assert [Z.frame_symbols(30, 1, C.CRC16, 1, f) for f in Z.MODES] == [540, 405, 360, 768, 512, 512]
-    assert Z.frame_symbols(0, 1, C.CRC16, 3, 0x41) == 86
+    assert [Z.span(40, 1, 1, C.CRC16, f) for f in Z.MODES] == [700, 525, 467, 768, 768, 512]
+    assert [Z.span(30, 1, 1, C.CRC16, f) for f in Z.MODES] == [540, 405, 360, 768, 512, 512]
+    assert Z.span(0, 3, 1, C.CRC16, 0x41) == 86
     for f in Z.MODES:
         for n in (0, 30, 40):
-            assert RX.span(n, 1, 1, C.CRC16, f) == Z.frame_symbols(n, 1, C.CRC16, 1, f)
+            assert RX.span(n, 1, 1, C.CRC16, f) == Z.span(n, 1, 1, C.CRC16, f)
 
 
 def test_receiver_takes_a_mode():
@@ -99,7 +100,7 @@ def test_receiver_takes_a_mode():
     fr, bodies, summ = rx.push([(sym, P)])
     assert bodies == [a, b] and fr["window"].tolist() == [1 + 7 * R, 1 + (7 + len(fa)) * R]
     assert int(rx.state["hold"][0]) == 1 + (7 + len(fa) + len(fb)) * R
-    assert Z.receiver(1, K, R, word, 0, N, h, kind, fec, 8, len(sym) + 64).push([(sym, P)])[1] == bodies
+    assert RX.Rx(1, K, R, word, 0, N, h, kind, fec, 8, len(sym) + 64).push([(sym, P)])[1] == bodies
     assert RX.one_shot(sym, P, R, word, 0, N, h, kind, fec) == [(int(f["window"]), 0, d) for f, d in zip(fr, bodies)]
 
 
@@ -119,10 +120,11 @@ def test_check_fixture(fec, K, Rn, h, kind):
     gives what it is named for; at least four rows covered and four kept."""
     case = TS.check_case(fec, K, Rn, h, kind)
     bits, gaps = case["bits"], case["gaps"]
-    chk, kept, bodies, summ = Z.check_group(case["hits"]["window"][0, :case["counts"][0]],
-                                            case["rows"][0, :case["counts"][0]], TS.L0, Rn, bits, h, kind, fec)
+    chk, kept, bodies, summ = C.check_group(case["hits"]["window"][0, :case["counts"][0]],
+                                            case["rows"][0, :case["counts"][0]], TS.L0, Rn,
+                                            Z.span_of(bits, h, kind, fec), None, h, kind)
     cov = chk["covered"]
-    own = group_under(case, 0, Rn, h, kind, lambda n: Z.frame_symbols(n, h, kind, bits, fec))
+    own = group_under(case, 0, Rn, h, kind, lambda n: Z.span(n, bits, h, kind, fec))
     assert np.array_equal(own, cov)
     assert int(cov.sum()) >= 4 and len(kept) >= 4 and len(kept) + int(cov.sum()) == int(summ["n_valid"])
     for i, gap in enumerate(gaps):
@@ -136,7 +138,7 @@ def test_check_fixture(fec, K, Rn, h, kind):
     names = set()
     for n in case["lens"]:
         for name, alt in TS.alt_spans(n, bits, h, kind, fec).items():
-            if alt != Z.frame_symbols(n, h, kind, bits, fec):
+            if alt != Z.span(n, bits, h, kind, fec):
                 names.add(name)
     if fec == 0x01:
         assert not names                                  # the control: every alternative is its own span
@@ -156,10 +158,10 @@ def test_check_fixture_tells_0x41_from_0x51():
     K, Rn, h, kind = 2, 1, 1, C.CRC16
     for fec, other in ((0x41, 0x51), (0x51, 0x41)):
         case = TS.check_case(fec, K, Rn, h, kind)
-        assert Z.frame_symbols(40, h, kind, 1, fec) == Z.frame_symbols(40, h, kind, 1, other)
-        assert any(Z.frame_symbols(n, h, kind, 1, fec) != Z.frame_symbols(n, h, kind, 1, other) for n in case["lens"])
-        a = group_under(case, 0, Rn, h, kind, lambda n: Z.frame_symbols(n, h, kind, 1, fec))
-        b = group_under(case, 0, Rn, h, kind, lambda n: Z.frame_symbols(n, h, kind, 1, other))
+        assert Z.span(40, 1, h, kind, fec) == Z.span(40, 1, h, kind, other)
+        assert any(Z.span(n, 1, h, kind, fec) != Z.span(n, 1, h, kind, other) for n in case["lens"])
+        a = group_under(case, 0, Rn, h, kind, lambda n: Z.span(n, 1, h, kind, fec))
+        b = group_under(case, 0, Rn, h, kind, lambda n: Z.span(n, 1, h, kind, other))
         assert not np.array_equal(a, b)
 
 
@@ -233,7 +235,7 @@ def test_collect_bites(fec, monkeypatch):
     c = TR.collect_case(S, mf, K, fec, TR.collect_seed(S, mf, K, fec), TR.MODE_LEN)
     right = TR.collect_reference(c, fec)[0]
     names = [k for k, v in TS.alt_spans(TR.MODE_LEN, c["bits"], c["h"], c["kind"], fec).items()
-             if v != Z.frame_symbols(TR.MODE_LEN, c["h"], c["kind"], c["bits"], fec)]
+             if v != Z.span(TR.MODE_LEN, c["bits"], c["h"], c["kind"], fec)]
     assert "a" in names
     for name in names:
         monkeypatch.setattr(RX, "span", lambda length, bits, h, kind, f, name=name:
@@ -259,7 +261,7 @@ def test_e2e_wrong_symbols_are_corrected(fec, K):
     bits, h, kind = F.bits_per_symbol(K), TS.E2E_H, TS.E2E_KIND
     Bd = Z.row_shape(N, bits, h, kind, fec)[1]
     for f, a in enumerate(at):
-        Sc = Z.frame_symbols(len(datas[f]), h, kind, bits, fec)
+        Sc = Z.span(len(datas[f]), bits, h, kind, fec)
         hard = truth[a + TS.E2E_L:a + TS.E2E_L + Sc]
         assert int((hard != sent[f][:Sc]).sum()) == (wrong if f in TS.E2E_HIT else 0)
     windows = np.array(at, np.uint64) * 4
@@ -273,5 +275,6 @@ def test_e2e_wrong_symbols_are_corrected(fec, K):
         rows = np.zeros((len(at), Bd), np.uint8)
         for i, b in enumerate(written):
             rows[i, :len(b)] = np.frombuffer(b, np.uint8)
-        chk, kept, bodies, summ = Z.check_group(windows, rows, TS.E2E_L, 4, bits, h, kind, fec)
+        chk, kept, bodies, summ = C.check_group(windows, rows, TS.E2E_L, 4, Z.span_of(bits, h, kind, fec), None, h,
+                                                kind)
         assert bodies == datas and kept.tolist() == list(range(5)), seed

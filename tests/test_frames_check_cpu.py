@@ -9,6 +9,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 
 KINDS = (C.CRC16, C.CRC32)
@@ -130,38 +131,39 @@ def test_covered_rule():
     """L = 4, R = 4, bits = 1, h = 1, CRC-16: a frame of len data bytes
     occupies 4 + (3 + len) 8 symbols, (28 + 8 len) 4 windows."""
     L, R, bits, h, kind, B = 4, 4, 1, 1, C.CRC16, 12
+    plain = Z.span_of(bits, h, kind, 0)
     good = [C.encode(bytes([i] * n), h, kind) for i, n in enumerate((2, 0, 5, 1))]
     span = [(L + C.frame_symbols(len(f), bits)) * R for f in good]
     assert span == [(28 + 8 * n) * 4 for n in (2, 0, 5, 1)]
     bad = bytearray(good[2])
     bad[3] ^= 0x10
     # touching frames: the second starts at the first's end
-    chk, kept, bodies, summ = C.check_group([10, 10 + span[0]], rows_of(good[:2], B), L, R, bits, h, kind)
+    chk, kept, bodies, summ = C.check_group([10, 10 + span[0]], rows_of(good[:2], B), L, R, plain, None, h, kind)
     assert chk["covered"].tolist() == [0, 0] and kept.tolist() == [0, 1]
     assert bodies == [bytes([0, 0]), b""]
     assert summ.tolist() == (2, 2, 2, 0)
     # one window of overlap
-    chk, kept, _, summ = C.check_group([10, 10 + span[0] - 1], rows_of(good[:2], B), L, R, bits, h, kind)
+    chk, kept, _, summ = C.check_group([10, 10 + span[0] - 1], rows_of(good[:2], B), L, R, plain, None, h, kind)
     assert chk["covered"].tolist() == [0, 1] and kept.tolist() == [0] and summ.tolist() == (2, 2, 1, 0)
     # an invalid frame in between covers nothing, and is not covered
     w = [10, 10 + span[0], 10 + span[0] + 4]
-    chk, kept, _, summ = C.check_group(w, rows_of([good[0], bytes(bad), good[3]], B), L, R, bits, h, kind)
+    chk, kept, _, summ = C.check_group(w, rows_of([good[0], bytes(bad), good[3]], B), L, R, plain, None, h, kind)
     assert chk["status"].tolist() == [C.OK, C.BAD_CRC, C.OK]
     assert chk["covered"].tolist() == [0, 0, 0] and kept.tolist() == [0, 2] and summ.tolist() == (3, 2, 2, 0)
     # the same place with a valid frame there: the third is covered
-    chk, kept, _, _ = C.check_group(w, rows_of([good[0], good[2], good[3]], B), L, R, bits, h, kind)
+    chk, kept, _, _ = C.check_group(w, rows_of([good[0], good[2], good[3]], B), L, R, plain, None, h, kind)
     assert chk["covered"].tolist() == [0, 0, 1] and kept.tolist() == [0, 1]
     # a covered frame still covers (prefix maximum, not the greedy hold-off): row 1 is
     # inside row 0, row 2 is past row 0's end but inside row 1
     w = [0, span[0] - 4, span[0] + 4]
-    chk, kept, _, _ = C.check_group(w, rows_of([good[0], good[2], good[3]], B), L, R, bits, h, kind)
+    chk, kept, _, _ = C.check_group(w, rows_of([good[0], good[2], good[3]], B), L, R, plain, None, h, kind)
     assert chk["covered"].tolist() == [0, 1, 1] and kept.tolist() == [0]
     # a bad length reads nothing past the header
     long_row = bytes([B - h - 2 + 1]) + bytes(B - 1)
-    chk, kept, _, summ = C.check_group([0], rows_of([long_row], B), L, R, bits, h, kind)
+    chk, kept, _, summ = C.check_group([0], rows_of([long_row], B), L, R, plain, None, h, kind)
     assert chk[0].tolist() == (B - 2, 0, C.BAD_LENGTH, 0) and kept.size == 0 and summ.tolist() == (1, 0, 0, 0)
     # ends wrap at 2^64 as the device's do
-    chk, _, _, _ = C.check_group([2 ** 64 - 8, 2 ** 64 - 4], rows_of(good[:2], B), L, R, bits, h, kind)
+    chk, _, _, _ = C.check_group([2 ** 64 - 8, 2 ** 64 - 4], rows_of(good[:2], B), L, R, plain, None, h, kind)
     assert chk["covered"].tolist() == [0, 0]
 
 

@@ -19,12 +19,13 @@ def test_exports_and_structs(A):
     H, T = A.DemodFrameHit, A.DemodFramesResult
     assert ctypes.sizeof(H) == 16 and (H.window.offset, H.errors.offset, H.reserved.offset) == (0, 8, 12)
     assert A.FRAME_HIT_DTYPE.itemsize == 16 and A.FRAME_HIT_DTYPE == F.HIT_DTYPE
-    assert ctypes.sizeof(T) == 64 * 8 + 48
+    assert ctypes.sizeof(T) == F.RESULT_DTYPE.itemsize and [f for f, _ in T._fields_] == list(F.RESULT_DTYPE.names)
+    for f in F.RESULT_DTYPE.names:                                  # every field where the tests' one dtype has it
+        at, size = F.RESULT_DTYPE.fields[f][1], F.RESULT_DTYPE[f].itemsize
+        assert (getattr(T, f).offset, getattr(T, f).size) == (at, size), f
     A_T = A.DemodAcquireResult
     for f in ("metric", "phases", "phase", "per_phase"):            # as demod_acquire_result_t
         assert getattr(T, f).offset == getattr(A_T, f).offset
-    assert (T.n_hits.offset, T.n_written.offset, T.tail_window.offset) == (528, 536, 544)
-    assert (T.tail_errors.offset, T.reserved.offset) == (552, 556)
     assert lib.demod_frames_async(None, None, None, 4, None, 0, 0, 0, None, None, None, 0, None, None,
                                   0, None) == A.DEMOD_BAD_ARG
     res = T()

@@ -22,7 +22,10 @@ import pytest
 
 import acquire_ref as R
 import guards as G
+from acquire_ref import make_inputs, plant
 from guards import MAG_TOL
+from gpu_support import (EPS, check_acquire as check, handle_fixture, parse_acquire as parse, phased, tones_375,
+                         torch)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -31,55 +34,12 @@ SHAPE_OF_R = {1: (1024, 1024), 2: (1024, 512), 4: (1024, 256), 8: (1024, 128), 1
               32: (256, 8), 64: (512, 8)}
 RS = sorted(SHAPE_OF_R)
 KS = (1, 2, 8, 16)
-EPS = 2.0 ** -52
-RES_BYTES = 64 * 8 + 56
+RES_BYTES = R.RESULT_DTYPE.itemsize
 LEAD = 4096          # guard bytes per side (a multiple of 8: d_result and d_work stay aligned)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = SHAPE_OF_R[Rn]
-            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def make_inputs(W, K, Rn, seed, boost=None, flat=False):
-    """sym random < K; P random positive fp32 over 1e0 .. 1e14, phase `boost`'s
-    powers scaled by 1.5. flat: every tone of a window the same power, so the
-    metric does not depend on the symbols (the sync sweeps plant symbols)."""
-    rng = np.random.default_rng(seed)
-    sym = rng.integers(0, K, W).astype(np.uint8)
-    P = (10.0 ** rng.uniform(0.0, 14.0, (W, 1 if flat else K))).astype(np.float32)
-    if flat:
-        P = np.repeat(P, K, axis=1)
-    if boost is not None:
-        P[boost::Rn] *= np.float32(1.5)
-    return sym, np.ascontiguousarray(P)
-
-
-def parse(A, raw):
-    res = A.DemodAcquireResult.from_buffer_copy(bytes(raw))
-    return A.acquire_result_dict(res)
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, SHAPE_OF_R, Rn, tones_375(K)))
 
 
 class Runner:
@@ -106,20 +66,6 @@ class Runner:
         res = parse(self.A, raw)
         out = d_out.cpu().numpy() if cap else np.zeros(0, np.uint8)
         return out, res, raw
-
-
-def check(res, out, ref_out, ref, cap, metric=True):
-    for f in ("phases", "phase", "per_phase", "sync_window", "sync_errors", "reserved",
-              "first_window", "n_out"):
-        assert res[f] == ref[f], (f, res[f], ref[f])
-    assert res["n_written"] == min(ref["n_out"], cap)
-    nw = res["n_written"]
-    assert np.array_equal(out[:nw], ref_out[:nw])
-    assert (out[nw:] == 0xFF).all(), "bytes past n_written were written"
-    if metric:
-        M, Mr = res["metric"], ref["metric"]
-        assert M.shape == Mr.shape
-        assert (np.abs(M - Mr) <= ref["per_phase"] * EPS * Mr).all(), (M, Mr)
 
 
 def windows_for(Rn, T):
@@ -157,19 +103,6 @@ def test_metric_phase_and_stream(A, torch, handle, Rn):
                 # (the planted symbols pick other powers: the phase may move off the word)
                 found += ref2["sync_window"] >= 0
     assert found >= 8
-
-
-def plant(sym, Rn, w0, word, n_bad, K, rng):
-    """word on sym[w0 :: Rn] with exactly n_bad mismatching positions, each
-    another symbol < K (K >= 2), so that with tone-independent powers the
-    metric stays what it was (bytes >= K: test_bytes_above_k)."""
-    assert K >= 2 or n_bad == 0
-    s = sym.copy()
-    L = len(word)
-    s[w0:w0 + L * Rn:Rn] = word
-    for pos in rng.choice(L, n_bad, replace=False):
-        s[w0 + pos * Rn] = (int(word[pos]) + 1 + int(rng.integers(0, K - 1))) % K
-    return s
 
 
 SWEEPS = [

@@ -25,7 +25,10 @@ import pytest
 import acquire_ref as R
 import acquire_segments_ref as SR
 import guards as G
+from acquire_ref import make_inputs, plant
 from guards import MAG_TOL
+from gpu_support import (ACQUIRE_INT_FIELDS as INT_FIELDS, EPS, check_acquire as check, handle_fixture, parse_acquire
+                         as parse, phased, tables, tones_375, torch)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,63 +36,12 @@ pytestmark = pytest.mark.gpu
 SHAPE_OF_R = {1: (1024, 1024), 4: (1024, 256), 64: (512, 8)}
 RS = sorted(SHAPE_OF_R)
 KS = (1, 2, 16)
-EPS = 2.0 ** -52
-RES_BYTES = 64 * 8 + 56
+RES_BYTES = R.RESULT_DTYPE.itemsize
 LEAD = 4096          # guard bytes per side (a multiple of 8: d_results and d_work stay aligned)
-INT_FIELDS = ("phases", "phase", "per_phase", "sync_window", "sync_errors", "reserved",
-              "first_window", "n_out")
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = SHAPE_OF_R[Rn]
-            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def make_inputs(W, K, Rn, seed, boost=None, flat=False):
-    """sym random < K; P random positive fp32 over 1e0 .. 1e14, phase `boost`'s
-    powers scaled by 1.5. flat: every tone of a window the same power, so the
-    metric does not depend on the symbols (the sync tests plant symbols)."""
-    rng = np.random.default_rng(seed)
-    sym = rng.integers(0, K, W).astype(np.uint8)
-    P = (10.0 ** rng.uniform(0.0, 14.0, (W, 1 if flat else K))).astype(np.float32)
-    if flat:
-        P = np.repeat(P, K, axis=1)
-    if boost is not None:
-        P[boost::Rn] *= np.float32(1.5)
-    return sym, np.ascontiguousarray(P)
-
-
-def parse(A, raw):
-    return A.acquire_result_dict(A.DemodAcquireResult.from_buffer_copy(bytes(raw)))
-
-
-def tables(torch, first, count):
-    """The uint64 / uint32 tables as the int64 / int32 tensors that carry them."""
-    f = np.ascontiguousarray(first, np.uint64).view(np.int64)
-    c = np.ascontiguousarray(count, np.uint32).view(np.int32)
-    return torch.from_numpy(f.copy()).cuda(), torch.from_numpy(c.copy()).cuda()
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, SHAPE_OF_R, Rn, tones_375(K)))
 
 
 class Runner:
@@ -126,19 +78,6 @@ class Runner:
         raws = [raw[s * RES_BYTES:(s + 1) * RES_BYTES] for s in range(S)]
         out = g_out.cpu().numpy().reshape(S, cap) if cap else np.zeros((S, 0), np.uint8)
         return out, [parse(A, r) for r in raws], raws
-
-
-def check(res, out, ref_out, ref, cap, metric=True):
-    for f in INT_FIELDS:
-        assert res[f] == ref[f], (f, res[f], ref[f])
-    assert res["n_written"] == min(ref["n_out"], cap)
-    nw = res["n_written"]
-    assert np.array_equal(out[:nw], ref_out[:nw])
-    assert (out[nw:] == 0xFF).all(), "bytes past n_written were written"
-    if metric:
-        M, Mr = res["metric"], ref["metric"]
-        assert M.shape == Mr.shape
-        assert (np.abs(M - Mr) <= ref["per_phase"] * EPS * Mr).all(), (M, Mr)
 
 
 def check_all(got, want, cap, metric=True):
@@ -230,17 +169,6 @@ def test_equivalence(A, torch, handle, Rn, K):
 
 
 # ---- 2. isolation ------------------------------------------------------------
-
-def plant(sym, Rn, w0, word, n_bad, K, rng):
-    """word on sym[w0 :: Rn] with exactly n_bad mismatching positions, each
-    another symbol < K."""
-    s = sym.copy()
-    L = len(word)
-    s[w0:w0 + L * Rn:Rn] = word
-    for pos in rng.choice(L, n_bad, replace=False):
-        s[w0 + pos * Rn] = (int(word[pos]) + 1 + int(rng.integers(0, K - 1))) % K
-    return s
-
 
 @pytest.mark.parametrize("Rn,K,max_errors,gap", [(1, 2, 0, 0), (1, 16, 1, 2), (4, 16, 2, 0), (4, 2, 1, 3),
                                                  (64, 2, 3, 0), (64, 16, 0, 63)])
@@ -716,12 +644,6 @@ def test_long_segments(A, torch, handle, Rn, K):
 
 # ---- 10. the most segments ------------------------------------------------------
 
-RESULT_DTYPE = np.dtype([("metric", "<f8", 64), ("phases", "<u4"), ("phase", "<u4"),
-                         ("per_phase", "<u8"), ("sync_window", "<i8"), ("sync_errors", "<u4"),
-                         ("reserved", "<u4"), ("first_window", "<u8"), ("n_out", "<u8"),
-                         ("n_written", "<u8")])
-
-
 def test_max_segments(A, torch, handle):
     """DEMOD_MAX_SEGMENTS segments of 0, 1 or 2 windows at R = 1, with a
     one-symbol word: 64 rounds of the plan, more tiles than the scan's grid has
@@ -731,7 +653,7 @@ def test_max_segments(A, torch, handle):
     against the reference on a sample of them."""
     Rn, K, cap = 1, 2, 2
     S = A.DEMOD_MAX_SEGMENTS
-    assert RESULT_DTYPE.itemsize == RES_BYTES
+    assert R.RESULT_DTYPE.itemsize == RES_BYTES
     rng = np.random.default_rng(65536)
     count = rng.integers(0, 3, S)
     first = np.cumsum(count + rng.integers(0, 2, S)) - count
@@ -750,7 +672,7 @@ def test_max_segments(A, torch, handle):
     chk_out(written=False)
     chk_res(written=False)
     chk_work(written=False)
-    res = np.frombuffer(g_res.cpu().numpy().tobytes(), RESULT_DTYPE)
+    res = np.frombuffer(g_res.cpu().numpy().tobytes(), R.RESULT_DTYPE)
     out = g_out.cpu().numpy().reshape(S, cap)
     # the closed form
     pw = P[np.arange(Wb), sym].astype(np.float64)

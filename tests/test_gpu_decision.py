@@ -21,20 +21,13 @@ import pytest
 
 from decision import check_decisions
 from guards import near_tie_windows
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 AUTO, GOERTZEL, FFT, FOLDED, RESIDUE = 0, 1, 2, 3, 4
 FSK8_ODD = tuple(46.875 * (32 + 9 * i) for i in range(8))
 NONINT8 = tuple(1234.5 + 1111.1 * i for i in range(8))
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 @pytest.mark.parametrize("plan,method", [

@@ -25,16 +25,9 @@ import os
 import pytest
 
 import error_model as EM
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 @pytest.mark.parametrize("case", EM.CASES, ids=[c[0] for c in EM.CASES])

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import fec_ml_ref as ML
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as X
 import frames_ref as F
@@ -107,8 +108,8 @@ def test_noisy_tones(A, torch, handle, K, Rn, boost):
     d = handle(Rn, K)
     bits = F.bits_per_symbol(K)
     rng = np.random.default_rng(1000 * K + 10 * Rn + boost)
-    shapes = [(M.LONG[0], M.LONG[1], X.symbols_for(M.LONG[2], bits, *M.LONG[:2]), 24),
-              (M.H2[0], M.H2[1], X.symbols_for(M.H2[2], bits, *M.H2[:2]), 8),
+    shapes = [(M.LONG[0], M.LONG[1], Z.symbols_for(M.LONG[2], bits, *M.LONG[:2], X.CONV_K7), 24),
+              (M.H2[0], M.H2[1], Z.symbols_for(M.H2[2], bits, *M.H2[:2], X.CONV_K7), 8),
               (1, C.CRC16, min_symbols(bits, 1), 8)]
     oks, steps, small = [], [], []
     for h, kind, N, n in shapes:
@@ -140,7 +141,7 @@ def test_longest_rows(A, torch, handle):
     K, Rn, bits = 16, 1, 4
     rng = np.random.default_rng(32822)
     q5, h, kind = M.longest_negated(rng)
-    N = X.symbols_for(4096, bits, h, kind)
+    N = Z.symbols_for(4096, bits, h, kind, X.CONV_K7)
     assert N * bits == q5.size and X.row_shape(N, bits, h, kind)[::2] == (32822, 4096)
     weights = np.array([8, 4, 2, 1])
     sym5 = ((q5 < 0).reshape(N, bits) * weights).sum(axis=1).astype(np.uint8)

@@ -11,6 +11,7 @@ Kernel level as tests/test_gpu_frames_fec.py: test-made hits, results, tables
 and powers on the device, so no detector and no scan run.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -20,51 +21,21 @@ import frames_check_ref as C
 import frames_fec_ref as X
 import frames_ref as F
 import guards as G
+import rx_ref as RX
 import tx_ref as T
+from gpu_support import handle_fixture, phased, results_bytes, same as whole_same, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SHAPE_OF_R = {1: (1024, 1024), 4: (1024, 256)}       # (n, hop) of a handle with R phases
-RES_BYTES = 64 * 8 + 48
-N_HITS_AT, N_WRITTEN_AT = 528, 536
+RES_BYTES = F.RESULT_DTYPE.itemsize
 POISON = 0xFF
 L0 = 8               # the word's symbols in the kernel-level tests (it is never read)
 MAX_LEN = 40         # rows that hold every edge length of fec_modes_ref.edge_lengths
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = SHAPE_OF_R[Rn]
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=T.loop_tones(K))
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def results_bytes(n_written):
-    """[G] demod_frames_result_t with n_hits = n_written = the given counts, the rest 0."""
-    res = np.zeros((len(n_written), RES_BYTES), np.uint8)
-    raw = np.array([int(n) for n in n_written], "<u8").view(np.uint8).reshape(-1, 8)
-    res[:, N_HITS_AT:N_HITS_AT + 8] = raw
-    res[:, N_WRITTEN_AT:N_WRITTEN_AT + 8] = raw
-    return res
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, SHAPE_OF_R, Rn, T.loop_tones(K)))
 
 
 def air_symbols(air, N, bits, rng):
@@ -173,10 +144,7 @@ class Run:
                 self.d_dec.cpu().numpy().reshape(self.n_groups, self.max_frames, 16))
 
 
-def same(got, want, what=""):
-    for name, g, w in zip(("rows", "decode"), got, want):
-        bad = np.argwhere(g != w)
-        assert bad.size == 0, (what, name, len(bad), bad[:4].tolist())
+same = functools.partial(whole_same, names=("rows", "decode"))
 
 
 def one_group(starts, max_frames=None):
@@ -386,7 +354,7 @@ def test_transmitter_symbols(A, torch, fec, K):
     word = (np.arange(11) * 5) % K
     rng = np.random.default_rng(fec + K)
     datas = [rng.integers(0, 256, ln).astype(np.uint8).tobytes() for ln in lens]
-    counts = [11 + Z.frame_symbols(ln, h, kind, bits, fec) for ln in lens]
+    counts = [11 + Z.span(ln, bits, h, kind, fec) for ln in lens]
     ring = sum(counts) + 9
     x = A.make_tx_cfg(word, h, kind, fec, MAX_LEN, 0, (0,), 8000, 0, 0, ring, len(lens), 2880)
     want = [A.tx_frame_symbols(x, K, data) for data in datas]
@@ -444,7 +412,7 @@ def link_run(A, torch, fec, zero=None, shape=LINK_SHAPE):
     word = rng.integers(0, K, LINK_L).astype(np.uint8)
     datas = [rng.integers(0, 256, ln).astype(np.uint8).tobytes() for ln in LINK_LENS]
     max_len, gap = max(LINK_LENS), 3
-    per = [LINK_L + Z.frame_symbols(len(dd), h, kind, bits, fec) + gap for dd in datas]
+    per = [LINK_L + Z.span(len(dd), bits, h, kind, fec) + gap for dd in datas]
     N = Z.symbols_for(max_len, bits, h, kind, fec)
     symbols = 3 + sum(per) + N + 8
     total = -(-symbols * LINK_N // LINK_PACKET) * LINK_PACKET
@@ -492,7 +460,7 @@ def link_reference(A, fec, streams, N, ring, word, shape=LINK_SHAPE):
             W = (len(pcm) - LINK_N) // LINK_HOP + 1
             sym, P = d.batch(pcm[:(W - 1) * LINK_HOP + LINK_N], mags=True)
             cuts.append(LR.pieces(sym, P, sizes, LINK_N, LINK_HOP))
-    ref = Z.receiver(LINK_S, K, R, word, 2, N, h, kind, fec, 8, ring)
+    ref = RX.Rx(LINK_S, K, R, word, 2, N, h, kind, fec, 8, ring)
     return [ref.push([cuts[s][i] for s in range(LINK_S)]) for i in range(len(cuts[0]))]
 
 

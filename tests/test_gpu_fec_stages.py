@@ -17,7 +17,7 @@ them changes `covered`.
 
 End to end: five coded frames as 2-FSK and 8-FSK PCM in every mapped mode,
 payload symbols of three of them on a wrong tone, through demod_frames_coded
-from a host array and from a device pointer, against fec_modes_ref.scan_check
+from a host array and from a device pointer, against rx_ref.scan_check
 on the device detector's own outputs.
 """
 import functools
@@ -29,7 +29,9 @@ import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as X
 import frames_ref as F
+import rx_ref as RX
 import test_gpu_frames_fec as TF
+from gpu_support import handle_fixture, phased, tones_375, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -42,30 +44,8 @@ CHECK_CASES = [(fec,) + s for fec in Z.MODES for s in CHECK_SHAPES] + [(0x51, 16
 GROUPS_SHAPE = dict(K=8, Rn=4, h=1, kind=C.CRC16, n_groups=65, max_frames=5)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = TF.SHAPE_OF_R[Rn]
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=tuple(1500.0 + 375.0 * i for i in range(K)))
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, TF.SHAPE_OF_R, Rn, tones_375(K)))
 
 
 # ---- the spans a per-mode slip would give ------------------------------------------------
@@ -122,7 +102,7 @@ def check_case(fec, K, Rn, h, kind):
     rng = np.random.default_rng(fec * 1000 + K * 10 + Rn + h)
 
     def span(n):
-        return Z.frame_symbols(n, h, kind, bits, fec)
+        return Z.span(n, bits, h, kind, fec)
 
     def far(n):
         return max([span(n)] + list(alt_spans(n, bits, h, kind, fec).values()))
@@ -185,7 +165,7 @@ def groups_case(fec):
                 f[h + len(f) % 3] ^= 0x10
             rows[s, i, :len(f)] = f
             hits["window"][s, i] = w
-            own, half = Z.frame_symbols(n, h, kind, bits, fec), X.coded_symbols(n, h, kind, bits)
+            own, half = Z.span(n, bits, h, kind, fec), X.coded_symbols(n, h, kind, bits)
             off = [(L0 + own) * Rn, (L0 + own) * Rn - 1, (L0 + own + 3) * Rn,
                    (L0 + min(own, half)) * Rn + abs(own - half) * Rn // 2][int(rng.integers(0, 4))]
             w += off
@@ -195,8 +175,7 @@ def groups_case(fec):
 
 
 def expected(case, Rn, h, kind, fec, poison):
-    return TF.coded_expected(case["hits"], case["rows"], case["counts"], L0, Rn, case["bits"], h, kind, poison,
-                             group=functools.partial(Z.check_group, fec=fec))
+    return TF.coded_expected(case["hits"], case["rows"], case["counts"], L0, Rn, case["bits"], h, kind, poison, fec)
 
 
 def run_check(torch, d, case, Rn, h, kind, fec):
@@ -216,7 +195,7 @@ def run_check(torch, d, case, Rn, h, kind, fec):
         d.frames_check_coded_async(d_in[0], d_in[1], d_in[2], n_groups, mf, L0, case["N"], h, kind, o["check"],
                                    o["kept"].view(torch.int32), o["body"], o["summary"], fec=fec)
         torch.cuda.synchronize()
-        TF.same_dict({k: v.cpu().numpy().reshape(shape[k]) for k, v in o.items()}, want, (hex(fec), poison))
+        TF.same({k: v.cpu().numpy().reshape(shape[k]) for k, v in o.items()}, want, (hex(fec), poison))
     for t, a in zip(d_in, inputs):
         assert t.cpu().numpy().tobytes() == a.tobytes(), "an input was written to"
     return refs
@@ -288,7 +267,7 @@ def e2e_symbols(K, fec, wrong=None, seed=91):
         row = air_symbols(air, N, bits, rng)
         sent.append(row.copy())
         if f in E2E_HIT:
-            Sc = Z.frame_symbols(len(data), h, kind, bits, fec)
+            Sc = Z.span(len(data), bits, h, kind, fec)
             for j in (Sc // 6, Sc // 2, (5 * Sc) // 6)[:wrong]:
                 row[j] = (row[j] + 1 + int(rng.integers(0, K - 1))) % K
         seq += [word, row, rng.integers(0, K, 8 + 3 * f).astype(np.uint8)]
@@ -315,7 +294,7 @@ def e2e_pcm(freqs, truth, seed, n=1024, sigma=400.0, amplitude=8000.0):
 @pytest.mark.parametrize("fec", Z.NEW_MODES)
 def test_frames_coded_modes(A, torch, fec, name):
     """demod_frames_coded in every mapped mode, n 1024, hop 256: bodies,
-    lengths, kept hits and summary equal fec_modes_ref.scan_check (scan, the
+    lengths, kept hits and summary equal rx_ref.scan_check (scan, the
     mode's decode, the coded check with the mode's span) on the device
     detector's own (sym, P); all five bodies come back although the hard
     decisions of three rows differ from what was sent. From a host array and
@@ -335,10 +314,10 @@ def test_frames_coded_modes(A, torch, fec, name):
         torch.cuda.synchronize()
         sym, P = d_sym.cpu().numpy(), d_mag.cpu().numpy().reshape(W, K)
         for f, w0 in enumerate(windows):             # the hard decisions: wrong where a wrong tone was sent
-            Sc = Z.frame_symbols(len(datas[f]), h, kind, bits, fec)
+            Sc = Z.span(len(datas[f]), bits, h, kind, fec)
             hard = sym[w0 + (E2E_L + np.arange(Sc)) * Rn]
             assert int((hard != sent[f][:Sc]).sum()) == (wrong if f in E2E_HIT else 0), f
-        r_hits, r_chk, r_kept, r_bodies, r_summ, r_res = Z.scan_check(sym, P, Rn, word, 1, N, h, kind, fec)
+        r_hits, r_chk, r_kept, r_bodies, r_summ, r_res = RX.scan_check(sym, P, Rn, word, 1, N, h, kind, fec)
         nw = r_res["n_written"]
         assert r_bodies == datas and [int(r_hits["window"][i]) for i in r_kept] == windows   # the reference alone
         assert r_res["phase"] == 0 and nw == len(r_hits)

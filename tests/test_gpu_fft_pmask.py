@@ -13,17 +13,10 @@ import numpy as np
 import pytest
 
 import error_model as EM
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 N = 1024
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def quad_slot(b):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from decision import check_decisions
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -35,14 +36,6 @@ K3 = tuple(46.875 * b for b in (40, 64, 120))                 # generic fold, od
 K5 = tuple(46.875 * b for b in (16, 48, 56, 96, 200))
 K16 = tuple(46.875 * (24 + 8 * i) for i in range(16))        # the LDS-free K = 16 fold
 FSK8_SHUFFLED = tuple(1500.0 + 375.0 * i for i in (5, 2, 7, 0, 3, 6, 1, 4))  # F16, permuted slots
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def wt(hop):

@@ -18,6 +18,8 @@ import pytest
 
 import frames_ref as F
 import guards as G
+from gpu_support import (LEAD, check_frames as check, guarded, handle_fixture, parse_frames as parse, phased,
+                         tones_375, torch)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -25,36 +27,13 @@ SHAPE_OF_R = {1: (1024, 1024), 4: (1024, 256), 64: (512, 8)}    # (n, hop) of a 
 RS, KS = (1, 4, 64), (1, 2, 16)
 LS, NS = (1, 24, 64), (0, 1, 7, 64, 300)
 MAX_ERRORS = {1: 0, 24: 2, 64: 5}
-RES_BYTES = 64 * 8 + 48
+RES_BYTES = F.RESULT_DTYPE.itemsize
+PREFIX = F.RESULT_DTYPE.fields["n_hits"][1]     # metric[64], phases, phase, per_phase: as demod_acquire_result_t
 HIT = 16
-LEAD = 4096          # guard bytes per side (a multiple of 8: d_hits, d_result and d_work stay aligned)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = SHAPE_OF_R[Rn]
-            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, SHAPE_OF_R, Rn, tones_375(K)))
 
 
 def windows_for(Rn, T):
@@ -98,20 +77,6 @@ def plant(sym, Rn, K, w0, word, n_bad, salt=0, keep=()):
     assert int(np.count_nonzero(sym[w0:w0 + L * Rn:Rn] != word)) == n_bad
 
 
-def result_bytes(A, ref):
-    r = A.DemodFramesResult()
-    for i, m in enumerate(ref["metric"]):
-        r.metric[i] = float(m)
-    for f in ("phases", "phase", "per_phase", "n_hits", "n_written", "tail_window", "tail_errors",
-              "reserved"):
-        setattr(r, f, int(ref[f]))
-    return bytes(r)
-
-
-def parse(A, raw):
-    return A.frames_result_dict(A.DemodFramesResult.from_buffer_copy(bytes(raw)))
-
-
 class Runner:
     """Device buffers of one (handle, W). run() returns the raw result, its
     dict and the three output arrays whole, rows past n_written included."""
@@ -148,28 +113,6 @@ class Runner:
         hits = d_hits.cpu().numpy().view(F.HIT_DTYPE) if d_hits is not None else np.zeros(0, F.HIT_DTYPE)
         return dict(raw=raw, res=parse(self.A, raw), hits=hits, payload=host(d_pay, (max_frames, N)),
                     packed=host(d_pak, (max_frames, B)))
-
-
-def check(A, out, ref, max_frames, poison=0xFF):
-    """Result bytes, hits, payload rows and packed rows equal the reference's;
-    rows past n_written still hold the poison."""
-    r_hits, r_pay, r_pak, r_res = ref
-    r_res = dict(r_res, n_written=min(r_res["n_hits"], max_frames))
-    nw = r_res["n_written"]
-    assert out["raw"] == result_bytes(A, r_res), (out["res"], r_res)
-    assert out["hits"][:nw].tobytes() == r_hits[:nw].tobytes()
-    assert (out["hits"][nw:].view(np.uint8) == poison).all(), "hit rows past n_written were written"
-    for got, want in ((out["payload"], r_pay), (out["packed"], r_pak)):
-        if got is not None:
-            assert np.array_equal(got[:nw], want[:nw])
-            assert (got[nw:] == poison).all(), "rows past n_written were written"
-
-
-def guarded(torch, numel, lead, poison):
-    """guards.guarded for a uint8 output; (None, a check of nothing) for an empty one."""
-    if numel == 0:
-        return None, lambda written: None
-    return G.guarded(torch, numel, torch.uint8, lead, LEAD, poison)
 
 
 def host_rows(t, rows, width):
@@ -393,7 +336,7 @@ def test_phase_decision_is_the_acquisition(A, torch, handle, Rn):
                     d.acquire_async(run.d_sym, run.d_P, W, word, 0, None, d_ares, d_awork)
                     torch.cuda.synchronize()
                     araw = d_ares.cpu().numpy().tobytes()
-                    assert out["raw"][:528] == araw[:528]       # metric[64], phases, phase, per_phase
+                    assert out["raw"][:PREFIX] == araw[:PREFIX]
                     acq = A.acquire_result_dict(A.DemodAcquireResult.from_buffer_copy(araw))
                     ref = F.frames(sym, P, Rn, word, 0, N, max_frames=4)
                     res = out["res"]

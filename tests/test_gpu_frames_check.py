@@ -14,60 +14,29 @@ and through the segmented scan and demod_frames_check_async.
 import numpy as np
 import pytest
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_ref as F
 import guards as G
+from gpu_support import handle_fixture, phased, results_bytes, same, tones_375, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SHAPE_OF_R = {1: (1024, 1024), 4: (1024, 256), 64: (512, 8)}    # (n, hop) of a handle with R phases
-RES_BYTES = 64 * 8 + 48
-N_HITS_AT, N_WRITTEN_AT = 528, 536
+RES_BYTES = F.RESULT_DTYPE.itemsize
 LEAD = 4096          # guard bytes per side (a multiple of 8: the aligned outputs stay aligned)
 POISON = 0xFF
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, SHAPE_OF_R, Rn, tones_375(K)))
 
 
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = SHAPE_OF_R[Rn]
-            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def symbols_for(B, bits):
+def row_symbols(B, bits):
     """A frame_symbols whose packed row is B bytes."""
     N = (B * 8) // bits
     assert (N * bits + 7) // 8 == B
     return N
-
-
-def results_bytes(n_written):
-    """[G] demod_frames_result_t with n_hits = n_written = the given counts, the rest 0."""
-    res = np.zeros((len(n_written), RES_BYTES), np.uint8)
-    raw = np.array([int(n) for n in n_written], "<u8").view(np.uint8).reshape(-1, 8)
-    res[:, N_HITS_AT:N_HITS_AT + 8] = raw
-    res[:, N_WRITTEN_AT:N_WRITTEN_AT + 8] = raw
-    return res
 
 
 def expected(hits, packed, n_written, L, Rn, bits, h, kind, poison=POISON):
@@ -78,7 +47,7 @@ def expected(hits, packed, n_written, L, Rn, bits, h, kind, poison=POISON):
     kept = np.full((n_groups, max_frames, 4), poison, np.uint8)
     body = np.full((n_groups, max_frames, max_len), poison, np.uint8)
     summ = np.zeros(n_groups, C.SUMMARY_DTYPE)
-    refs = C.check_groups(hits, packed, n_written, max_frames, L, Rn, bits, h, kind)
+    refs = C.check_groups(hits, packed, n_written, max_frames, L, Rn, Z.span_of(bits, h, kind, 0), None, h, kind)
     for g, (r_chk, r_kept, r_bodies, r_summ) in enumerate(refs):
         chk[g, :len(r_chk)] = r_chk.view(np.uint8).reshape(-1, 16)
         kept[g, :len(r_kept)] = r_kept.view(np.uint8).reshape(-1, 4)
@@ -129,12 +98,6 @@ class Run:
         shape = dict(check=(self.n_groups, self.max_frames, 16), kept=(self.n_groups, self.max_frames, 4),
                      body=(self.n_groups, self.max_frames, max_len), summary=(self.n_groups, 32))
         return {k: v.cpu().numpy().reshape(shape[k]) for k, v in o.items() if v is not None}
-
-
-def same(got, want, what=""):
-    for k, v in got.items():
-        bad = np.argwhere(v != want[k])
-        assert bad.size == 0, (what, k, len(bad), bad[:4].tolist())
 
 
 def frame_row(rng, length, B, h, kind):
@@ -193,7 +156,7 @@ def test_crc_shapes(A, torch, handle, h, kind):
         hits = np.zeros((1, max_frames), C.HIT_DTYPE)
         hits["window"] = np.arange(max_frames) * 10 ** 6          # nothing covers anything
         want, refs = expected(hits, packed, [nw], 24, 4, 1, h, kind)
-        got = Run(torch, hits, packed, [nw])(d, 24, symbols_for(B, 1), h, kind)
+        got = Run(torch, hits, packed, [nw])(d, 24, row_symbols(B, 1), h, kind)
         same(got, want, B)
         statuses |= set(refs[0][0]["status"].tolist())
         assert refs[0][0]["status"][0] == C.OK and refs[0][3]["n_kept"] == refs[0][3]["n_valid"] >= 1
@@ -276,7 +239,7 @@ def test_select_shapes(A, torch, handle, Rn, K):
         assert summ["n_checked"] >= summ["n_valid"] >= summ["n_kept"]
         assert summ["n_kept"] == len(kept) and (np.diff(kept.astype(np.int64)) > 0).all()
     assert seen >= 200
-    got = Run(torch, hits, packed, counts)(d, SELECT_L, symbols_for(SELECT_B, bits), SELECT_H, SELECT_KIND)
+    got = Run(torch, hits, packed, counts)(d, SELECT_L, row_symbols(SELECT_B, bits), SELECT_H, SELECT_KIND)
     same(got, want, (Rn, K))
 
 
@@ -300,7 +263,7 @@ def test_groups(A, torch, handle, n_groups):
     for g in range(n_groups):
         hits["window"][g], packed[g], _ = select_group(rng, counts[g], max_frames, Rn, bits)
     want, refs = expected(hits, packed, counts, SELECT_L, Rn, bits, SELECT_H, SELECT_KIND)
-    N = symbols_for(SELECT_B, bits)
+    N = row_symbols(SELECT_B, bits)
     got = Run(torch, hits, packed, counts)(d, SELECT_L, N, SELECT_H, SELECT_KIND)
     same(got, want, n_groups)
     assert sum(int(r[3]["n_kept"]) for r in refs) > n_groups
@@ -631,7 +594,8 @@ def test_end_to_end(A, torch, name):
         nw = s_res["n_written"]
         assert s_res["phase"] == 0 and s_res["n_hits"] == nw
         assert set(windows) | {copy_window} <= set(s_hits["window"].tolist())     # the scan lists them all
-        chk, kept, bodies, summ = C.check_group(s_hits["window"], s_packed, E2E_L, Rn, bits, h, kind)
+        chk, kept, bodies, summ = C.check_group(s_hits["window"], s_packed, E2E_L, Rn, Z.span_of(bits, h, kind, 0),
+                                                None, h, kind)
         for pcm in (x, torch.from_numpy(x).cuda()):
             hits, lengths, body, res, summary = d.frames_checked(pcm, word, max_errors=1, frame_symbols=N,
                                                                 len_bytes=h, crc=kind)

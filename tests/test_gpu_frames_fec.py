@@ -13,59 +13,29 @@ payload symbols replaced by a wrong tone, through demod_frames_coded and, as
 two segments, through the segmented scan, the decode and the coded check.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as X
 import frames_ref as F
 import guards as G
+from gpu_support import handle_fixture, phased, results_bytes, same as whole_same, tones_375, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SHAPE_OF_R = {1: (1024, 1024), 4: (1024, 256), 64: (512, 8)}    # (n, hop) of a handle with R phases
-RES_BYTES = 64 * 8 + 48
-N_HITS_AT, N_WRITTEN_AT = 528, 536
+RES_BYTES = F.RESULT_DTYPE.itemsize
 LEAD = 4096          # guard bytes per side (a multiple of 8)
 POISON = 0xFF
 L0 = 8               # the word's symbols in the kernel-level tests (it is never read)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = SHAPE_OF_R[Rn]
-            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def results_bytes(n_written):
-    """[G] demod_frames_result_t with n_hits = n_written = the given counts, the rest 0."""
-    res = np.zeros((len(n_written), RES_BYTES), np.uint8)
-    raw = np.array([int(n) for n in n_written], "<u8").view(np.uint8).reshape(-1, 8)
-    res[:, N_HITS_AT:N_HITS_AT + 8] = raw
-    res[:, N_WRITTEN_AT:N_WRITTEN_AT + 8] = raw
-    return res
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, SHAPE_OF_R, Rn, tones_375(K)))
 
 
 def min_symbols(bits, h):
@@ -192,10 +162,7 @@ class Run:
                 self.d_dec.cpu().numpy().reshape(self.n_groups, self.max_frames, 16))
 
 
-def same(got, want, what=""):
-    for name, g, w in zip(("rows", "decode"), got, want):
-        bad = np.argwhere(g != w)
-        assert bad.size == 0, (what, name, len(bad), bad[:4].tolist())
+same = functools.partial(whole_same, names=("rows", "decode"))
 
 
 def one_group(starts, max_frames=None):
@@ -256,7 +223,7 @@ def test_shapes(A, torch, handle, K, Rn, h, kind):
     bits = F.bits_per_symbol(K)
     n0 = min_symbols(bits, h)
     statuses = set()
-    for N in (n0, n0 + 1, X.symbols_for(24, bits, h, kind)):
+    for N in (n0, n0 + 1, Z.symbols_for(24, bits, h, kind, X.CONV_K7)):
         rng = np.random.default_rng(N * 1000 + K * 10 + h + kind)
         rows, frames = shape_rows(rng, N, bits, h, kind, K)
         P, starts = lay_rows(rows, K, Rn, rng)
@@ -277,7 +244,7 @@ def test_longest_row(A, torch, handle):
     the host decoder demod_coded_frame_decode on the reference's soft values
     (tests/test_frames_fec_cpu.py holds that decoder to the reference)."""
     K, Rn, h, kind, bits = 16, 1, 2, C.CRC32, 4
-    N = X.symbols_for(4096, bits, h, kind)
+    N = Z.symbols_for(4096, bits, h, kind, X.CONV_K7)
     assert X.row_shape(N, bits, h, kind)[2] == 4096
     rng = np.random.default_rng(4096)
     row, frame = frame_symbols(rng, 4096, N, bits, h, kind, flips=0)
@@ -309,7 +276,7 @@ def test_counts_and_erasures(A, torch, handle):
     n_windows and beyond, and one of 2^64 - 1."""
     K, Rn, h, kind = 4, 4, 1, C.CRC16
     d = handle(Rn, K)
-    N = X.symbols_for(9, 2, h, kind)
+    N = Z.symbols_for(9, 2, h, kind, X.CONV_K7)
     rng = np.random.default_rng(77)
     P, starts = pool(rng, K, Rn, h, kind, N)
     W = len(P)
@@ -356,7 +323,7 @@ def test_segments(A, torch, handle):
     an erasure)."""
     K, Rn, h, kind = 8, 4, 2, C.CRC16
     d = handle(Rn, K)
-    N = X.symbols_for(6, 3, h, kind)
+    N = Z.symbols_for(6, 3, h, kind, X.CONV_K7)
     rng = np.random.default_rng(8)
     P, starts = pool(rng, K, Rn, h, kind, N, count=10)
     W = len(P)
@@ -390,7 +357,7 @@ def test_guards(A, torch, handle, Rn, K, h, kind):
     inputs are unchanged."""
     d = handle(Rn, K)
     bits = F.bits_per_symbol(K)
-    N = X.symbols_for(11, bits, h, kind) + 1
+    N = Z.symbols_for(11, bits, h, kind, X.CONV_K7) + 1
     rng = np.random.default_rng(K + Rn)
     P, starts = pool(rng, K, Rn, h, kind, N)
     counts, max_frames = [40, 0, 70], 70
@@ -521,7 +488,7 @@ def test_refusals(A, torch, handle):
 # ---- a scan in front: determinism, capture and replay --------------------------------------
 
 SCAN_R, SCAN_K, SCAN_L, SCAN_H, SCAN_KIND, SCAN_CAP = 4, 4, 16, 2, C.CRC16, 12
-SCAN_N = X.symbols_for(16, 2, SCAN_H, SCAN_KIND)
+SCAN_N = Z.symbols_for(16, 2, SCAN_H, SCAN_KIND, X.CONV_K7)
 SCAN_BD, SCAN_MAX = X.row_shape(SCAN_N, 2, SCAN_H, SCAN_KIND)[1:]
 
 
@@ -550,9 +517,8 @@ def scan_content(seed, n_frames, W=20001):
     return sym, np.ascontiguousarray(P), word
 
 
-def coded_expected(hits, rows, n_written, L, Rn, bits, h, kind, poison=POISON, group=X.check_group):
-    """The check's four outputs whole, with the coded span (group: the
-    reference of one group's rows)."""
+def coded_expected(hits, rows, n_written, L, Rn, bits, h, kind, poison=POISON, fec=X.CONV_K7):
+    """The check's four outputs whole, with the span of the mode `fec`."""
     n_groups, max_frames, Bd = rows.shape
     max_len = Bd - h - C.CRC_BYTES[kind]
     chk = np.full((n_groups, max_frames, 16), poison, np.uint8)
@@ -562,7 +528,7 @@ def coded_expected(hits, rows, n_written, L, Rn, bits, h, kind, poison=POISON, g
     refs = []
     for g in range(n_groups):
         nw = min(int(n_written[g]), max_frames)
-        r = group(hits["window"][g, :nw], rows[g, :nw], L, Rn, bits, h, kind)
+        r = C.check_group(hits["window"][g, :nw], rows[g, :nw], L, Rn, Z.span_of(bits, h, kind, fec), None, h, kind)
         chk[g, :nw] = r[0].view(np.uint8).reshape(-1, 16)
         kept[g, :len(r[1])] = r[1].view(np.uint8).reshape(-1, 4)
         for i, data in enumerate(r[2]):
@@ -621,12 +587,6 @@ class ScanBuffers:
         return {k: v.cpu().numpy().reshape(shape[k]) for k, v in self.outs.items()}
 
 
-def same_dict(got, want, what=""):
-    for k, v in got.items():
-        bad = np.argwhere(v != want[k])
-        assert bad.size == 0, (what, k, len(bad), bad[:4].tolist())
-
-
 def test_determinism_and_second_stream(A, torch, handle):
     """Two runs, and a run on a second stream with buffers of its own, give
     byte-identical outputs: the reference's. Every third frame is covered
@@ -651,7 +611,7 @@ def test_determinism_and_second_stream(A, torch, handle):
         b.step(word, stream=side.cuda_stream)
     runs.append(b.results())
     for r in runs:
-        same_dict(r, want)
+        same(r, want)
 
 
 def test_capture_and_replay(A, torch, handle):
@@ -671,7 +631,7 @@ def test_capture_and_replay(A, torch, handle):
         buf.poison()
         buf.step(word, stream=side.cuda_stream)          # an eager call of the shape first
         side.synchronize()
-    same_dict(buf.results(), refs[0][1], "eager")
+    same(buf.results(), refs[0][1], "eager")
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=side):
         buf.step(word, stream=torch.cuda.current_stream().cuda_stream)
@@ -681,7 +641,7 @@ def test_capture_and_replay(A, torch, handle):
             buf.poison()
             torch.cuda.synchronize()
             g.replay()
-            same_dict(buf.results(), want, rep)
+            same(buf.results(), want, rep)
 
 
 # ---- the coded check -------------------------------------------------------------------------
@@ -695,7 +655,7 @@ def test_coded_check(A, torch, handle, Rn, K):
     demod_frames_check_async on the same buffers still gives its old bytes."""
     d = handle(Rn, K)
     bits, h, kind, L = F.bits_per_symbol(K), 1, C.CRC16, 8
-    N = X.symbols_for(30, bits, h, kind)
+    N = Z.symbols_for(30, bits, h, kind, X.CONV_K7)
     Bd = X.row_shape(N, bits, h, kind)[1]
     B = (N * bits + 7) // 8
     rng = np.random.default_rng(Rn + K)
@@ -723,8 +683,7 @@ def test_coded_check(A, torch, handle, Rn, K):
     for coded in (True, False):
         view, width = (coded_rows, Bd) if coded else (rows, B)
         max_len = width - h - 2
-        want, refs = coded_expected(hits, view, [nw], L, Rn, bits, h, kind,
-                                    group=X.check_group if coded else C.check_group)
+        want, refs = coded_expected(hits, view, [nw], L, Rn, bits, h, kind, fec=X.CONV_K7 if coded else 0)
         o = dict(check=torch.full((hits.size * 16,), POISON, **u8), kept=torch.full((hits.size * 4,), POISON, **u8),
                  body=torch.full((hits.size * max_len,), POISON, **u8), summary=torch.full((32,), POISON, **u8))
         call = d.frames_check_coded_async if coded else d.frames_check_async
@@ -732,10 +691,11 @@ def test_coded_check(A, torch, handle, Rn, K):
              o["body"], o["summary"])
         torch.cuda.synchronize()
         shape = dict(check=(1, -1, 16), kept=(1, -1, 4), body=(1, -1, max_len), summary=(1, 32))
-        same_dict({k: v.cpu().numpy().reshape(shape[k]) for k, v in o.items()}, want, coded)
+        same({k: v.cpu().numpy().reshape(shape[k]) for k, v in o.items()}, want, coded)
         if coded:
             cov = refs[0][0]["covered"].tolist()
-            plain_cov = C.check_group(hits["window"][0, :nw], coded_rows[0, :nw], L, Rn, bits, h, kind)[0]["covered"]
+            plain_cov = C.check_group(hits["window"][0, :nw], coded_rows[0, :nw], L, Rn, Z.span_of(bits, h, kind, 0),
+                                      None, h, kind)[0]["covered"]
             assert sum(cov) >= 4 and sum(cov) > int(plain_cov.sum())       # the fixture's condition
 
 
@@ -753,7 +713,7 @@ def e2e_stream(freqs, h=2, kind=C.CRC16, n=1024, hop=256, sigma=400.0, amplitude
     K, Rn = len(freqs), n // hop
     bits = F.bits_per_symbol(K)
     word = rng.integers(0, K, E2E_L).astype(np.uint8)
-    N = X.symbols_for(max(E2E_LENS), bits, h, kind) + 3
+    N = Z.symbols_for(max(E2E_LENS), bits, h, kind, X.CONV_K7) + 3
     datas = [rng.integers(0, 256, m).astype(np.uint8).tobytes() for m in E2E_LENS]
     seq, at, sent = [rng.integers(0, K, 9).astype(np.uint8)], [], []
     for f, data in enumerate(datas):
@@ -806,7 +766,8 @@ def test_end_to_end(A, torch, name):
         h1 = np.zeros((1, nw), C.HIT_DTYPE)
         h1[0] = s_hits
         rows, dec, _ = reference(P, W, None, h1, [nw], E2E_L, Rn, N, h, kind)
-        chk, kept, bodies, summ = X.check_group(s_hits["window"], rows[0], E2E_L, Rn, bits, h, kind)
+        chk, kept, bodies, summ = C.check_group(s_hits["window"], rows[0], E2E_L, Rn,
+                                                Z.span_of(bits, h, kind, X.CONV_K7), None, h, kind)
         assert bodies == datas and [int(s_hits["window"][i]) for i in kept] == windows
         for pcm in (x, d_pcm):
             hits, lengths, body, res, summary = d.frames_coded(pcm, word, max_errors=1, frame_symbols=N,
@@ -843,6 +804,6 @@ def test_end_to_end(A, torch, name):
         want.update(rows=rows2, decode=dec2)
         shape = dict(rows=(2, cap, Bd), decode=(2, cap, 16), check=(2, cap, 16), kept=(2, cap, 4),
                      body=(2, cap, max_len), summary=(2, 32))
-        same_dict({k: v.cpu().numpy().reshape(shape[k]) for k, v in outs.items()}, want, "segments")
+        same({k: v.cpu().numpy().reshape(shape[k]) for k, v in outs.items()}, want, "segments")
         assert [int(h2[s, i]["window"]) + first[s] for s in range(2) for i in refs[s][1]] == windows
         assert [b for s in range(2) for b in refs[s][2]] == datas

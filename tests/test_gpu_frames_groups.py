@@ -49,7 +49,7 @@ import test_gpu_rs as TR
 import test_gpu_rx as TX
 import test_gpu_tx as TT
 import tx_ref as T
-from test_gpu_frames import result_bytes
+from gpu_support import frames_result_bytes as result_bytes, handle_fixture, phased, tones_375, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -64,31 +64,8 @@ POOL = 48                    # distinct groups of a case
 LIVE = {5461: 3, 8193: 1, 16385: 1}   # live waves of a partial last block (wpg = most in every launch here)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = TC.SHAPE_OF_R[Rn]
-            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, TC.SHAPE_OF_R, Rn, tones_375(K)))
 
 
 # ---- the launch arithmetic, restated from the kernels' comments ---------------------
@@ -222,7 +199,7 @@ def late_bytes(refs, idx, max_len, step):
 
 def run_check(torch, d, case, hits, packed, counts, body=True, poison=TC.POISON, guard=False):
     shape = case[0]
-    N = TC.symbols_for(shape["B"], F.bits_per_symbol(shape["K"]))
+    N = TC.row_symbols(shape["B"], F.bits_per_symbol(shape["K"]))
     return TC.Run(torch, hits, packed, counts, body=body, poison=poison, guard=guard)(
         d, shape["L"], N, shape["h"], shape["kind"])
 
@@ -518,7 +495,7 @@ def test_decode_fallback_mapped(A, torch, handle):
 # ---- Part 3: the chain behind a sparse segmented scan -----------------------------------------
 
 CH = dict(S=20000, Rn=1, K=16, L=8, h=1, kind=C.CRC16, cap=2, planted=64, short=300)
-CH_N = X.symbols_for(6, 4, CH["h"], CH["kind"])
+CH_N = Z.symbols_for(6, 4, CH["h"], CH["kind"], X.CONV_K7)
 CH_ST, CH_BD, CH_MAX = X.row_shape(CH_N, 4, CH["h"], CH["kind"])
 
 
@@ -576,7 +553,7 @@ def chain_reference(A):
                 packed=np.full((S, cap, B), 0xFF, np.uint8))
     # segments without windows: the closed form of a short segment (test_max_segments checks its
     # all-hit cousin the same way), held to the reference on a sample below
-    empty = np.zeros((), TS.RESULT_DTYPE)
+    empty = np.zeros((), F.RESULT_DTYPE)
     empty["phases"], empty["tail_window"] = Rn, -1
     res = np.tile(np.frombuffer(empty.tobytes(), np.uint8), (S, 1))
     some = np.flatnonzero(count > 0)
@@ -683,21 +660,21 @@ def test_chain_behind_sparse_scan(A, torch, handle):
     ch = Chain(A, torch, handle(CH["Rn"], CH["K"]))
     ch.scan()
     ch.later()
-    TF.same_dict(ch.results(Chain.SCAN + Chain.LATER), want, "eager")
+    TF.same(ch.results(Chain.SCAN + Chain.LATER), want, "eager")
     side = torch.cuda.Stream()
     ch.poison(Chain.LATER + ("fwork",))
     torch.cuda.synchronize()
     with torch.cuda.stream(side):
         ch.later(stream=side.cuda_stream)                 # an eager call of the shape on the stream first
         side.synchronize()
-    TF.same_dict(ch.results(Chain.LATER), want, "side stream")
+    TF.same(ch.results(Chain.LATER), want, "side stream")
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=side):
         ch.later(stream=torch.cuda.current_stream().cuda_stream)
     ch.poison(Chain.LATER + ("fwork",))
     torch.cuda.synchronize()
     g.replay()
-    TF.same_dict(ch.results(Chain.SCAN + Chain.LATER), want, "replay")
+    TF.same(ch.results(Chain.SCAN + Chain.LATER), want, "replay")
 
 
 # ---- Part 4: the other launches on the same walk (csrc/frame_rows.h) -----------------------------

@@ -19,64 +19,26 @@ import functools
 import numpy as np
 import pytest
 
+import acquire_ref as AR
 import acquire_segments_ref as SR
 import frames_ref as F
 import frames_segments_ref as FS
 import guards as G
-from test_gpu_frames import SHAPE_OF_R, float_inputs, make_inputs, plant, result_bytes
+from test_gpu_frames import SHAPE_OF_R, float_inputs, make_inputs, plant
+from gpu_support import (LEAD, check_frames as check, frames_result_bytes as result_bytes, guarded, handle_fixture,
+                         parse_frames as parse, phased, tables, tones_375, torch)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 RS, KS = (1, 4, 64), (1, 2, 16)
-RES_BYTES = 64 * 8 + 48
-ARES_BYTES = 64 * 8 + 56
+RES_BYTES = F.RESULT_DTYPE.itemsize
+ARES_BYTES = AR.RESULT_DTYPE.itemsize
+PREFIX = F.RESULT_DTYPE.fields["n_hits"][1]     # metric[64], phases, phase, per_phase: as demod_acquire_result_t
 HIT = 16
-LEAD = 4096          # guard bytes per side (a multiple of 8: d_hits, d_results and d_work stay aligned)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(R, K): one Demodulator per (R, K), closed with the module."""
-    def get(Rn, K):
-        if (Rn, K) not in _HANDLES:
-            n, hop = SHAPE_OF_R[Rn]
-            freqs = tuple(1500.0 + 375.0 * i for i in range(K))
-            _HANDLES[Rn, K] = A.Demodulator(n=n, hop=hop, freqs=freqs)
-            assert _HANDLES[Rn, K].n // _HANDLES[Rn, K].hop == Rn
-        return _HANDLES[Rn, K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def parse(A, raw):
-    return A.frames_result_dict(A.DemodFramesResult.from_buffer_copy(bytes(raw)))
-
-
-def tables(torch, first, count):
-    """The uint64 / uint32 tables as the int64 / int32 tensors that carry them."""
-    f = np.ascontiguousarray(first, np.uint64).view(np.int64)
-    c = np.ascontiguousarray(count, np.uint32).view(np.int32)
-    return torch.from_numpy(f.copy()).cuda(), torch.from_numpy(c.copy()).cuda()
-
-
-def guarded(torch, numel, lead, poison):
-    """guards.guarded for a uint8 output; (None, a check of nothing) for an empty one."""
-    if numel == 0:
-        return None, lambda written: None
-    return G.guarded(torch, numel, torch.uint8, lead, LEAD, poison)
+# handle(R, K): one Demodulator per (R, K), closed with the module.
+handle = handle_fixture(lambda A, Rn, K: phased(A, SHAPE_OF_R, Rn, tones_375(K)))
 
 
 class Runner:
@@ -134,21 +96,6 @@ class Runner:
                             payload=pay[s] if g_pay is not None else None,
                             packed=pak[s] if g_pak is not None else None))
         return out
-
-
-def check(A, out, ref, cap, poison=0xFF):
-    """One segment: result bytes, hits, payload rows and packed rows equal the
-    reference's; rows past n_written still hold the poison."""
-    r_hits, r_pay, r_pak, r_res = ref
-    r_res = dict(r_res, n_written=min(r_res["n_hits"], cap))
-    nw = r_res["n_written"]
-    assert out["raw"] == result_bytes(A, r_res), (out["res"], r_res)
-    assert out["hits"][:nw].tobytes() == r_hits[:nw].tobytes()
-    assert (out["hits"][nw:].view(np.uint8) == poison).all(), "hit rows past n_written were written"
-    for got, want in ((out["payload"], r_pay), (out["packed"], r_pak)):
-        if got is not None:
-            assert np.array_equal(got[:nw], want[:nw])
-            assert (got[nw:] == poison).all(), "rows past n_written were written"
 
 
 def check_all(A, outs, refs, cap, poison=0xFF):
@@ -226,7 +173,7 @@ def phase_fields_agree(A, torch, d, Wb, K, Rn, first, count, word, me, N):
     torch.cuda.synchronize()
     araw = d_ares.cpu().numpy().tobytes()
     for s in range(S):
-        assert fgot[s]["raw"][:528] == araw[s * ARES_BYTES:s * ARES_BYTES + 528], s
+        assert fgot[s]["raw"][:PREFIX] == araw[s * ARES_BYTES:s * ARES_BYTES + PREFIX], s
 
 
 # ---- 1. equivalence ----------------------------------------------------------
@@ -530,11 +477,6 @@ def test_long_segments(A, torch, handle, Rn, K):
 
 # ---- 6. the most segments ------------------------------------------------------
 
-RESULT_DTYPE = np.dtype([("metric", "<f8", 64), ("phases", "<u4"), ("phase", "<u4"), ("per_phase", "<u8"),
-                         ("n_hits", "<u8"), ("n_written", "<u8"), ("tail_window", "<i8"),
-                         ("tail_errors", "<u4"), ("reserved", "<u4")])
-
-
 def test_max_segments(A, torch, handle):
     """DEMOD_MAX_SEGMENTS segments of 0, 1 or 2 windows at R = 1, L = 1, K = 1,
     all symbols 0: every window is a hit (the all-hit case), more tiles than the
@@ -544,7 +486,7 @@ def test_max_segments(A, torch, handle):
     form against the reference on a sample."""
     Rn, K, cap, N = 1, 1, 2, 1
     S = A.DEMOD_MAX_SEGMENTS
-    assert RESULT_DTYPE.itemsize == RES_BYTES
+    assert F.RESULT_DTYPE.itemsize == RES_BYTES
     rng = np.random.default_rng(65536)
     count = rng.integers(0, 3, S)
     first = np.cumsum(count + rng.integers(0, 2, S)) - count
@@ -564,7 +506,7 @@ def test_max_segments(A, torch, handle):
                                 g_pak, cap, g_res, g_work)
     for chk in (chk_hits, chk_pay, chk_pak, chk_res, chk_work):
         chk(written=False)
-    res = np.frombuffer(g_res.cpu().numpy().tobytes(), RESULT_DTYPE)
+    res = np.frombuffer(g_res.cpu().numpy().tobytes(), F.RESULT_DTYPE)
     hits = g_hits.cpu().numpy().view(F.HIT_DTYPE).reshape(S, cap)
     pay, pak = g_pay.cpu().numpy().reshape(S, cap), g_pak.cpu().numpy().reshape(S, cap)
     pw = P[:, 0].astype(np.float64)

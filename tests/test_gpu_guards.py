@@ -43,6 +43,7 @@ import pytest
 import guards as G
 from decision import check_decisions
 from guards import F32_GUARD, F32_POISON, MAG_TOL, SYM_GUARD, SYM_POISON
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -118,14 +119,6 @@ for _hop in (200, 8):
 # FFT detector, tones only (it rescues in its own kernel)
 for _hop in (1024, 256, 200):
     PATHS[f"fft_fsk8_hop{_hop}"] = Path(FSK8, N, _hop, FFT, FFT, "fft", 0, 1, dict())
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 @functools.lru_cache(maxsize=None)

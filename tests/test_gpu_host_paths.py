@@ -8,20 +8,13 @@ including the sizes either side of each boundary.
 """
 import numpy as np
 import pytest
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ZERO_COPY_SAMPLES = 1 << 14
 SMALL_SAMPLES = 1 << 21
 K8_ODD = tuple(46.875 * (32 + 9 * i) for i in range(8))   # residue detector
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def windows_for(samples, n, hop):

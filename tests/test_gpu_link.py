@@ -17,6 +17,7 @@ import pytest
 import link_ref as LR
 import rx_ref as X
 import tx_ref as T
+from gpu_support import handle_fixture, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -25,32 +26,12 @@ S = LR.DEV_STREAMS
 
 
 @pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-@pytest.fixture(scope="module")
 def lut(O):
     return O.sine_lut()
 
 
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(K): one Demodulator (n 1024, hop 256) per K, closed with the module."""
-    def get(K):
-        if K not in _HANDLES:
-            _HANDLES[K] = A.Demodulator(n=N_FFT, hop=HOP, freqs=T.loop_tones(K))
-        return _HANDLES[K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
+# handle(K): one Demodulator (n 1024, hop 256) per K, closed with the module.
+handle = handle_fixture(lambda A, K: A.Demodulator(n=N_FFT, hop=HOP, freqs=T.loop_tones(K)))
 
 
 def tx_cfg(A, c):

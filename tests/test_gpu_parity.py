@@ -8,18 +8,11 @@ import numpy as np
 import pytest
 
 from decision import check_decisions
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 MAG_TOL = 1e-5  # relative to the window's max_k P_ref (north_star)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def rel_err(mag, P):

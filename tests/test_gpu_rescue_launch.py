@@ -20,20 +20,13 @@ import pytest
 import error_model as EM
 from decision import check_decisions
 from error_model import mixed_stream
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 N = 1024
 K16 = tuple(46.875 * (20 + 7 * i) for i in range(16))
 FOLD3 = (8 * EM.BIN, 16 * EM.BIN, 504 * EM.BIN)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def run(A, O, freqs, hop, W, seed, expect_slide=True):

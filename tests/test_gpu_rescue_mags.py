@@ -48,6 +48,7 @@ import pytest
 import error_model as EM
 import guards as G
 from decision import check_decisions
+from gpu_support import torch  # noqa: F401
 
 gpu = pytest.mark.gpu
 
@@ -96,14 +97,6 @@ def case_env(case):
     segments (tests/test_gpu_error_model.py
     test_rescue_launch_equals_in_kernel_rescue)."""
     return (("FSKD_PASS0_FOLD", "0"),) if case[0] == "FSK2_FREQS" and case[1] == GOERTZEL else ()
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 _FIXTURES = {}

@@ -8,10 +8,12 @@ and demod_rx_push in a plain and a coded parity mode against the host chain
 demod_tx_frame_symbols, with a loop into the receiver.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_ref as F
 import guards as G
@@ -19,46 +21,17 @@ import rs_cases as TC
 import rs_chain_ref as H
 import rs_ref as R
 import tx_ref as T
+from gpu_support import handle_fixture, results_bytes, same as whole_same, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-RES_BYTES = 64 * 8 + 48
-N_HITS_AT, N_WRITTEN_AT = 528, 536
+RES_BYTES = F.RESULT_DTYPE.itemsize
 GUARD = 4096
 POISON = 0xFF
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(K): one Demodulator (n 1024, hop 256) per K, closed with the module."""
-    def get(K):
-        if K not in _HANDLES:
-            _HANDLES[K] = A.Demodulator(n=1024, hop=256, freqs=T.loop_tones(K))
-        return _HANDLES[K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def results_bytes(n_written):
-    """[G] demod_frames_result_t with n_hits = n_written = the given counts, the rest 0."""
-    res = np.zeros((len(n_written), RES_BYTES), np.uint8)
-    raw = np.array([int(n) for n in n_written], "<u8").view(np.uint8).reshape(-1, 8)
-    res[:, N_HITS_AT:N_HITS_AT + 8] = raw
-    res[:, N_WRITTEN_AT:N_WRITTEN_AT + 8] = raw
-    return res
+# handle(K): one Demodulator (n 1024, hop 256) per K, closed with the module.
+handle = handle_fixture(lambda A, K: A.Demodulator(n=1024, hop=256, freqs=T.loop_tones(K)))
 
 
 def host_stage(A, rows, counts, max_frames, h, kind, fec):
@@ -95,10 +68,7 @@ def run_stage(A, torch, d, rows, counts, max_frames, N, h, kind, fec, stream=0):
     return (d_rows.cpu().numpy().reshape(n_groups, max_frames, W), d_rs.cpu().numpy().reshape(n_groups, max_frames, 16))
 
 
-def same(got, want, what=""):
-    for name, g, w in zip(("rows", "records"), got, want):
-        bad = np.argwhere(g != w)
-        assert bad.size == 0, (what, name, len(bad), bad[:4].tolist())
+same = functools.partial(whole_same, names=("rows", "records"))
 
 
 def case_rows(A, flag, h, kind, W, rng, lengths=None, patterns=TC.PATTERNS):
@@ -237,7 +207,7 @@ def test_capture_behind_the_scan(A, torch, handle):
     d = handle(2)
     K, Rn, h, kind, fec, L = 2, 4, 1, C.CRC16, R.FLAG16, 16
     lens = (0, 30, 250, 7)
-    N = H.symbols_for(A, max(lens), 1, h, kind, fec) + 3
+    N = Z.symbols_for(max(lens), 1, h, kind, fec) + 3
     contents = []
     for seed in (1, 2):
         rng = np.random.default_rng(seed)
@@ -416,7 +386,7 @@ def test_refusals_receiver_and_transmitter(A, torch, handle):
         with A.Receiver(S, A.make_rx_cfg(fec=fec, **rx_base), n=1024, hop=256, freqs=T.loop_tones(2)) as rx:
             assert rx.sizes["max_len"] == H.max_len(A, 1024, 1, 1, C.CRC16, fec)
         with A.Transmitter(S, x, n=1024, hop=256, freqs=T.loop_tones(2)) as tx:
-            assert tx.sizes["max_symbols"] == 5 + H.span(A, 16, 1, 1, C.CRC16, fec)
+            assert tx.sizes["max_symbols"] == 5 + Z.span(16, 1, 1, C.CRC16, fec)
     torch.cuda.synchronize()
     assert bool((d_ring == POISON).all())
 
@@ -441,7 +411,7 @@ def e2e_case(A, fec):
         rng = np.random.default_rng(fec)
         word = rng.integers(0, K, E2E_L).astype(np.uint8)
         datas = [rng.integers(0, 256, m).astype(np.uint8).tobytes() for m in lens]
-        N = H.symbols_for(A, max(lens), bits, h, kind, fec) + 3
+        N = Z.symbols_for(max(lens), bits, h, kind, fec) + 3
         if fec & 0xFF:
             def plant(f, Sp, rng):
                 return list(range(100, 110)) if Sp > 300 else []
@@ -472,6 +442,7 @@ def test_frames_coded(A, torch, handle, fec):
     sym, P = d_sym.cpu().numpy(), d_mag.cpu().numpy().reshape(Wn, K)
     hits, before, after, rec, chk, res = H.chain(A, sym, P, 4, word, 1, N, h, kind, fec)
     check, kept, bodies, summ = chk
+    summ = dict(zip(summ.dtype.names, summ.tolist()))
     assert bodies == c["datas"] and [int(hits["window"][i]) for i in kept] == [4 * a for a in c["at"]]
     assert int(rec["corrected"][kept].sum()) > 0 and not np.array_equal(before, after)   # the outer code did it
     for pcm in (x, d_pcm):
@@ -525,7 +496,7 @@ def test_transmitter_symbols(A, torch, fec, K):
     rng = np.random.default_rng(fec + K)
     datas = [rng.integers(0, 256, ln).astype(np.uint8).tobytes() for ln in lens]
     bits = F.bits_per_symbol(K)
-    counts = [11 + H.span(A, ln, bits, h, kind, fec) for ln in lens]
+    counts = [11 + Z.span(ln, bits, h, kind, fec) for ln in lens]
     ring = sum(counts) + 9
     x = A.make_tx_cfg(word, h, kind, fec, max(lens), 0, (0,), 8000, 0, 0, ring, len(lens), 2880)
     want = [A.tx_frame_symbols(x, K, data) for data in datas]
@@ -572,8 +543,8 @@ def test_loop_into_the_receiver(A, torch, fec, length):
     word = rng.integers(0, K, L).astype(np.uint8)
     datas = [rng.integers(0, 256, m).astype(np.uint8).tobytes() for m in (length, 5)]
     gap = 3
-    per = [L + H.span(A, len(dd), 3, h, kind, fec) + gap for dd in datas]
-    N = H.symbols_for(A, length, 3, h, kind, fec)
+    per = [L + Z.span(len(dd), 3, h, kind, fec) + gap for dd in datas]
+    N = Z.symbols_for(length, 3, h, kind, fec)
     total = -(-(3 + sum(per) + N + 8) * n // packet) * packet
     x = A.make_tx_cfg(word, h, kind, fec, length, gap, (0, 1), 8000, 400, 77, sum(per) + 5, len(datas), packet)
     freqs = T.loop_tones(K)

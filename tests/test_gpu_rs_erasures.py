@@ -8,10 +8,12 @@ one captured graph; demod_frames_coded and demod_rx_push through a dropout; and
 the refusals of the device entries.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 import frames_fec_ref as X
 import frames_ref as F
@@ -21,46 +23,17 @@ import rs_chain_ref as H
 import rs_erasure_cases as EC
 import rs_ref as R
 import tx_ref as T
+from gpu_support import handle_fixture, results_bytes, same as whole_same, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-RES_BYTES = 64 * 8 + 48
-N_HITS_AT, N_WRITTEN_AT = 528, 536
+RES_BYTES = F.RESULT_DTYPE.itemsize
 GUARD = 4096
 POISONS = (0xFF, 0x5A)
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(K, hop): one Demodulator (n 1024) per K and hop, closed with the module."""
-    def get(K, hop=256):
-        if (K, hop) not in _HANDLES:
-            _HANDLES[K, hop] = A.Demodulator(n=1024, hop=hop, freqs=T.loop_tones(K))
-        return _HANDLES[K, hop]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
-
-
-def results_bytes(n_written):
-    """[G] demod_frames_result_t with n_hits = n_written = the given counts, the rest 0."""
-    res = np.zeros((len(n_written), RES_BYTES), np.uint8)
-    raw = np.array([int(n) for n in n_written], "<u8").view(np.uint8).reshape(-1, 8)
-    res[:, N_HITS_AT:N_HITS_AT + 8] = raw
-    res[:, N_WRITTEN_AT:N_WRITTEN_AT + 8] = raw
-    return res
+# handle(K, hop): one Demodulator (n 1024) per K and hop, closed with the module.
+handle = handle_fixture(lambda A, K, hop=256: A.Demodulator(n=1024, hop=hop, freqs=T.loop_tones(K)))
 
 
 def as_i64(torch, words):
@@ -115,10 +88,7 @@ def run_stage(A, torch, d, rows, masks, counts, max_frames, N, h, kind, fec, poi
             d_erec.cpu().numpy().reshape(*shape, 16))
 
 
-def same(got, want, what=""):
-    for name, g, w in zip(("rows", "records", "erasure records"), got, want):
-        bad = np.argwhere(g != w)
-        assert bad.size == 0, (what, name, len(bad), bad[:4].tolist())
+same = functools.partial(whole_same, names=("rows", "records", "erasure records"))
 
 
 def planted_rows(A, flag, h, kind, length, W, rng):
@@ -440,7 +410,8 @@ def host_chain(A, sym, P, Rn, word, N, h, kind, fec, level):
             got, r, _ = A.rs_frame_decode(before[i], h, kind, fec)
         after[i] = got
         rec[i] = tuple(r[f] for f in A.FRAME_RS_DTYPE.names)
-    chk = H.check_group(A, hits["window"], after, L, Rn, bits, h, kind, fec, H.max_len(A, N, bits, h, kind, fec))
+    chk = C.check_group(hits["window"], after, L, Rn, Z.span_of(bits, h, kind, fec), H.max_len(A, N, bits, h, kind, fec),
+                        h, kind)
     return dict(hits=hits, before=before, after=after, rec=rec, erec=erec, masks=masks, chk=chk, res=res)
 
 
@@ -452,7 +423,7 @@ def test_capture_scan_producer_stage_check(A, torch, handle):
     d = handle(2)
     K, Rn, h, kind, fec, level = 2, 4, 1, C.CRC16, R.FLAG16, 16
     lens = (0, 60, 200, 7)
-    N = H.symbols_for(A, max(lens), 1, h, kind, fec) + 3
+    N = Z.symbols_for(max(lens), 1, h, kind, fec) + 3
     word = np.array([0, 1, 1, 0, 1, 0, 0, 1, 1, 1, 0, 0, 1, 0, 1, 1], np.uint8)
     L = len(word)
     contents = []
@@ -536,7 +507,7 @@ def e2e_case(A):
         K, h, kind, fec, lens = 2, 1, C.CRC16, R.FLAG16, (5, 60, 7)
         rng = np.random.default_rng(12)
         word = rng.integers(0, K, 16).astype(np.uint8)
-        N = H.symbols_for(A, max(lens), 1, h, kind, fec) + 3
+        N = Z.symbols_for(max(lens), 1, h, kind, fec) + 3
         truth, at, lost, datas = dropout_stream(A, K, fec, h, kind, lens, N, word, rng, which=1, first_byte=40)
         pcm = H.pcm_of(T.loop_tones(K), truth, 21)
         pcm[lost[0] * 1024:(lost[-1] + 1) * 1024] = 0
@@ -562,6 +533,7 @@ def test_frames_coded_through_a_dropout(A, torch, handle):
     for level, datas in ((1, c["datas"]), (0, c["datas"][:1] + c["datas"][2:])):
         want = host_chain(A, sym, P, 4, word, N, h, kind, fec, level)
         check, kept, bodies, summ = want["chk"]
+        summ = dict(zip(summ.dtype.names, summ.tolist()))
         assert bodies == datas
         if level:
             er = want["erec"][kept[1]]
@@ -627,7 +599,7 @@ def test_widest_rows_through_the_one_shot_call_and_the_receiver(A, torch):
     rng = np.random.default_rng(32)
     word = rng.integers(0, K, 16).astype(np.uint8)
     N = 8 * 4710
-    assert H.symbols_for(A, 4096, 1, h, kind, fec) == N
+    assert Z.symbols_for(4096, 1, h, kind, fec) == N
     truth, at, lost, datas = dropout_stream(A, K, fec, h, kind, (4096,), N, word, rng, which=0, first_byte=100,
                                             n_bytes=40)
     x = H.pcm_of(T.loop_tones(K), truth, 5, n=n)
@@ -642,6 +614,7 @@ def test_widest_rows_through_the_one_shot_call_and_the_receiver(A, torch):
         sym, P = d_sym.cpu().numpy(), d_mag.cpu().numpy().reshape(Wn, K)
         want = host_chain(A, sym, P, 1, word, N, h, kind, fec, 1)
         check, kept, bodies, summ = want["chk"]
+        summ = dict(zip(summ.dtype.names, summ.tolist()))
         assert bodies == datas and len(kept) == 1
         er = want["erec"][kept[0]]
         assert int(er["erased"]) == 40 and int(er["used"]) >= 19 - 1 and want["masks"].shape[1] == 74

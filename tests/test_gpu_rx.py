@@ -21,6 +21,7 @@ import frames_ref as F
 import guards as G
 import link_ref as LR
 import rx_ref as X
+from gpu_support import handle_fixture, same, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -32,32 +33,12 @@ R = N // HOP
 H, KIND, L_WORD = 1, C.CRC16, 16
 
 
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
-
-
 def tones(K):
     return tuple(1500.0 + 375.0 * i for i in range(K))
 
 
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(K): one Demodulator (n 1024, hop 256) per K, closed with the module."""
-    def get(K):
-        if K not in _HANDLES:
-            _HANDLES[K] = A.Demodulator(n=N, hop=HOP, freqs=tones(K))
-        return _HANDLES[K]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
+# handle(K): one Demodulator (n 1024, hop 256) per K, closed with the module.
+handle = handle_fixture(lambda A, K: A.Demodulator(n=N, hop=HOP, freqs=tones(K)))
 
 
 class Outs:
@@ -83,13 +64,6 @@ class Outs:
         self.torch.cuda.synchronize()
         for chk in self.checks:
             chk(written=False)
-
-
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad.size, bad[:6].tolist(), got[bad[:6]].tolist(), want[bad[:6]].tolist())
 
 
 # ---- advance ---------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from decision import check_decisions
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -32,14 +33,6 @@ FSK8_ODD = tuple(46.875 * (32 + 9 * i) for i in range(8))
 NONINT3 = (1234.5, 2345.6, 4321.0)
 REINSCH2 = (30.0, 23950.0)          # |sin w| < 0.1: the Reinsch-form recurrence
 K16 = tuple(46.875 * (20 + 7 * i) for i in range(16))
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def wt(hop):

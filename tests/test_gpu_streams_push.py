@@ -9,18 +9,11 @@ import numpy as np
 import pytest
 
 from decision import check_decisions
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 MAG_TOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def streams_vs_single(A, O, n_streams, freqs, hop, channels=1, mode=0, lead_in=0, method=0,

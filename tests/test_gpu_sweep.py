@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from decision import check_decisions
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -37,14 +38,6 @@ def mag_denom(P, mono, n, hop):
     starts = np.arange(P.shape[0]) * hop
     energy = n * (c2[starts + n] - c2[starts]) / 2
     return np.maximum(np.maximum(P.max(axis=1), energy), 1e-30)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def draw_case(i, fft_nonint=False):

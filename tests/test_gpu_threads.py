@@ -7,16 +7,9 @@ import threading
 
 import numpy as np
 import pytest
+from gpu_support import torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 def test_concurrent_handles(A, O, torch):

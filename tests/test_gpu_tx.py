@@ -19,19 +19,12 @@ import frames_check_ref as C
 import guards as G
 import rx_ref as X
 import tx_ref as T
+from gpu_support import handle_fixture, same, torch  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LEAD = 4096                      # guard bytes per side (a multiple of 16: aligned outputs stay aligned)
 POISONS = (0xFF, 0x5A)
-
-
-@pytest.fixture(scope="module")
-def torch():
-    import torch as t
-    if not t.cuda.is_available():
-        pytest.skip("no GPU visible")
-    return t
 
 
 @pytest.fixture(scope="module")
@@ -43,20 +36,8 @@ def tones(K):
     return T.loop_tones(K)
 
 
-_HANDLES = {}
-
-
-@pytest.fixture(scope="module")
-def handle(A, torch):
-    """handle(K, n): one Demodulator (hop n / 4) per (K, n), closed with the module."""
-    def get(K, n):
-        if (K, n) not in _HANDLES:
-            _HANDLES[K, n] = A.Demodulator(n=n, hop=n // 4, freqs=tones(K))
-        return _HANDLES[K, n]
-    yield get
-    for d in _HANDLES.values():
-        d.close()
-    _HANDLES.clear()
+# handle(K, n): one Demodulator (hop n / 4) per (K, n), closed with the module.
+handle = handle_fixture(lambda A, K, n: A.Demodulator(n=n, hop=n // 4, freqs=tones(K)))
 
 
 class Outs:
@@ -77,13 +58,6 @@ class Outs:
         self.torch.cuda.synchronize()
         for chk in self.checks:
             chk(written=False)
-
-
-def same(got, want, what):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad.size, bad[:6].tolist(), got[bad[:6]].tolist(), want[bad[:6]].tolist())
 
 
 def host(t, dtype):

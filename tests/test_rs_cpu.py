@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fec_modes_ref as Z
 import frames_check_ref as C
 import rs_cases as RC
 import rs_ref as R
@@ -87,6 +88,37 @@ def test_layout_against_a_count(A, flag):
                     assert A.rs_max_len(W, h, kind, flag) == want, (W, h, kind)
             # without a parity flag the frame is the checked frame
             assert A.rs_frame_size(10, h, kind, 1) == h + 10 + c and A.rs_max_len(40, h, kind, 0x41) == 40 - h - c
+
+
+def test_reference_span_equals_the_library(A):
+    """fec_modes_ref.span, the span every check reference and the receiver's
+    reference use, against demod_fec_frame_symbols and against
+    demod_tx_frame_symbol_count less the word: every mode, bits 1 to 4, both
+    header sizes and CRC kinds, at the lengths where the outer code's layout
+    changes and where the convolutional modes' kept bits cross a block.
+    demod_fec_frame_symbols refuses a mode without the convolutional code."""
+    word, n = (1, 0, 1), 0
+    for fec in A.RS_MODES:
+        conv = fec & 0xFF
+        for h in (1, 2):
+            for kind in KINDS:
+                c = C.CRC_BYTES[kind]
+                lens = set(Z.edge_lengths(255 if h == 1 else 600, h, kind, conv or Z.CONV_K7))
+                for P in R.PARITY.values():
+                    lens.update(edge_lengths(h, c, P))
+                tx = A.make_tx_cfg(word, h, kind, fec, 4096)
+                for length in sorted(lens):
+                    for bits in (1, 2, 3, 4):
+                        want = Z.span(length, bits, h, kind, fec)
+                        what = (fec, h, kind, length, bits)
+                        assert A.tx_frame_symbol_count(tx, 1 << bits, length) - len(word) == want, what
+                        if conv:
+                            assert A.fec_frame_symbols(length, h, kind, bits, fec) == want, what
+                        else:
+                            with pytest.raises(A.DemodError):
+                                A.fec_frame_symbols(length, h, kind, bits, fec)
+                        n += 1
+    assert n > 20 * 2 * 2 * 4 * 8
 
 
 # ---- encoder and decoder against the reference -----------------------------------------
